@@ -4,6 +4,7 @@
     python bench.py --gpus 1 --steps 3 --warmup 1
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR     # + what the last timed step returned, DIR/enhanced_spec.npy
 
 One "step" = one full pass of the hot path over one batch: the 30-step predictor-corrector sampler
 (reverse_diffusion + Langevin x1, snr 0.5 => 60 score-network evaluations) on B=8 synthetic 4 s / 24 kHz utterances
@@ -38,6 +39,26 @@ PEAK_HBM_TBPS = 8.0                  # HBM3E (MI355X_MICROARCH.md); ~6.3 TB/s is
 
 
 from universal_speech_enhancement_amd.testing.cpu import usable_cores  # noqa: E402
+
+DUMP_LIMIT_BYTES = 64 << 20          # --dump-outputs: at most this much in all
+
+
+def dump_outputs(d, outputs, limit=DUMP_LIMIT_BYTES):
+    """Writes each named complex64 [B,1,F,T'] output as d/<name>.npy, float32 [..., 2] (real, imaginary).  Above `limit` in all, a
+    fixed sample is kept: the first utterances, each array its share of the limit, and the first frames of the first utterance
+    if a single one is larger still."""
+    os.makedirs(d, exist_ok=True)
+    share = limit // max(len(outputs), 1)
+    for name, x in outputs.items():
+        a = torch.view_as_real(x.detach().cpu()).numpy().astype(np.float32, copy=False)
+        if a.nbytes > share:
+            per_item = a[0].nbytes
+            if per_item <= share:
+                a = a[:share // per_item]
+            else:
+                per_frame = a[0, :, :, 0].nbytes
+                a = a[:1, :, :, :max(share // per_frame, 1)]
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a))
 
 
 def cpu_baseline(sd_np):
@@ -167,9 +188,14 @@ def main():
     ap.add_argument("--roofline-only", action="store_true",
                     help="skip the timed sampler steps; run only the per-launch measurement of the dominant kernel (for "
                          "`rocprofv3 --kernel-trace --stats -- python bench.py --roofline-only`, see profiles/README.md)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (rank 0: the sampled spectrogram, complex64 "
+                         "[B,1,F,T'] as float32 [..., 2]) as DIR/enhanced_spec.npy, at most 64 MB; same arguments, same inputs")
     a = ap.parse_args()
     if a.roofline_only:
         a.steps, a.warmup, a.no_cpu_baseline, a.no_secondary = 0, 0, True, True
+    if a.dump_outputs and a.steps < 1:
+        raise SystemExit("--dump-outputs needs at least one timed step")
     if a.config == 3:
         a.batch, a.N = 16, 200
     elif a.config == 4:
@@ -263,6 +289,8 @@ def main():
     barrier()
     dt_local = time.perf_counter() - t0
     dt = D.max_over_ranks(dt_local, device=dev)
+    if a.dump_outputs and rank == 0:                            # (outside the timed region; before anything else runs on the engine)
+        dump_outputs(a.dump_outputs, {"enhanced_spec": out})
     # self-verification of an N-GPU line: what RCCL saw (world size after init) and, per rank, its own step time and the device it ran on
     me = {"rank": rank, "local_rank": local, "ms_per_step": round(dt_local / max(a.steps, 1) * 1e3, 2), "device": torch.cuda.get_device_name(local),
           "pci_bus_id": pci_bus_id(local)}

@@ -7,6 +7,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -55,16 +56,18 @@ def test_rccl_path_at_world_size_one():
     assert r.returncode == 0 and "RCCL_WORLD1_OK" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
 
 
-def test_bench_under_the_launcher_with_one_process():
+def test_bench_under_the_launcher_with_one_process(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1",
-           "--batch", "2", "--seconds", "1", "--N", "2", "--no-cpu-baseline"]
+           "--batch", "2", "--seconds", "1", "--N", "2", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)]
     env = dict(os.environ); env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
     res = json.loads(line)
     assert res["n_gpus"] == 1 and res["value"] > 0 and res["config"]["parallelism"] == "utterance-sharded x1"
+    out = np.load(tmp_path / "enhanced_spec.npy")         # what the timed step returned: the 2 utterances as float32 (real, imaginary)
+    assert out.dtype == np.float32 and out.shape == (2, 1, 512, res["config"]["padded_frames_per_utt"], 2) and np.isfinite(out).all()
 
 
 _TRAIN_WORKER = r"""
