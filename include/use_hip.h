@@ -207,7 +207,12 @@ int use_conv_bench(const use_conv_case* c, float* out_host, float* stats_host, d
  *   res-block (ResnetBlockBigGANpp, layerspp.py:282-314); channel counts are multiples of 32 (zero-pad smaller ones); `w` is the
  *   reference's [Cout][Cin][3][3] (ntaps 9) or [Cout][Cin] (ntaps 1) tensor, `w2` [Cout][XC]; coef = GroupNorm folded to (a, b) per
  *   (item, channel) or null; stats (zeroed by the caller) receives the fixed-point GroupNorm totals of the output.  variant: 0 = the
- *   library's dispatcher, 1 generic, 2 conv_v2, 4 conv_v4, 7 conv_sk.  Synchronises the stream.
+ *   library's dispatcher, 1 generic, 2 conv_v2, 4 conv_v4, 5 conv_v5, 7 conv_sk; a forced variant that cannot run the case returns
+ *   USE_E_INVALID naming the violated condition.  Synchronises the stream.
+ *   Trailing fields (zero: off): pyr / w4 / b4 add the Combine 1x1 over a 4-channel fp32 map after the out_scale (the order of
+ *   ConvArgs: out = ((conv + shortcut + bias + temb) + res) * out_scale + (pyr . w4 + b4)); gn_st0 (with coef null) makes the kernel
+ *   finalise GroupNorm(gn_groups, eps gn_eps) of concat(src0, src1) itself from the totals its producers accumulated, with the affine
+ *   gn_gamma / gn_beta, as the engine does on the small maps; temb_bstride is the distance between temb's rows (0: Cout, -1: shared).
  * use_op_fir: upsample_2d / downsample_2d with the [1,3,3,1] kernel (up_or_down_sampling.py:202-264); out_act = FIR(act(a x + b)),
  *   out_raw = FIR(x) (either may be null).
  * use_op_attention: softmax(q k^T / sqrt(C)) v per item (AttnBlockpp core, layerspp.py:84-88), q/k/v/out [B][N][C].
@@ -225,6 +230,15 @@ typedef struct use_conv_op {
     float out_scale;
     void* out;
     long long* stats;
+    /* optional trailing fields: zero = off (the behaviour before they existed) */
+    const float* pyr;                     /* device fp32 [B][H][W][4] or null: + pyr . w4[co] + b4[co] (Combine 'sum', layerspp.py:50-55) */
+    const float* w4;                      /* host fp32 [Cout][4] */
+    const float* b4;                      /* host fp32 [Cout] or null */
+    const long long *gn_st0, *gn_st1;     /* coef == null and gn_st0 set: GroupNorm finalised in the kernel from the sources' totals */
+    const float *gn_gamma, *gn_beta;      /*   (device [B][C0][2], [B][C1][2] as `stats` accumulates them) and the affine (device [C0+C1]) */
+    int gn_groups;                        /*   groups over C0+C1 channels */
+    float gn_eps;
+    int temb_bstride;                     /* elements between temb's batch rows: 0 = Cout, -1 = one row shared by the batch */
 } use_conv_op;
 int use_op_conv(const use_conv_op* c, use_stream_t stream);
 /* use_op_conv_dev: the same operator for the training path (reference SGMSE_module.py:46-54 -> model_wrapper.py:147-208, where the

@@ -37,7 +37,9 @@ class UseConvCase(C.Structure):
 class UseConvOp(C.Structure):
     _fields_ = ([(k, C.c_int) for k in ("B", "H", "W", "C0", "C1", "Cout", "XC0", "XC1", "ntaps", "act", "dtype", "out_dtype", "variant")] +
                 [(k, C.c_void_p) for k in ("src0", "src1", "coef", "w", "bias", "temb", "x0", "x1", "w2", "res")] +
-                [("out_scale", C.c_float), ("out", C.c_void_p), ("stats", C.c_void_p)])
+                [("out_scale", C.c_float), ("out", C.c_void_p), ("stats", C.c_void_p)] +
+                [(k, C.c_void_p) for k in ("pyr", "w4", "b4", "gn_st0", "gn_st1", "gn_gamma", "gn_beta")] +
+                [("gn_groups", C.c_int), ("gn_eps", C.c_float), ("temb_bstride", C.c_int)])
 
 
 class UseHipError(RuntimeError):

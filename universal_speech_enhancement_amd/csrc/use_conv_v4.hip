@@ -531,6 +531,8 @@ __global__ __launch_bounds__(512) void conv_v4_kernel(ConvArgs p) {
     constexpr int STG_LD = BN + 4;
     constexpr bool ATID = EPI >= 0 && !(EPI & 4) && sizeof(TOUT) == 2;   // lane-linear staging of half rounds by ds_write_addtid_b32 (v4_stage8)
     constexpr int STG_WAVE = ATID ? V4_STG_ATID_BYTES : 32 * STG_LD * 4;   // 8,384 B per wave and half round / 16,896 B per wave and round
+    // M0[15:0] holds the staging base of ds_write_addtid_b32: wave 7's base must fit in 16 bits (the dynamic block starts at LDS offset 0)
+    static_assert(!ATID || 7 * STG_WAVE < 65536, "conv_v4: wave-7 staging base exceeds M0[15:0]");
     constexpr int CH = 16 / (int)sizeof(TOUT);
     constexpr int CPR = BN / CH;                             // 16-byte chunks per pixel row: 16 (bf16) / 32 (fp32)
     constexpr int QN = 32 * CPR / 64;                        // passes per round: 8 / 16
@@ -785,16 +787,30 @@ static void v4_launch_t(const ConvArgs& a, hipStream_t s) {
 static long g_v4_min_blocks = 80;      // (round 4: 128 -> 80: the 128 x 160 maps of the benchmark shape run 1.4 % of an evaluation faster here than on conv_v2)
 void conv_v4_set_min_blocks(long n) { g_v4_min_blocks = n; }
 
-bool conv_v4_eligible(const ConvArgs& a) {
-    static const bool off = getenv("USE_HIP_NO_V4") != nullptr && atoi(getenv("USE_HIP_NO_V4")) != 0;   // A/B switch
+// What the kernel itself can run (launches forced past the dispatcher: use_op_conv / use_conv_bench variants 4 and 5): every condition of
+// conv_v4_eligible except the grid-size threshold and the A/B switch.  Null, or the first violated condition.
+const char* conv_v4_unrunnable(const ConvArgs& a) {
     const int Ctot = a.C0 + a.C1, XC = a.XC0 + a.XC1;
     const int ck = conv_v4_chunk(a.in_dtype);
+    if (a.ntaps != 9) return "ntaps == 9";
+    if (a.Cout <= 32) return "Cout > 32";
+    if (a.in_dtype != a.out_dtype) return "in_dtype == out_dtype";
+    if (Ctot % ck || (a.C1 && a.C0 % ck)) return "C0 and C1 multiples of the K chunk (16 fp32 / 32 16-bit channels)";
+    if (Ctot > 512) return "C0 + C1 <= 512 (one GroupNorm coefficient per thread)";
+    if (XC % ck || (a.XC1 && a.XC0 % ck)) return "XC0 and XC1 multiples of the K chunk";
+    if (a.cout_pad % V4_BN) return "cout_pad a multiple of 128";
+    if (!a.wb || (XC && !a.w2b)) return "slab-major weights";
+    if (a.H % V4_TH || a.W % V4_TW) return "H % 16 == 0 and W % 32 == 0 (whole tiles)";
+    return nullptr;
+}
+
+bool conv_v4_eligible(const ConvArgs& a) {
+    static const bool off = getenv("USE_HIP_NO_V4") != nullptr && atoi(getenv("USE_HIP_NO_V4")) != 0;   // A/B switch
     // 512-pixel tiles need enough workgroups per image to fill the chip evenly at batch 8; smaller maps stay on conv_v2
     // (use_set_option("conv_v4_min_blocks", n) moves the threshold: the parity tests force the kernel onto small maps)
     // (per image, so that the kernel choice - and with it the summation order - does not depend on the batch size)
     const long blocks = (long)conv_v4_tiles(a.H, a.W) * ((a.Cout + V4_BN - 1) / V4_BN);
-    return !off && a.wb != nullptr && (XC == 0 || a.w2b != nullptr) && a.ntaps == 9 && a.Cout > 32 && a.in_dtype == a.out_dtype &&
-           Ctot % ck == 0 && Ctot <= 512 && XC % ck == 0 && (a.C1 == 0 || a.C0 % ck == 0) && (a.XC1 == 0 || a.XC0 % ck == 0) && a.cout_pad % V4_BN == 0 && a.H % V4_TH == 0 && a.W % V4_TW == 0 && blocks >= g_v4_min_blocks;
+    return !off && !conv_v4_unrunnable(a) && blocks >= g_v4_min_blocks;
 }
 
 void launch_conv_v4(const ConvArgs& a0, hipStream_t s) {

@@ -612,6 +612,8 @@ __global__ __launch_bounds__(512) void conv_v5_kernel(ConvArgs p) {
     // fp32 values (of which the stored ones are the roundings) instead of re-expanding the packed result.
     constexpr bool ATID = true;                              // lane-linear staging of half rounds by ds_write_addtid_b32 (v5_stage8), every form
     constexpr int STG_WAVE = V5_STG_BYTES;                   // 8,448 B per wave and half round
+    // M0[15:0] holds the staging base of ds_write_addtid_b32: wave 7's base must fit in 16 bits (the dynamic block starts at LDS offset 0)
+    static_assert(7 * STG_WAVE < 65536, "conv_v5: wave-7 staging base exceeds M0[15:0]");
     constexpr int CH = 16 / (int)sizeof(TOUT);
     constexpr int CPR = BN / CH;                             // 16-byte chunks per pixel row: 16 (bf16) / 32 (fp32)
     constexpr int QN = 32 * CPR / 64;                        // passes per round: 8 / 16

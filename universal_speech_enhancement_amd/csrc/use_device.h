@@ -220,7 +220,9 @@ DEVI uint4 mfma16_with_transform(ACC& acc, const AF& af, const BF& bf, const uin
 // wave-instruction against 4 for ds_write_b32 / 6 for ds_write2_b32 - MI355X_MICROARCH.md, LDS: a store's cost is the transfer of its
 // address and data registers; the epilogue's 1 024 staging stores per tile were 4 k of its ~10 k cycles).  M0 holds 16 bits, so a wave
 // stages HALF a round at a time (conv_v4; the input convolution: one of its two tile rows) - accumulator registers r = 8 hb ... 8 hb + 7 of its four 32-channel blocks = pixel columns 16 hb ...
-// 16 hb + 15 of its tile row x 128 channels, 8 KB - and the eight regions end below 64 KB.  Register (j, r') is one lane-linear row of 64
+// 16 hb + 15 of its tile row x 128 channels, 8 KB.  Only a wave's BASE must fit in M0's 16 bits, not the whole region: the eight regions
+// end above 64 KB (8 x 8 384 B = 67 072 B for conv_v4, 8 x 8 448 B = 67 584 B for conv_v5), and the kernels static_assert that the last
+// wave's base (58 688 / 59 136 B, from LDS offset 0) is below 65 536.  Register (j, r') is one lane-linear row of 64
 // floats [pixel half h][channel c] at dword j * 512 + r' * 64 + 4 A(j), A(j) = (j & 1) + 8 (j >> 1): the shift by A(j) bank quads makes
 // the read-back conflict-free (a 16-lane group of a ds_read_b128 - lanes {0-3, 12-15, 20-27} etc. - reads one pixel's channel chunks
 // {0-3, 12-15} and its neighbour's {4-11}: bank quad = A(ch >> 2) + 2 (ch & 3) + 8 h + half: 16 distinct values).

@@ -1632,6 +1632,13 @@ __global__ void to_float_kernel(const void* p, float* out, size_t n, int dtype) 
 }
 }  // namespace
 
+// forced launches of conv_v5 (use_op_conv / use_conv_bench variant 5): conv_v4's conditions and 16-bit storage
+static const char* conv_v5_unrunnable(const ConvArgs& a) {
+    return a.in_dtype == DT_F32 ? "16-bit storage" : conv_v4_unrunnable(a);
+}
+// use_conv_op::temb_bstride: 0 = Cout (one row per item), -1 = one row shared by the batch, else the stride in elements
+static int op_temb_bstride(const use_conv_op* c) { return c->temb_bstride == 0 ? c->Cout : c->temb_bstride < 0 ? 0 : c->temb_bstride; }
+
 int use_conv_bench(const use_conv_case* c, float* out_host, float* stats_host, double* ms_avg, double* flops) {
     if (!c || c->B < 1 || c->H < 1 || c->W < 1 || c->C0 < 1 || c->Cout < 1) return fail(USE_E_INVALID, "bad conv case");
     const int dt = c->dtype;
@@ -1700,8 +1707,8 @@ int use_conv_bench(const use_conv_case* c, float* out_host, float* stats_host, d
             case 1: launch_conv_generic(a, 0); return 0;
             case 7: if (!conv_sk_eligible(a)) return -1; launch_conv_sk(a, 0); return 0;
             case 2: if (!conv_v2_eligible(a)) return -1; launch_conv_v2(a, 0); return 0;
-            case 4: if (!a.wb || (XC && !a.w2b) || a.H % 16 || a.W % 32) return -1; launch_conv_v4(a, 0); return 0;   // (conv_v4 has no partial tiles)
-            case 5: if (!a.wb || (XC && !a.w2b) || a.H % 16 || a.W % 32 || a.in_dtype == DT_F32) return -1; launch_conv_v5(a, 0); return 0;
+            case 4: if (conv_v4_unrunnable(a)) return -1; launch_conv_v4(a, 0); return 0;
+            case 5: if (conv_v5_unrunnable(a)) return -1; launch_conv_v5(a, 0); return 0;
             default: return -1;
         }
     };
@@ -1712,7 +1719,10 @@ int use_conv_bench(const use_conv_case* c, float* out_host, float* stats_host, d
         if (trace) { (void)hipMemset(trace, 0, 512 * 8); a.trace = trace; a.dbg = atoi(getenv("USE_HIP_TRACE")); }
     }
     if (stats) (void)hipMemset(stats, 0, stats_bytes);
-    if (run() != 0) { cleanup(); return fail(USE_E_INVALID, "variant %d cannot run this case", c->variant); }
+    if (run() != 0) {
+        const char* why = c->variant == 4 ? conv_v4_unrunnable(a) : c->variant == 5 ? conv_v5_unrunnable(a) : nullptr;
+        cleanup(); return fail(USE_E_INVALID, "variant %d cannot run this case%s%s", c->variant, why ? ": needs " : "", why ? why : "");
+    }
     if (hipDeviceSynchronize() != hipSuccess) { cleanup(); return fail(USE_E_HIP, "conv bench: launch failed: %s", hipGetErrorString(hipGetLastError())); }
     if (trace) {
         unsigned long long hb[512];
@@ -1776,7 +1786,12 @@ int use_op_conv(const use_conv_op* c, use_stream_t stream) {
     char* dw = (char*)dalloc(wbytes); char* dwb = slab ? (char*)dalloc(wbytes) : nullptr;
     char* dw2 = XC ? (char*)dalloc(w2bytes) : nullptr; char* dw2b = slab2 ? (char*)dalloc(w2bytes) : nullptr;
     float* dbias = (float*)dalloc((size_t)w.cout_pad * 4);
-    if (!dw || !dbias || (slab && !dwb) || (XC && !dw2) || (slab2 && !dw2b)) { cleanup(); return fail(USE_E_NOMEM, "use_op_conv: allocation failed"); }
+    float* dw4 = c->pyr ? (float*)dalloc((size_t)w.cout_pad * 5 * 4) : nullptr;     // [cout_pad][4] then b4 [cout_pad], zero-padded
+    if (!dw || !dbias || (slab && !dwb) || (XC && !dw2) || (slab2 && !dw2b) || (c->pyr && !dw4)) { cleanup(); return fail(USE_E_NOMEM, "use_op_conv: allocation failed"); }
+    if (c->pyr && !c->w4) { cleanup(); return fail(USE_E_INVALID, "use_op_conv: pyr without w4"); }
+    if (!c->coef && c->gn_st0 && (!c->gn_gamma || !c->gn_beta || c->gn_groups < 1 || Cin % c->gn_groups || (c->C1 && !c->gn_st1))) {
+        cleanup(); return fail(USE_E_INVALID, "use_op_conv: in-kernel GroupNorm needs gn_gamma, gn_beta, gn_st1 (with C1) and groups dividing C0 + C1");
+    }
     {
         std::vector<char> hp(wbytes), hpb(slab ? wbytes : 0);
         pack_conv_raw(c->w, w, hp.data(), slab ? hpb.data() : nullptr);
@@ -1792,20 +1807,34 @@ int use_op_conv(const use_conv_op* c, use_stream_t stream) {
         std::vector<float> hb((size_t)w.cout_pad, 0.f);
         if (c->bias) memcpy(hb.data(), c->bias, (size_t)c->Cout * 4);
         (void)hipMemcpy(dbias, hb.data(), hb.size() * 4, hipMemcpyHostToDevice);
+        if (c->pyr) {
+            std::vector<float> h4((size_t)w.cout_pad * 5, 0.f);
+            memcpy(h4.data(), c->w4, (size_t)c->Cout * 4 * 4);
+            if (c->b4) memcpy(h4.data() + (size_t)w.cout_pad * 4, c->b4, (size_t)c->Cout * 4);
+            (void)hipMemcpy(dw4, h4.data(), h4.size() * 4, hipMemcpyHostToDevice);
+        }
     }
     ConvArgs a{};
     a.B = c->B; a.H = c->H; a.W = c->W; a.Cout = c->Cout; a.ntaps = ntaps; a.in_dtype = dt; a.out_dtype = odt;
     a.src0 = c->src0; a.src1 = c->C1 ? c->src1 : nullptr; a.C0 = c->C0; a.C1 = c->C1; a.coef = c->coef; a.act = c->act;
     a.w = dw; a.wb = dwb; a.cout_pad = w.cout_pad;
     a.x0 = XC ? c->x0 : nullptr; a.x1 = c->XC1 ? c->x1 : nullptr; a.XC0 = c->XC0; a.XC1 = c->XC1; a.w2 = dw2; a.w2b = dw2b;
-    a.bias = dbias; a.temb = c->temb; a.temb_bstride = c->Cout; a.res = c->res; a.out_scale = c->out_scale;
+    a.bias = dbias; a.temb = c->temb; a.temb_bstride = op_temb_bstride(c); a.res = c->res; a.out_scale = c->out_scale;
     a.out = c->out; a.stats = c->stats;
+    if (c->pyr) { a.pyr = c->pyr; a.w4 = dw4; a.b4 = dw4 + (size_t)w.cout_pad * 4; }
+    if (!c->coef && c->gn_st0) {                              // finalised in the kernel, gn_inv_n as Fwd::conv computes it
+        a.gn_st0 = c->gn_st0; a.gn_st1 = c->C1 ? c->gn_st1 : nullptr; a.gn_gamma = c->gn_gamma; a.gn_beta = c->gn_beta;
+        a.gn_groups = c->gn_groups; a.gn_eps = c->gn_eps;
+        a.gn_inv_n = 1.0f / ((float)(Cin / c->gn_groups) * (float)(c->H * c->W));
+    }
     int rc = USE_OK;
+    const char* why = nullptr;
     switch (c->variant) {
         case 0: launch_conv(a, s); break;
         case 1: launch_conv_generic(a, s); break;
         case 2: if (!conv_v2_eligible(a)) rc = fail(USE_E_INVALID, "conv_v2 cannot run this case"); else launch_conv_v2(a, s); break;
-        case 4: if (!slab || (XC && !slab2) || a.H % 16 || a.W % 32 || dt != odt) rc = fail(USE_E_INVALID, "conv_v4 cannot run this case"); else launch_conv_v4(a, s); break;
+        case 4: if ((why = conv_v4_unrunnable(a))) rc = fail(USE_E_INVALID, "conv_v4 cannot run this case: needs %s", why); else launch_conv_v4(a, s); break;
+        case 5: if ((why = conv_v5_unrunnable(a))) rc = fail(USE_E_INVALID, "conv_v5 cannot run this case: needs %s", why); else launch_conv_v5(a, s); break;
         case 7: if (!conv_sk_eligible(a)) rc = fail(USE_E_INVALID, "conv_sk cannot run this case"); else launch_conv_sk(a, s); break;
         default: rc = fail(USE_E_INVALID, "use_op_conv: unknown variant %d", c->variant);
     }
@@ -1835,6 +1864,7 @@ int use_op_conv_dev(const use_conv_op* c, int w_mode, void* work, size_t work_by
     const int Cin = c->C0 + c->C1, ntaps = c->ntaps == 1 ? 1 : 9;
     if (Cin % 32 != 0 || (c->C1 && c->C0 % 32)) return fail(USE_E_INVALID, "use_op_conv_dev: channel counts must be multiples of 32 (zero-pad)");
     if (c->XC0 || c->XC1 || c->x0 || c->w2) return fail(USE_E_INVALID, "use_op_conv_dev: no fused shortcut in this form");
+    if (c->pyr || c->gn_st0) return fail(USE_E_INVALID, "use_op_conv_dev: no Combine or in-kernel GroupNorm in this form");
     size_t wbytes; bool slab; int cout_pad;
     if (conv_dev_layout(c, &wbytes, &slab, &cout_pad) > work_bytes) return fail(USE_E_INVALID, "use_op_conv_dev: workspace too small");
     hipStream_t s = (hipStream_t)stream;
@@ -1845,7 +1875,7 @@ int use_op_conv_dev(const use_conv_op* c, int w_mode, void* work, size_t work_by
     a.B = c->B; a.H = c->H; a.W = c->W; a.Cout = c->Cout; a.ntaps = ntaps; a.in_dtype = dt; a.out_dtype = odt;
     a.src0 = c->src0; a.src1 = c->C1 ? c->src1 : nullptr; a.C0 = c->C0; a.C1 = c->C1; a.coef = c->coef; a.act = c->act;
     a.w = dw; a.wb = dwb; a.cout_pad = cout_pad;
-    a.bias = dbias; a.temb = c->temb; a.temb_bstride = c->Cout; a.res = c->res; a.out_scale = c->out_scale;
+    a.bias = dbias; a.temb = c->temb; a.temb_bstride = op_temb_bstride(c); a.res = c->res; a.out_scale = c->out_scale;
     a.out = c->out; a.stats = c->stats;
     launch_conv(a, s);
     HIPCHK(hipGetLastError());

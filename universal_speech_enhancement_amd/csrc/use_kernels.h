@@ -98,6 +98,7 @@ void launch_conv_sk(const ConvArgs& a, hipStream_t s);
 void launch_conv_generic(const ConvArgs& a, hipStream_t s);   // conv_kernel / pyr_conv_kernel / conv_in_kernel only (no specialised schedule)
 void pyr_conv_set_ws(int n);                            // wave-specialised form of the same layer (0: off, 1: on, n > 1: workgroups per launch)
 bool conv_v4_eligible(const ConvArgs& a);
+const char* conv_v4_unrunnable(const ConvArgs& a);         // null if conv_v4 can run `a` (forced launches), else the violated condition
 void conv_v4_set_min_blocks(long n);                     // smallest grid conv_v4 is used for (default 80 workgroups per image)
 void launch_conv_v4(const ConvArgs& a, hipStream_t s);
 // the same kernel on v_mfma_f32_16x16x32 (use_conv_v5.hip; 16-bit storage): less energy per FLOP than the 32x32x16 shape

@@ -834,6 +834,7 @@ __global__ __launch_bounds__(256) void conv_in_split_kernel(ConvArgs p, int tile
     // one block, carved by hand: the staging regions first (ds_write_addtid_b32 takes its base from M0[15:0])
     constexpr int O_STG = 0, O_X = O_STG + 4 * V4_STG_ATID_BYTES, O_W = O_X + 3 * CINS_XB, O_RED = O_W + 128 * CINS_WP, SM_BYTES = O_RED + 4 * 128 * 2 * 4;
     static_assert(O_X % 16 == 0 && O_W % 16 == 0 && O_RED % 16 == 0 && SM_BYTES <= 80 * 1024, "LDS layout (two workgroups per CU)");
+    static_assert(O_STG + 3 * V4_STG_ATID_BYTES < 65536, "conv_in_split: wave-3 staging base exceeds M0[15:0]");
     __shared__ __attribute__((aligned(64))) char s_all[SM_BYTES];
     char* const s_x = s_all + O_X;                            // [xh | xl | zeros], each [180][4] bf16
     char* const s_w = s_all + O_W;                            // [128 co][112 (+8)] bf16
