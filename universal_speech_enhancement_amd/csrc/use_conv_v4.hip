@@ -44,11 +44,6 @@ constexpr int V4_BN = 128;
 #ifndef V4_DEAD_LOADS               /* 1: the loads of the last K chunk's staging pass (results unused) go through an empty buffer descriptor */
 #define V4_DEAD_LOADS 1
 #endif
-#ifdef USE_HIP_XF_LEGACY            /* A/B builds only: the round 1-3 form (transform left to the compiler's scheduling) */
-constexpr bool V4_XF_LEGACY = true;
-#else
-constexpr bool V4_XF_LEGACY = false;
-#endif
 
 template <typename TIN, typename TOUT, int CK, bool ACT, int EPI>
 __global__ __launch_bounds__(512) void conv_v4_kernel(ConvArgs p) {
@@ -366,7 +361,7 @@ __global__ __launch_bounds__(512) void conv_v4_kernel(ConvArgs p) {
 #define V4_MFMA(CC, T)                                                                                               \
     {                                                                                                                \
         V4_SETPRIO(1)                                                                                                \
-        if constexpr (sizeof(TIN) == 2 && !V4_XF_LEGACY) {                                                           \
+        if constexpr (sizeof(TIN) == 2) {                    /* (fp32: stage_transform and sched_group_barrier below) */ \
             if (V4_XF_PHASE(T)) {                            /* unconditional at run time: same basic block as the MFMAs */ \
                 /* 16 MFMAs, slice g of the GroupNorm + SiLU transform of one halo piece behind MFMA g, one asm statement */ \
                 /* each (use_device.h, XfAsm: left to itself hipcc runs the transform with the matrix pipe idle)          */ \
@@ -802,6 +797,10 @@ const char* conv_v4_unrunnable(const ConvArgs& a) {
     if (!a.wb || (XC && !a.w2b)) return "slab-major weights";
     if (a.H % V4_TH || a.W % V4_TW) return "H % 16 == 0 and W % 32 == 0 (whole tiles)";
     return nullptr;
+}
+// the same for conv_v5_kernel (the 16x16x32 form of this kernel, use_conv_v5.hip; forced launches: variant 5): conv_v4's conditions and 16-bit storage
+const char* conv_v5_unrunnable(const ConvArgs& a) {
+    return a.in_dtype == DT_F32 ? "16-bit storage" : conv_v4_unrunnable(a);
 }
 
 bool conv_v4_eligible(const ConvArgs& a) {

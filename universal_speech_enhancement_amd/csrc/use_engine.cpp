@@ -1632,10 +1632,6 @@ __global__ void to_float_kernel(const void* p, float* out, size_t n, int dtype) 
 }
 }  // namespace
 
-// forced launches of conv_v5 (use_op_conv / use_conv_bench variant 5): conv_v4's conditions and 16-bit storage
-static const char* conv_v5_unrunnable(const ConvArgs& a) {
-    return a.in_dtype == DT_F32 ? "16-bit storage" : conv_v4_unrunnable(a);
-}
 // use_conv_op::temb_bstride: 0 = Cout (one row per item), -1 = one row shared by the batch, else the stride in elements
 static int op_temb_bstride(const use_conv_op* c) { return c->temb_bstride == 0 ? c->Cout : c->temb_bstride < 0 ? 0 : c->temb_bstride; }
 
