@@ -6,6 +6,7 @@
  *   use_score        <- ScoreModel.forward / forward_score      src/models/components/sgmse/model_wrapper.py:135-145
  *                       (= -NCSNpp.forward(cat[x, Y], t)         .../backbones/ncsnpp.py:324-501)
  *   use_sample       <- sampling.get_pc_sampler()->pc_sampler()  .../sampling/__init__.py:23-73
+ *   use_sample_ode   <- sampling.get_ode_sampler()->ode_sampler() .../sampling/__init__.py:76-159 (scipy RK45, on the device)
  *   use_set_weight   <- LightningModule checkpoint load: state_dict keys "all_modules.<i>....", "output_layer.*"
  *                       (.../backbones/ncsnpp.py:116-316)
  *   use_sde_*        <- OUVESDE.prior_sampling (sdes.py:248-254), ReverseDiffusionPredictor / EulerMaruyamaPredictor
@@ -129,6 +130,50 @@ int use_sample_cond(use_handle* h, const void* y, const void* cond, const void* 
 int use_sample_cond2(use_handle* h, const void* y, const void* cond, const void* cond2, const void* noise, uint64_t seed, void* out,
                      use_stream_t stream);
 
+/* Probability-flow ODE sampler (reference sampling/__init__.py:76-159 get_ode_sampler; model_wrapper.py:238-260): the ODE
+ * dx = [theta (y - x) - g(t)^2 score / 2] dt integrated from T = 1 down to t_eps by scipy's RK45 (Dormand-Prince 5(4), scipy 1.15
+ * rk.py / common.py, reproduced on the device), then, with `denoise`, one noise-free reverse-diffusion step at t_eps with dt = 1/N.
+ * Each group of `group` consecutive items (0: the whole batch) has its own step-size controller and its own error norm (RMS over
+ * the group's complex elements, as scipy's over its flattened vector); every item carries its own t into the network.  A finished
+ * group is frozen: its items are still evaluated, their state does not change.  The float fields are taken at their shortest
+ * decimal spelling (1e-5f -> 1e-5, 0.03f -> 0.03), so that they mean the Python floats the reference passes.
+ * Per group: nfev = 2 + 6 x attempted steps (1 + 6 x ... with first_step), status 0 = reached t_eps, -1 = step below scipy's
+ * min_step (the last accepted state is kept, as the reference keeps solution.y[:, -1]), -2 = max_nfe reached. */
+typedef struct use_ode_config {
+    float rtol, atol;      /* > 0, >= 0                                           sampling/__init__.py:82-83 */
+    float t_eps;           /* end of the integration (3e-2)                                                 */
+    int N;                 /* the denoise step's dt = 1/N                         model_wrapper.py:239-241   */
+    int group;             /* items per step-size controller; 0 = the whole batch (ScoreModel minibatch)    */
+    int denoise;           /* 1: one noise-free reverse-diffusion step at t_eps                             */
+    float first_step, max_step; /* 0 = scipy's defaults (select_initial_step, inf)                          */
+    int max_nfe;           /* evaluations per group before status -2; 0 = 10000                             */
+    int use_graph;         /* 1: capture one RK45 step (6 evaluations + the stepper's kernels) as a hipGraph and replay it */
+} use_ode_config;
+enum { USE_ODE_FINISHED = 0, USE_ODE_TOO_SMALL_STEP = -1, USE_ODE_MAX_NFE = -2 };
+/* Belongs to the plan like use_set_sampler (a new use_plan shape needs it again; a stale plan gives USE_E_STATE). */
+int use_set_ode(use_handle* h, const use_ode_config* cfg);
+/* prior (draw 0 of the Philox stream of `seed`, or noise = that one draw [B,1,F,T']) -> RK45 -> denoise -> out (complex64).
+ * cond / cond2 as in use_sample_cond2.  nfev / status: HOST int arrays of n_groups = ceil(B / group) entries (may be null).
+ * Synchronises the stream once per RK45 step (the "all groups done" word).  Stats: "ode_steps" (accepted steps, summed over the
+ * groups), "ode_rejected", "ode_nfev_max" (what every item was evaluated: finished groups are evaluated until the last one ends). */
+int use_sample_ode(use_handle* h, const void* y, const void* cond, const void* cond2, const void* noise, uint64_t seed, void* out,
+                   int* nfev, int* status, use_stream_t stream);
+/* The same RK45 stepper for callers with their own drift (reverse communication; the seam path of sampling.get_ode_sampler).
+ * h: any handle (only its OUVE constants are used).  _start: y_sde = the SDE's y, x0 = the prior sample (complex64, n_per_item x B,
+ * both copied).  _request: 1 = evaluate the drift at (x, t) - x complex64 [n], t float32 [B] (device) - and _supply it; 0 = every
+ * group is done (synchronises the stream once per step).  _supply: kind 0 = f is the drift, 1 = f is the OUVE score at (x, t)
+ * (the drift is formed on the device).  _result: out = complex64 of the solution, per-group nfev / status (host, may be null).
+ * _state: per-group t, h_abs, nfev, status, accepted steps (host arrays, may be null; synchronises). */
+typedef struct use_ode use_ode;
+int use_ode_create(use_handle* h, int B, int64_t n_per_item, const use_ode_config* cfg, use_ode** out);
+int use_ode_start(use_ode* o, const void* y_sde, const void* x0, use_stream_t stream);
+int use_ode_request(use_ode* o, void* x, float* t, use_stream_t stream);
+int use_ode_supply(use_ode* o, const void* f, int kind, use_stream_t stream);
+int use_ode_result(use_ode* o, void* out, int* nfev, int* status, use_stream_t stream);
+int use_ode_state(use_ode* o, double* t, double* h_abs, int* nfev, int* status, int* steps, use_stream_t stream);
+int use_ode_num_groups(use_ode* o);
+int use_ode_destroy(use_ode* o);
+
 /* Element-wise SDE pieces for callers that drive the loop themselves through the reference's
  * Predictor / Corrector registries (uniform t over the batch). n = number of complex elements. */
 int use_sde_prior(use_handle* h, const void* y, const void* noise, uint64_t seed, void* x, int64_t n, use_stream_t s);
@@ -168,7 +213,8 @@ int use_stft_fwd(const float* wav, void* Y, int B, int L, int n_fft, int hop, co
 int use_istft_back(const void* X, float* wav, int B, int L, int n_fft, int hop, const float* window, int Tpad, float factor,
                    float exponent, use_stream_t s);
 
-/* Counters of a handle: "graph_captures" (segments of the sampling loop captured so far), "plans_built", "plan_cache_hits",
+/* Counters of a handle: "graph_captures" (segments of the sampling loop captured so far), "plans_built", "plan_cache_hits", "ode_steps",
+ * "ode_rejected", "ode_nfev_max" (of the last use_sample_ode),
  * "plans_parked", "plan_stale" (1: use_set_option was called since use_plan - the evaluation entry points will refuse the plan).  A handle keeps the plans - workspace, state, time-embedding tables, captured graphs - of the most recently used
  * (B, T') shapes (use_set_option("plan_cache", k), default 4 besides the current one): use_plan of a parked shape costs nothing and
  * its graphs replay as they are. */

@@ -29,6 +29,11 @@ class UseSamplerConfig(C.Structure):
                 ("snr", C.c_float), ("t_eps", C.c_float), ("use_graph", C.c_int)]
 
 
+class UseOdeConfig(C.Structure):
+    _fields_ = [("rtol", C.c_float), ("atol", C.c_float), ("t_eps", C.c_float), ("N", C.c_int), ("group", C.c_int), ("denoise", C.c_int),
+                ("first_step", C.c_float), ("max_step", C.c_float), ("max_nfe", C.c_int), ("use_graph", C.c_int)]
+
+
 class UseConvCase(C.Structure):
     _fields_ = [(k, C.c_int) for k in ("B", "H", "W", "C0", "C1", "Cout", "XC0", "XC1", "act", "gn", "temb", "res", "stats",
                                        "dtype", "variant", "iters")]
@@ -75,6 +80,16 @@ SYMBOLS = {
     "use_get_timesteps": (_i, [_vp, C.POINTER(_f), _i]),
     "use_sample": (_i, [_vp, _vp, _vp, _u64, _vp, _vp]),
     "use_sample_cond": (_i, [_vp, _vp, _vp, _vp, _u64, _vp, _vp]),
+    "use_set_ode": (_i, [_vp, C.POINTER(UseOdeConfig)]),
+    "use_sample_ode": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, C.POINTER(_i), C.POINTER(_i), _vp]),
+    "use_ode_create": (_i, [_vp, _i, _i64, C.POINTER(UseOdeConfig), C.POINTER(_vp)]),
+    "use_ode_start": (_i, [_vp, _vp, _vp, _vp]),
+    "use_ode_request": (_i, [_vp, _vp, _vp, _vp]),
+    "use_ode_supply": (_i, [_vp, _vp, _i, _vp]),
+    "use_ode_result": (_i, [_vp, _vp, C.POINTER(_i), C.POINTER(_i), _vp]),
+    "use_ode_state": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _vp]),
+    "use_ode_num_groups": (_i, [_vp]),
+    "use_ode_destroy": (_i, [_vp]),
     "use_spec_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_float, C.c_float, _vp]),
     "use_spec_back": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_float, C.c_float, _vp]),
     "use_stft_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, C.c_float, C.c_float, _vp]),

@@ -159,6 +159,14 @@ struct use_handle {
     int debug_B = 0;
     std::vector<hipGraphExec_t> graph_exec[2];           // [0]: device RNG, [1]: injected noise; one graph per segment of steps
     hipGraphExec_t score_graph = nullptr;
+    // probability-flow ODE sampler (use_set_ode / use_sample_ode): the configuration belongs to the plan, the stepper's buffers and the
+    // captured step graph to the handle (re-made when the shape, the stepper or a pointer the graph holds changes)
+    use_ode_config oc{};
+    bool ode_set = false;
+    use_ode* ode_run = nullptr;
+    hipGraphExec_t ode_graph = nullptr;
+    std::vector<const void*> ode_graph_key;
+    long long ode_steps = 0, ode_rejected = 0, ode_nfev_max = 0;
     // plan cache: a predict run over files of different lengths alternates between a handful of (B, T') shapes; the plans of the
     // most recently used ones are parked here - workspace, state buffers, time-embedding tables and the captured graphs with the
     // addresses they hold - so that a shape that returns is neither re-planned nor re-captured.  use_set_option("plan_cache", k).
@@ -818,6 +826,7 @@ static void predictor_coeffs(const use_config& c, int predictor, float t, int N,
 // the PC loop (reference sampling/__init__.py:59-71)
 // ---------------------------------------------------------------------------------------------------------
 __global__ void set_rng_kernel(unsigned long long* st, unsigned long long seed, unsigned long long base) { st[0] = seed; st[1] = base; }
+__global__ void fill_f32_kernel(float* p, float v, int n) { for (int i = threadIdx.x; i < n; i += blockDim.x) p[i] = v; }
 
 // steps [i0, i1) of the loop (i0 == 0: preceded by the prior sampling); the whole loop is run_sampler(h, noise, s, 0, N)
 static void run_sampler(use_handle* h, const float2* noise, hipStream_t s, int i0, int i1) {
@@ -858,6 +867,7 @@ static void run_sampler(use_handle* h, const float2* noise, hipStream_t s, int i
 static void drop_graphs(use_handle* h) {
     for (auto& v : h->graph_exec) { for (auto g : v) if (g) (void)hipGraphExecDestroy(g); v.clear(); }
     if (h->score_graph) { (void)hipGraphExecDestroy(h->score_graph); h->score_graph = nullptr; }
+    if (h->ode_graph) { (void)hipGraphExecDestroy(h->ode_graph); h->ode_graph = nullptr; }
 }
 
 // everything of the handle that belongs to ONE plan (the current plan lives in the handle's own fields)
@@ -865,7 +875,7 @@ static void drop_graphs(use_handle* h) {
     X(B) X(T) X(nsub) X(arena) X(arena_alloc) X(arena_plan_bytes) X(persist) X(persist_bytes) X(persist_alloc) X(x4) X(silu_temb) X(tembias) X(t_dev) \
     X(Y) X(X) X(Xmean) X(score) X(xin) X(cond_buf) X(cond2_buf) X(Cond) X(lang_partial) X(lang_step) X(rng_state) X(lang_blocks)   \
     X(sc) X(sampler_set) X(timesteps) X(ts_dev) X(temb_table) X(silu_table) X(noise_copy) X(noise_copy_bytes) X(score_graph)      \
-    X(debug) X(debug_B) X(opt_gen_at_plan)
+    X(debug) X(debug_B) X(opt_gen_at_plan) X(oc) X(ode_set)
 struct use_handle::PlanState {
 #define X(f) decltype(use_handle::f) f;
     USE_PLAN_FIELDS(X)
@@ -883,7 +893,7 @@ static void plan_stash(use_handle* h, use_handle::PlanState& p) {      // handle
     for (int i = 0; i < 2; ++i) { p.graph_exec[i] = std::move(h->graph_exec[i]); h->graph_exec[i].clear(); }
     h->B = h->T = 0; h->arena = Arena{}; h->arena_alloc = 0; h->persist = nullptr; h->persist_bytes = h->persist_alloc = 0;
     h->ts_dev = h->temb_table = h->silu_table = nullptr; h->noise_copy = nullptr; h->noise_copy_bytes = 0; h->score_graph = nullptr;
-    h->sampler_set = false; h->timesteps.clear(); h->debug.clear();
+    h->sampler_set = false; h->timesteps.clear(); h->debug.clear(); h->ode_set = false;
 }
 static void plan_restore(use_handle* h, use_handle::PlanState& p) {    // p -> handle
 #define X(f) h->f = std::move(p.f);
@@ -937,6 +947,9 @@ int use_get_stat(use_handle* h, const char* name, long long* value) {
     if (!strcmp(name, "plans_built")) { *value = h->n_plans_built; return USE_OK; }
     if (!strcmp(name, "plan_cache_hits")) { *value = h->n_plan_cache_hits; return USE_OK; }
     if (!strcmp(name, "plans_parked")) { *value = (long long)h->plan_cache.size(); return USE_OK; }
+    if (!strcmp(name, "ode_steps")) { *value = h->ode_steps; return USE_OK; }                    // of the last use_sample_ode
+    if (!strcmp(name, "ode_rejected")) { *value = h->ode_rejected; return USE_OK; }
+    if (!strcmp(name, "ode_nfev_max")) { *value = h->ode_nfev_max; return USE_OK; }
     if (!strcmp(name, "plan_stale")) { *value = h->B && h->opt_gen_at_plan != g_opt_gen ? 1 : 0; return USE_OK; }   // an option changed since use_plan
     return fail(USE_E_INVALID, "unknown statistic '%s'", name);
 }
@@ -989,6 +1002,7 @@ int use_destroy(use_handle* h) {
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
     drop_graphs(h); plan_cache_clear(h);
+    if (h->ode_run) (void)use_ode_destroy(h->ode_run);
     if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
     for (int i = 0; i < MAX_SUB; ++i) {
         if (h->aux_stream[i]) (void)hipStreamDestroy(h->aux_stream[i]);
@@ -1154,6 +1168,7 @@ int use_plan(use_handle* h, int B, int Tpad) {
     HIPCHK(hipSetDevice(h->device));
     if (h->arena.base && h->B == B && h->T == Tpad && h->opt_gen_at_plan == g_opt_gen) return USE_OK;     // the current plan
     HIPCHK(hipDeviceSynchronize());
+    if (h->ode_graph) { (void)hipGraphExecDestroy(h->ode_graph); h->ode_graph = nullptr; }   // it holds the current plan's workspace
     use_handle::PlanState* hit = nullptr;                     // the requested plan, if it is parked: taken out BEFORE the current one
     for (size_t i = 0; i < h->plan_cache.size(); ++i) {       // goes in (else a cycle over capacity + 1 shapes would evict what it needs)
         use_handle::PlanState* p = h->plan_cache[i];
@@ -1173,7 +1188,7 @@ int use_plan(use_handle* h, int B, int Tpad) {
     }
     ++h->n_plans_built;
     h->opt_gen_at_plan = g_opt_gen;
-    h->B = B; h->T = Tpad; h->sampler_set = false;
+    h->B = B; h->T = Tpad; h->sampler_set = false; h->ode_set = false;
     // sub-batch pipelining (run_score): `subbatch` sub-batches of at least 2 items each
     // How many sub-batches: a question of grid quantisation on the 256 CUs (same-box sweeps, profiles/r5_e2e_ab_subbatch_sweep.txt).  The 3x3
     // convolutions of the 256 x 320 / 128 x 160 maps launch 160 / 80 workgroups per item: sub-batches of 4 items leave 2.5 / 1.25 rounds (83 % /
@@ -1427,6 +1442,18 @@ int use_sample_cond(use_handle* h, const void* y, const void* cond, const void* 
     return use_sample_cond2(h, y, cond, nullptr, noise, seed, out, stream);
 }
 
+// the sampler's inputs into the plan's buffers: the SDE's y, and the conditioning the network sees beside x - y itself, or a
+// separate one (condition="denoised"), and the second one of condition="both"
+static int load_sampler_inputs(use_handle* h, const void* y, const void* cond, const void* cond2, hipStream_t s) {
+    const size_t n = (size_t)h->B * h->cfg.n_freq * h->T;
+    HIPCHK(hipMemcpyAsync(h->Y, y, n * 8, hipMemcpyDeviceToDevice, s));
+    if (cond2) HIPCHK(hipMemcpyAsync(h->cond2_buf, cond2, n * 8, hipMemcpyDeviceToDevice, s));
+    float2* want = cond ? h->cond_buf : h->Y;
+    if (want != h->Cond) { HIPCHK(hipStreamSynchronize(s)); drop_graphs(h); h->Cond = want; }    // captured graphs hold the pointer
+    if (cond) HIPCHK(hipMemcpyAsync(h->cond_buf, cond, n * 8, hipMemcpyDeviceToDevice, s));
+    return USE_OK;
+}
+
 int use_sample_cond2(use_handle* h, const void* y, const void* cond, const void* cond2, const void* noise, uint64_t seed, void* out,
                      use_stream_t stream) {
     int rc = check_ready(h); if (rc) return rc;
@@ -1437,13 +1464,7 @@ int use_sample_cond2(use_handle* h, const void* y, const void* cond, const void*
                                                               : "this network takes one conditioning tensor");
     hipStream_t s = (hipStream_t)stream;
     const size_t n = (size_t)h->B * h->cfg.n_freq * h->T;
-    HIPCHK(hipMemcpyAsync(h->Y, y, n * 8, hipMemcpyDeviceToDevice, s));
-    if (cond2) HIPCHK(hipMemcpyAsync(h->cond2_buf, cond2, n * 8, hipMemcpyDeviceToDevice, s));
-    {   // the conditioning spectrogram the network sees beside x: the SDE's y itself, or a separate one (condition="denoised")
-        float2* want = cond ? h->cond_buf : h->Y;
-        if (want != h->Cond) { HIPCHK(hipStreamSynchronize(s)); drop_graphs(h); h->Cond = want; }    // captured graphs hold the pointer
-        if (cond) HIPCHK(hipMemcpyAsync(h->cond_buf, cond, n * 8, hipMemcpyDeviceToDevice, s));
-    }
+    rc = load_sampler_inputs(h, y, cond, cond2, s); if (rc) return rc;
     hipLaunchKernelGGL(set_rng_kernel, dim3(1), dim3(1), 0, s, h->rng_state, (unsigned long long)seed, 0ull);
     if (!h->sc.use_graph) {
         run_sampler(h, (const float2*)noise, s, 0, h->sc.N);
@@ -1498,6 +1519,309 @@ int use_sample_cond2(use_handle* h, const void* y, const void* cond, const void*
     }
     HIPCHK(hipMemcpyAsync(out, h->Xmean, n * 8, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipGetLastError());
+    return USE_OK;
+}
+
+// ---- probability-flow ODE sampler (reference sampling/__init__.py:76-159): the RK45 stepper of use_ode.hip -------------------
+}  // extern "C"
+
+struct use_ode {
+    use_handle* h = nullptr;
+    use_ode_config cfg{};
+    OdeDev d{};
+    OdeCtl c{};
+    char* buf = nullptr;
+    float2* ysde_buf = nullptr;
+    int* done_host = nullptr;                 // pinned: the "all groups done" word read back once per step
+    int phase = -1;                           // the stage-time row of the next evaluation: 0 f0, 7 f1 of select_initial_step, 1..6 a step
+};
+
+namespace {
+// the double a float field of use_ode_config stands for: its shortest decimal spelling (1e-5f -> 1e-5), i.e. the Python float the
+// reference passes to solve_ivp
+double float_as_decimal(float f) {
+    char b[48];
+    for (int p = 6; p <= 9; ++p) {
+        snprintf(b, sizeof b, "%.*g", p, (double)f);
+        if (strtof(b, nullptr) == f) break;
+    }
+    return strtod(b, nullptr);
+}
+
+int ode_check_config(const use_ode_config* oc) {
+    if (!oc) return fail(USE_E_INVALID, "null ODE configuration");
+    if (!(oc->rtol > 0.f) || !(oc->atol >= 0.f)) return fail(USE_E_INVALID, "ODE sampler needs rtol > 0 and atol >= 0 (got %g, %g)", oc->rtol, oc->atol);
+    if (!(oc->t_eps > 0.f && oc->t_eps < 1.f)) return fail(USE_E_INVALID, "ODE sampler needs 0 < t_eps < T = 1 (got %g)", oc->t_eps);
+    if (oc->group < 0) return fail(USE_E_INVALID, "ODE group must be >= 0 (0 = the whole batch), got %d", oc->group);
+    if (oc->denoise && oc->N < 1) return fail(USE_E_INVALID, "the denoise step needs N >= 1");
+    if (!(oc->first_step >= 0.f) || !(oc->max_step >= 0.f) || oc->max_nfe < 0) return fail(USE_E_INVALID, "first_step, max_step and max_nfe must be >= 0");
+    if (oc->first_step > 0.f && float_as_decimal(oc->first_step) > 1.0 - float_as_decimal(oc->t_eps))
+        return fail(USE_E_INVALID, "first_step exceeds the integration interval");   // validate_first_step (common.py:40-48)
+    return USE_OK;
+}
+
+// one supplied evaluation: the stage kernel of the current row, then the controller where a decision is due
+void ode_supply_impl(use_ode* o, const float2* f, int kind, hipStream_t s) {
+    launch_ode_stage(o->d, o->phase, f, kind, s);
+    switch (o->phase) {
+        case 0:                                            // f0: select_initial_step's d0, d1 (or the given first_step)
+            launch_ode_ctrl(o->c, o->d, ODE_INIT1, s);
+            if (o->c.first_step > 0) { launch_ode_commit(o->d, 0.2, s); o->phase = 1; }
+            else { launch_ode_commit(o->d, 1.0, s); o->phase = 7; }   // the probe y0 + h0 direction f0
+            break;
+        case 7:
+            launch_ode_ctrl(o->c, o->d, ODE_INIT2, s);
+            launch_ode_commit(o->d, 0.2, s);
+            o->phase = 1;
+            break;
+        case 6:                                            // accept / reject, FSAL, the first stage input of the next attempt
+            launch_ode_ctrl(o->c, o->d, ODE_STEP, s);
+            launch_ode_commit(o->d, 0.2, s);
+            o->phase = 1;
+            break;
+        default: ++o->phase;
+    }
+}
+
+void ode_start_impl(use_ode* o, hipStream_t s) {           // d.xin holds the prior sample, d.ysde the SDE's y
+    launch_ode_load(o->d, s);
+    launch_ode_ctrl(o->c, o->d, ODE_START, s);
+    o->phase = 0;
+}
+
+int ode_all_done(use_ode* o, hipStream_t s, bool* done) {
+    HIPCHK(hipMemcpyAsync(o->done_host, o->d.done, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *done = *o->done_host != 0;
+    return USE_OK;
+}
+
+int ode_read_groups(use_ode* o, std::vector<OdeGroup>& g, hipStream_t s) {
+    g.resize((size_t)o->c.ngroups);
+    HIPCHK(hipMemcpyAsync(g.data(), o->d.grp, g.size() * sizeof(OdeGroup), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return USE_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int use_ode_create(use_handle* h, int B, int64_t n_per_item, const use_ode_config* cfg, use_ode** out) {
+    if (!h || !out) return fail(USE_E_INVALID, "null argument");
+    *out = nullptr;
+    int rc = ode_check_config(cfg); if (rc) return rc;
+    if (B < 1 || n_per_item < 1) return fail(USE_E_INVALID, "ODE stepper needs B >= 1 and n_per_item >= 1");
+    HIPCHK(hipSetDevice(h->device));
+    auto* o = new use_ode();
+    o->h = h; o->cfg = *cfg;
+    const int G = cfg->group == 0 || cfg->group > B ? B : cfg->group;
+    const int ng = (B + G - 1) / G;
+    const long n = (long)B * n_per_item;
+    const int nblk = (int)std::max(1L, std::min(128L, (long)((n_per_item + 2047) / 2048)));
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o0 = off; off = (off + bytes + 255) & ~(size_t)255; return o0; };
+    const size_t o_y = take((size_t)n * 16), o_yn = take((size_t)n * 16), o_K = take((size_t)n * 8 * 7), o_x = take((size_t)n * 8),
+                 o_ys = take((size_t)n * 8), o_h = take((size_t)B * 8), o_ts = take((size_t)8 * B * 4), o_cg = take((size_t)8 * B * 4),
+                 o_p = take((size_t)2 * B * nblk * 8), o_g = take((size_t)ng * sizeof(OdeGroup)), o_d = take(sizeof(int));
+    if (hipMalloc((void**)&o->buf, off) != hipSuccess) { (void)hipGetLastError(); delete o; return fail(USE_E_NOMEM, "cannot allocate %.1f MB for the ODE stepper", off / 1e6); }
+    if (hipHostMalloc((void**)&o->done_host, sizeof(int), 0) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(o->buf); delete o; return fail(USE_E_NOMEM, "pinned host word"); }
+    if (hipMemset(o->buf, 0, off) != hipSuccess) { (void)use_ode_destroy(o); return fail(USE_E_HIP, "hipMemset of the ODE stepper failed"); }
+    OdeDev& d = o->d;
+    d.y = (double2*)(o->buf + o_y); d.ynew = (double2*)(o->buf + o_yn); d.K = (float2*)(o->buf + o_K); d.xin = (float2*)(o->buf + o_x);
+    o->ysde_buf = (float2*)(o->buf + o_ys); d.ysde = o->ysde_buf;
+    d.h_item = (double*)(o->buf + o_h); d.ts = (float*)(o->buf + o_ts); d.cg = (float*)(o->buf + o_cg); d.part = (double*)(o->buf + o_p);
+    d.grp = (OdeGroup*)(o->buf + o_g); d.done = (int*)(o->buf + o_d);
+    d.n_per_b = (long)n_per_item; d.B = B; d.G = G; d.nblk = nblk;
+    d.theta = h->cfg.theta; d.rtol = float_as_decimal(cfg->rtol); d.atol = float_as_decimal(cfg->atol);
+    OdeCtl& c = o->c;
+    c.t0 = 1.0; c.t_bound = float_as_decimal(cfg->t_eps);                       // sde.T = 1 (sdes.py:201)
+    c.first_step = cfg->first_step > 0 ? float_as_decimal(cfg->first_step) : 0.0;
+    c.max_step = cfg->max_step > 0 ? float_as_decimal(cfg->max_step) : INFINITY;
+    c.max_nfe = cfg->max_nfe > 0 ? cfg->max_nfe : 10000;
+    c.ngroups = ng; c.G = G; c.B = B; c.nblk = nblk; c.n_per_b = (long)n_per_item;
+    {   // the OUVE constants as the reference's Python floats (sdes.py:205-221), cast to float32 where torch meets a float32 tensor
+        const double smin = float_as_decimal(h->cfg.sigma_min), smax = float_as_decimal(h->cfg.sigma_max);
+        c.sigma_min = h->cfg.sigma_min; c.base = (float)(smax / smin); c.sq2ls = (float)std::sqrt(2 * std::log(smax / smin));
+    }
+    *out = o;
+    return USE_OK;
+}
+
+int use_ode_destroy(use_ode* o) {
+    if (!o) return USE_OK;
+    (void)hipSetDevice(o->h->device);
+    (void)hipDeviceSynchronize();
+    if (o->buf) (void)hipFree(o->buf);
+    if (o->done_host) (void)hipHostFree(o->done_host);
+    delete o;
+    return USE_OK;
+}
+
+int use_ode_num_groups(use_ode* o) { return o ? o->c.ngroups : fail(USE_E_INVALID, "null stepper"); }
+
+int use_ode_start(use_ode* o, const void* y_sde, const void* x0, use_stream_t stream) {
+    if (!o || !y_sde || !x0) return fail(USE_E_INVALID, "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n = (size_t)o->d.B * o->d.n_per_b;
+    o->d.ysde = o->ysde_buf;
+    HIPCHK(hipMemcpyAsync(o->ysde_buf, y_sde, n * 8, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(o->d.xin, x0, n * 8, hipMemcpyDeviceToDevice, s));
+    ode_start_impl(o, s);
+    HIPCHK(hipGetLastError());
+    return USE_OK;
+}
+
+int use_ode_request(use_ode* o, void* x, float* t, use_stream_t stream) {
+    if (!o || !x || !t) return fail(USE_E_INVALID, "null argument");
+    if (o->phase < 0) return fail(USE_E_STATE, "use_ode_start has not been called");
+    hipStream_t s = (hipStream_t)stream;
+    if (o->phase == 1) {                                   // the start of a step: is any group still running?
+        bool done = false;
+        int rc = ode_all_done(o, s, &done); if (rc) return rc;
+        if (done) return 0;
+    }
+    const size_t n = (size_t)o->d.B * o->d.n_per_b;
+    HIPCHK(hipMemcpyAsync(x, o->d.xin, n * 8, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(t, o->d.ts + (size_t)o->phase * o->d.B, (size_t)o->d.B * 4, hipMemcpyDeviceToDevice, s));
+    return 1;
+}
+
+int use_ode_supply(use_ode* o, const void* f, int kind, use_stream_t stream) {
+    if (!o || !f) return fail(USE_E_INVALID, "null argument");
+    if (o->phase < 0) return fail(USE_E_STATE, "use_ode_start has not been called");
+    if (kind != 0 && kind != 1) return fail(USE_E_INVALID, "kind: 0 = drift, 1 = score");
+    ode_supply_impl(o, (const float2*)f, kind, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return USE_OK;
+}
+
+int use_ode_state(use_ode* o, double* t, double* h_abs, int* nfev, int* status, int* steps, use_stream_t stream) {
+    if (!o) return fail(USE_E_INVALID, "null stepper");
+    std::vector<OdeGroup> g;
+    int rc = ode_read_groups(o, g, (hipStream_t)stream); if (rc) return rc;
+    for (size_t i = 0; i < g.size(); ++i) {
+        if (t) t[i] = g[i].t;
+        if (h_abs) h_abs[i] = g[i].h_abs;
+        if (nfev) nfev[i] = g[i].nfev;
+        if (status) status[i] = g[i].status;
+        if (steps) steps[i] = g[i].steps;
+    }
+    return USE_OK;
+}
+
+int use_ode_result(use_ode* o, void* out, int* nfev, int* status, use_stream_t stream) {
+    if (!o || !out) return fail(USE_E_INVALID, "null argument");
+    launch_ode_result(o->d, (float2*)out, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return use_ode_state(o, nullptr, nullptr, nfev, status, nullptr, stream);
+}
+
+int use_set_ode(use_handle* h, const use_ode_config* oc) {
+    int rc = check_ready(h); if (rc) return rc;
+    if (h->cfg.unconditional || h->cfg.input_channels == 2 || h->cfg.no_sigma_scale)
+        return fail(USE_E_STATE, "the ODE sampler needs the conditional 4- or 6-channel score network");
+    rc = ode_check_config(oc); if (rc) return rc;
+    h->oc = *oc;
+    h->ode_set = true;
+    return USE_OK;
+}
+
+int use_sample_ode(use_handle* h, const void* y, const void* cond, const void* cond2, const void* noise, uint64_t seed, void* out,
+                   int* nfev, int* status, use_stream_t stream) {
+    int rc = check_ready(h); if (rc) return rc;
+    if (!h->ode_set) return fail(USE_E_STATE, "use_set_ode has not been called");
+    if (!y || !out) return fail(USE_E_INVALID, "null tensor");
+    if ((h->cfg.input_channels == 6) != (cond2 != nullptr))
+        return fail(USE_E_INVALID, h->cfg.input_channels == 6 ? "a 6-channel network samples with two conditioning tensors"
+                                                              : "this network takes one conditioning tensor");
+    hipStream_t s = (hipStream_t)stream;
+    const long n_per_b = (long)h->cfg.n_freq * h->T, n = (long)h->B * n_per_b;
+    use_ode* o = h->ode_run;
+    if (!o || o->d.B != h->B || o->d.n_per_b != n_per_b || memcmp(&o->cfg, &h->oc, sizeof h->oc)) {
+        HIPCHK(hipStreamSynchronize(s));
+        if (h->ode_graph) { (void)hipGraphExecDestroy(h->ode_graph); h->ode_graph = nullptr; }   // it holds the old stepper's buffers
+        if (o) (void)use_ode_destroy(o);
+        h->ode_run = nullptr;
+        rc = use_ode_create(h, h->B, n_per_b, &h->oc, &h->ode_run); if (rc) return rc;
+        o = h->ode_run;
+    }
+    rc = load_sampler_inputs(h, y, cond, cond2, s); if (rc) return rc;
+    o->d.ysde = h->Y;
+    const float2* c2 = h->pcp == 8 ? h->cond2_buf : nullptr;
+    auto eval = [&](int row) {                              // the network at the items' stage times, into h->score
+        const float* t = o->d.ts + (size_t)row * h->B;
+        run_temb(h, t, h->B, h->silu_temb, h->tembias, s);
+        run_score(h, o->d.xin, h->Cond, h->tembias, h->dense_rows, t, 1, h->score, s, -1.f, c2);
+    };
+    auto step = [&](hipStream_t st) {                       // one RK45 attempt per running group: 6 evaluations
+        for (int r = 1; r <= 6; ++r) {
+            const float* t = o->d.ts + (size_t)r * h->B;
+            run_temb(h, t, h->B, h->silu_temb, h->tembias, st);
+            run_score(h, o->d.xin, h->Cond, h->tembias, h->dense_rows, t, 1, h->score, st, -1.f, c2);
+            ode_supply_impl(o, h->score, 1, st);
+        }
+    };
+    // 1. prior: draw 0 of the Philox stream (use_sample's), or the given draw
+    hipLaunchKernelGGL(set_rng_kernel, dim3(1), dim3(1), 0, s, h->rng_state, (unsigned long long)seed, 0ull);
+    launch_prior(h->Y, (const float2*)noise, RngRef{h->rng_state, 0}, ouve_std(h->cfg, 1.0f), o->d.xin, n, s);
+    // 2. f0 and select_initial_step
+    ode_start_impl(o, s);
+    eval(0); ode_supply_impl(o, h->score, 1, s);
+    if (o->phase == 7) { eval(7); ode_supply_impl(o, h->score, 1, s); }
+    HIPCHK(hipGetLastError());
+    rc = eval_status(h); if (rc) return rc;
+    // 3. steps until every group is done
+    if (h->oc.use_graph) {
+        const std::vector<const void*> key = {o, o->buf, h->persist, h->arena.base, h->Cond, c2, h->Y, h->blob};   // (use_plan drops it too)
+        if (h->ode_graph && key != h->ode_graph_key) { (void)hipGraphExecDestroy(h->ode_graph); h->ode_graph = nullptr; }
+        if (!h->ode_graph) {
+            rc = ensure_cap_stream(h); if (rc) return rc;
+            hipGraph_t g = nullptr;
+            HIPCHK(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
+            step(h->cap_stream);
+            hipError_t e = hipStreamEndCapture(h->cap_stream, &g);
+            o->phase = 1;
+            if (eval_status(h)) { if (g) (void)hipGraphDestroy(g); (void)hipGetLastError(); return USE_E_STATE; }
+            if (e != hipSuccess || !g) {
+                if (g) (void)hipGraphDestroy(g);
+                (void)hipGetLastError();
+                return fail(USE_E_HIP, "capturing the RK45 step failed: %s", hipGetErrorString(e));
+            }
+            e = hipGraphInstantiate(&h->ode_graph, g, nullptr, nullptr, 0);
+            (void)hipGraphDestroy(g);
+            if (e != hipSuccess) { h->ode_graph = nullptr; return fail(USE_E_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e)); }
+            h->ode_graph_key = key;
+            ++h->n_graph_captures;
+        }
+    }
+    for (;;) {
+        bool done = false;
+        rc = ode_all_done(o, s, &done); if (rc) return rc;
+        if (done) break;
+        if (h->ode_graph && h->oc.use_graph) HIPCHK(hipGraphLaunch(h->ode_graph, s));
+        else { step(s); HIPCHK(hipGetLastError()); rc = eval_status(h); if (rc) return rc; }
+    }
+    // 4. denoise: one reverse-diffusion step at t_eps without its noise (x_mean); 5. out
+    launch_ode_result(o->d, h->X, s);
+    if (h->oc.denoise) {
+        hipLaunchKernelGGL(fill_f32_kernel, dim3(1), dim3(256), 0, s, h->t_dev, h->oc.t_eps, h->B);
+        run_temb(h, h->t_dev, h->B, h->silu_temb, h->tembias, s);
+        run_score(h, h->X, h->Cond, h->tembias, h->dense_rows, h->t_dev, 1, h->score, s, -1.f, c2);
+        float cd, cs, cn; predictor_coeffs(h->cfg, USE_PRED_REVERSE_DIFFUSION, h->oc.t_eps, h->oc.N, cd, cs, cn);
+        launch_predictor(h->X, h->Y, h->score, nullptr, RngRef{h->rng_state, 1}, cd, cs, cn, h->Xmean, (float2*)out, n, s);
+    } else {
+        HIPCHK(hipMemcpyAsync(out, h->X, (size_t)n * 8, hipMemcpyDeviceToDevice, s));
+    }
+    HIPCHK(hipGetLastError());
+    rc = eval_status(h); if (rc) return rc;
+    std::vector<OdeGroup> g;
+    rc = ode_read_groups(o, g, s); if (rc) return rc;
+    h->ode_steps = h->ode_rejected = h->ode_nfev_max = 0;
+    for (size_t i = 0; i < g.size(); ++i) {
+        h->ode_steps += g[i].steps; h->ode_rejected += g[i].nrej; h->ode_nfev_max = std::max<long long>(h->ode_nfev_max, g[i].nfev);
+        if (nfev) nfev[i] = g[i].nfev;
+        if (status) status[i] = g[i].status;
+    }
     return USE_OK;
 }
 

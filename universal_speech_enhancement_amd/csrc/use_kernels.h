@@ -218,4 +218,40 @@ void launch_corrector(const float2* x, const float2* score, const float2* noise,
                       float step_host, float2* x_out, float2* x_mean, long n, hipStream_t s);
 void launch_fill_noise(float2* out, RngRef rng, long n, hipStream_t s);
 
+// ---- probability-flow ODE sampler (use_ode.hip): scipy's RK45 on the device, one step-size controller per group of items ----
+struct OdeGroup {                          // controller state of one group (scipy's RungeKutta solver object)
+    double t, h_abs, h, t_new, min_step, h0, d1;
+    int status;                            // 1 running, 0 reached t_bound, -1 step below min_step (scipy's failure), -2 max_nfe reached
+    int rejected, accepted, nfev, steps, nrej;
+};
+struct OdeDev {                            // device buffers of one integration (n = B * n_per_b complex elements)
+    double2 *y, *ynew;                     // solution and candidate, fp64
+    float2* K;                             // stages K0..K6, complex64 [7][n]
+    float2* xin;                           // the network's next input (complex64)
+    const float2* ysde;                    // the SDE's y (drift theta (y - x))
+    double* h_item;                        // [B] signed step of the item's group (0: frozen)
+    float *ts, *cg;                        // [8][B] stage times (float32, as the network sees them) and g(t)^2 / 2 at them
+    double* part;                          // [2][B][nblk] reduction partials
+    OdeGroup* grp;
+    int* done;                             // 1 when no group is running
+    long n_per_b;
+    int B, G, nblk;                        // G items per group
+    float theta;
+    double rtol, atol;
+};
+struct OdeCtl {
+    double t0, t_bound, first_step, max_step;
+    int max_nfe, ngroups, G, B, nblk;
+    long n_per_b;
+    float sigma_min, base, sq2ls;          // sigma_min, sigma_max / sigma_min and sqrt(2 log(sigma_max / sigma_min)), each as float32
+};
+enum { ODE_START = 0, ODE_INIT1 = 1, ODE_INIT2 = 2, ODE_STEP = 3 };
+void launch_ode_load(const OdeDev& d, hipStream_t s);                                         // y = xin
+// row 0: f0 (+ the d0 / d1 partials of select_initial_step); 1..5: stage K_row and the next input (5: y_new); 6: FSAL stage + error
+// partials; 7: f1 of select_initial_step (+ d2 partials).  kind 1: f is the network's score, 0: f is the drift itself
+void launch_ode_stage(const OdeDev& d, int row, const float2* f, int kind, hipStream_t s);
+void launch_ode_commit(const OdeDev& d, double coef, hipStream_t s);                         // accept (per group) + first stage input
+void launch_ode_ctrl(const OdeCtl& c, const OdeDev& d, int mode, hipStream_t s);              // one workgroup
+void launch_ode_result(const OdeDev& d, float2* out, hipStream_t s);                          // out = complex64(y)
+
 }  // namespace use

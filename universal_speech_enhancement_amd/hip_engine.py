@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import UseConfig, UseHipError, UseSamplerConfig, check
+from ._lib import UseConfig, UseHipError, UseOdeConfig, UseSamplerConfig, check
 
 
 def _stream_ptr(device) -> int:
@@ -310,6 +310,30 @@ class HipScoreEngine:
                                       _stream_ptr(y.device)), "use_sample_cond2")
         return out
 
+    # ---- probability-flow ODE sampler (use_set_ode / use_sample_ode) --------------------------------------
+    def set_ode(self, rtol=1e-5, atol=1e-5, t_eps=3e-2, N=30, group=0, denoise=True, first_step=None, max_step=None, max_nfe=0,
+                use_graph=True):
+        """Configure the ODE sampler for the current plan (``use_set_ode``); ``group``: items per step-size controller (0: the batch)."""
+        oc = ode_config(rtol, atol, t_eps, N, group, denoise, first_step, max_step, max_nfe, use_graph)
+        check(self.L.use_set_ode(self.h, C.byref(oc)), "use_set_ode")
+        self.ode_groups = -(-self.plan_shape[0] // (group or self.plan_shape[0]))
+
+    def sample_ode(self, y: torch.Tensor, noise: Optional[torch.Tensor] = None, seed: int = 0, cond: Optional[torch.Tensor] = None,
+                   cond2: Optional[torch.Tensor] = None):
+        """RK45 probability-flow ODE sampler on y (complex64 [B,1,F,T']), configured by ``set_ode``: returns (x, nfev per group,
+        status per group).  ``noise``: the prior's draw [B,1,F,T'] (else draw 0 of the Philox stream of ``seed``)."""
+        y = _require_cuda_c64("y", y)
+        if (y.shape[0], y.shape[3]) != self.plan_shape:
+            raise UseHipError(f"sampler planned for {self.plan_shape}, got B={y.shape[0]} T'={y.shape[3]}")
+        cptr = None if cond is None or cond is y else _require_cuda_c64("cond", cond, y.shape).data_ptr()
+        c2ptr = None if cond2 is None else _require_cuda_c64("cond2", cond2, y.shape).data_ptr()
+        nptr = None if noise is None else _require_cuda_c64("noise", noise, y.shape).data_ptr()
+        out = torch.empty_like(y)
+        nfev, status = (C.c_int * y.shape[0])(), (C.c_int * y.shape[0])()     # n_groups <= B entries
+        check(self.L.use_sample_ode(self.h, y.data_ptr(), cptr, c2ptr, nptr, int(seed) & (2**64 - 1), out.data_ptr(), nfev, status,
+                                    _stream_ptr(y.device)), "use_sample_ode")
+        return out, list(nfev)[: self.ode_groups], list(status)[: self.ode_groups]
+
     def fill_noise(self, seed: int, draw: int, shape) -> torch.Tensor:
         """Draw ``draw`` of the device noise stream of ``sample(noise=None, seed=seed)`` as a complex64 tensor of ``shape`` = the whole
         batch tensor [B,1,F,T'] (``use_fill_noise``): draw 0 is the prior's, then per reverse step the corrector draws and the
@@ -360,3 +384,86 @@ class HipScoreEngine:
                                        None if noise is None else _require_cuda_c64("noise", noise, x.shape).data_ptr(), int(seed),
                                        xo.data_ptr(), xm.data_ptr(), x.numel(), _stream_ptr(x.device)), "use_sde_corrector")
         return xo, xm
+
+
+def ode_config(rtol=1e-5, atol=1e-5, t_eps=3e-2, N=30, group=0, denoise=True, first_step=None, max_step=None, max_nfe=0,
+               use_graph=True) -> UseOdeConfig:
+    return UseOdeConfig(float(rtol), float(atol), float(t_eps), int(N), int(group), int(bool(denoise)), float(first_step or 0.0),
+                        float(max_step or 0.0) if max_step not in (None, np.inf) else 0.0, int(max_nfe), int(bool(use_graph)))
+
+
+class OdeStepper:
+    """The library's RK45 stepper driven from Python (``use_ode_*``, reverse communication): for callers whose drift is not the
+    fused network, e.g. ``sampling.get_ode_sampler`` with any ``score_fn`` callable.
+
+        st = OdeStepper(engine, y_sde, x0, rtol=..., group=...)
+        while (req := st.request()) is not None:
+            x, t = req
+            st.supply(drift(x, t))            # or st.supply(score, kind="score")
+        x, nfev, status = st.result()
+    """
+
+    def __init__(self, engine: "HipScoreEngine", y_sde: torch.Tensor, x0: torch.Tensor, record_times: bool = True, **cfg):
+        y_sde = _require_cuda_c64("y_sde", y_sde)
+        x0 = _require_cuda_c64("x0", x0, y_sde.shape)
+        self.L, self.shape, self.device = engine.L, tuple(y_sde.shape), y_sde.device
+        B = self.shape[0]
+        oc = ode_config(**cfg)
+        o = C.c_void_p()
+        check(self.L.use_ode_create(engine.h, B, y_sde[0].numel(), C.byref(oc), C.byref(o)), "use_ode_create")
+        self.o, self.engine = o, engine          # the engine owns the device context the stepper was made on
+        self.ng = check(self.L.use_ode_num_groups(o))
+        self.x = torch.empty_like(y_sde)
+        self.t = torch.empty(B, dtype=torch.float32, device=y_sde.device)
+        self.record_times = record_times         # run(): one state read per step (the step already synchronises once)
+        self.n_init = 1 if cfg.get("first_step") else 2
+        self.times = [[1.0] for _ in range(self.ng)]   # per group: the accepted times (solution.t of solve_ivp)
+        check(self.L.use_ode_start(o, y_sde.data_ptr(), x0.data_ptr(), _stream_ptr(self.device)), "use_ode_start")
+
+    def request(self):
+        """(x, t) to evaluate the drift at, or None when every group is done."""
+        rc = check(self.L.use_ode_request(self.o, self.x.data_ptr(), self.t.data_ptr(), _stream_ptr(self.device)), "use_ode_request")
+        return (self.x, self.t) if rc == 1 else None
+
+    def supply(self, f: torch.Tensor, kind: str = "drift"):
+        f = _require_cuda_c64("f", f, self.shape)
+        check(self.L.use_ode_supply(self.o, f.data_ptr(), {"drift": 0, "score": 1}[kind], _stream_ptr(self.device)), "use_ode_supply")
+
+    def state(self):
+        """Per group: (t, h_abs, nfev, status, accepted steps) - synchronises."""
+        t, h = (C.c_double * self.ng)(), (C.c_double * self.ng)()
+        nf, st, sp = (C.c_int * self.ng)(), (C.c_int * self.ng)(), (C.c_int * self.ng)()
+        check(self.L.use_ode_state(self.o, t, h, nf, st, sp, _stream_ptr(self.device)), "use_ode_state")
+        return list(t), list(h), list(nf), list(st), list(sp)
+
+    def run(self, drift_fn, kind: str = "drift"):
+        """Drive the integration to its end with ``drift_fn(x, t)``; returns (x, nfev per group, status per group)."""
+        k = 0
+        while True:
+            req = self.request()
+            if req is None:
+                break
+            self.supply(drift_fn(*req), kind)
+            k += 1
+            if self.record_times and k > self.n_init and (k - self.n_init) % 6 == 0:     # a step ended: its accepted times
+                for g, tg in enumerate(self.state()[0]):
+                    if tg != self.times[g][-1]:
+                        self.times[g].append(tg)
+        return self.result()
+
+    def result(self):
+        out = torch.empty(self.shape, dtype=torch.complex64, device=self.device)
+        nf, st = (C.c_int * self.ng)(), (C.c_int * self.ng)()
+        check(self.L.use_ode_result(self.o, out.data_ptr(), nf, st, _stream_ptr(self.device)), "use_ode_result")
+        return out, list(nf), list(st)
+
+    def close(self):
+        if getattr(self, "o", None):
+            self.L.use_ode_destroy(self.o)
+            self.o = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

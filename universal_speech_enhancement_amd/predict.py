@@ -2,6 +2,8 @@
 
     python -m universal_speech_enhancement_amd.predict model=SGMSE_Large ckpt_path=last.ckpt \
         data.data_folder=noisy/ data.target_folder=enhanced/ [model.Score.precision=fp32] [model.sampler_kwargs.N=30]
+        [model.sampler_kwargs.sampler_type=ode [model.sampler_kwargs.rtol=1e-5 model.sampler_kwargs.atol=1e-5
+         model.sampler_kwargs.minibatch=1]]      (the probability-flow ODE sampler: RK45, one step-size controller per utterance)
 
 Hydra and Lightning are not available on the target image, so this is a small stand-in: the same YAML groups
 (``configs/predict.yaml`` -> ``data/``, ``model/``), ``key=value`` / ``group=name`` overrides, ``_target_`` instantiation,

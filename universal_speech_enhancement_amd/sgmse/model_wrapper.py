@@ -3,7 +3,9 @@
 score network and the whole reverse-SDE loop in libuse_hip.so.
 
 Additions over the reference (all optional, defaults reproduce stock behaviour): ``precision`` ("bf16" | "fp32"),
-``use_graph``, and ``noise`` / ``seed`` keywords on ``sample`` / ``enhance`` for reproducible runs.
+``use_graph``, and ``noise`` / ``seed`` keywords on ``sample`` / ``enhance`` for reproducible runs.  ``sampler_type="ode"`` runs the
+probability-flow ODE sampler (RK45 on the device) with the score's conditioning, which the reference's own ODE path does not pass
+(DESIGN.md section 7).
 ``train_step`` returns the loss with its tape once ``score_net.requires_grad_(True)`` was called (fp32 HIP operators forward and
 backward: ``training.py``); with frozen parameters it is the forward-only value of the sampling engine.
 """
@@ -151,11 +153,30 @@ class ScoreModel(SpectralGlue, nn.Module):
             return torch.cat(samples, dim=0), ns
         return batched_sampling_fn
 
-    def get_ode_sampler(self, *args, **kwargs):
-        raise NotImplementedError("the probability-flow ODE sampler (scipy RK45 host solver) is not on the predict path")
+    def fused_sample_ode(self, y, N, t_eps, group=0, rtol=1e-5, atol=1e-5, denoise=True, noise=None, seed=0, use_graph=True, sde=None,
+                         cond=None, cond2=None, first_step=None, max_step=None, max_nfe=0):
+        """Probability-flow ODE sampler inside libuse_hip.so (``use_sample_ode``): RK45 with one step-size controller per ``group``
+        items (0: the batch); returns (x, nfev per group, status per group)."""
+        sde = self.sde if sde is None else sde
+        eng = self.score_net.engine(y.shape[2], y.device, sde_constants=(sde.theta, sde.sigma_min, sde.sigma_max))
+        eng.plan(y.shape[0], y.shape[3])
+        eng.set_ode(rtol=rtol, atol=atol, t_eps=t_eps, N=N, group=group, denoise=denoise, first_step=first_step, max_step=max_step,
+                    max_nfe=max_nfe, use_graph=use_graph)
+        return eng.sample_ode(y, noise=noise, seed=seed, cond=cond, cond2=cond2)
 
-    def sample(self, batch, sampler_type="pc", N=50, corrector_steps=1, snr=0.5, noise=None, seed=0):
-        """Reference :262-329: adds ``batch['enhanced']`` (float32 [B, L]) for condition / sde_input 'noisy'."""
+    def get_ode_sampler(self, y, N=None, minibatch=1, **kwargs):
+        """Reference :238-260: ``(x, [nfe per minibatch])``, or ``(x, nfe)`` for ``minibatch=None``.  Every minibatch is its own RK45
+        integration, as the reference's loop makes it - here one fused call with one step-size controller per minibatch."""
+        N = self.sde.N if N is None else N
+        sde = self.sde.copy()
+        sde.N = N
+        kwargs = {"eps": self.t_eps, "use_graph": self.use_graph, **kwargs}
+        return sampling.get_ode_sampler(sde, self, y=y, minibatch=minibatch, **kwargs)
+
+    def sample(self, batch, sampler_type="pc", N=50, corrector_steps=1, snr=0.5, noise=None, seed=0, **ode_kwargs):
+        """Reference :262-329: adds ``batch['enhanced']`` (float32 [B, L]) for condition / sde_input 'noisy'.
+        ``sampler_type="ode"``: the probability-flow ODE sampler (``get_ode_sampler``; ``ode_kwargs``: ``rtol``, ``atol``,
+        ``minibatch`` (default 1), ``first_step``, ``max_step``, ``max_nfe``); its NFE is left in ``self.last_nfe``."""
         y = batch["perturbed"]
         T_orig = y.size(1)
         Y = self._spectrogram(y)
@@ -176,11 +197,17 @@ class ScoreModel(SpectralGlue, nn.Module):
             sde_input = Y
         else:
             raise NotImplementedError(f"Don't know the sde input you have wished for: {self.sde_input}")
-        if sampler_type != "pc":
+        if sampler_type == "pc":
+            if ode_kwargs:
+                raise TypeError(f"sample(sampler_type='pc') got ODE sampler options {sorted(ode_kwargs)}")
+            sampler = self.get_pc_sampler(self.predictor, self.corrector, sde_input, N=N, corrector_steps=corrector_steps, snr=snr,
+                                          intermediate=False, conditioning=score_conditioning, noise=noise, seed=seed)
+        elif sampler_type == "ode":                                      # reference :314-316
+            sampler = self.get_ode_sampler(sde_input, N=N, conditioning=score_conditioning, noise=noise, seed=seed, **ode_kwargs)
+        else:
             raise NotImplementedError(f"{sampler_type} is not a valid sampler type!")
-        sampler = self.get_pc_sampler(self.predictor, self.corrector, sde_input, N=N, corrector_steps=corrector_steps, snr=snr,
-                                      intermediate=False, conditioning=score_conditioning, noise=noise, seed=seed)
         sample, nfe = sampler()
+        self.last_nfe = nfe
         # reference :320-328: the key depends on what the SDE started from
         batch["fake_sde_enhanced" if (self.sde_input == "denoised" and Y_denoised is not None) else "enhanced"] = self._waveform(sample, T_orig)
         return batch
@@ -198,10 +225,13 @@ class ScoreModel(SpectralGlue, nn.Module):
         if not y.is_cuda:
             y = y.cuda()
         Y = self._spectrogram(y)
-        if sampler_type != "pc":
+        if sampler_type == "pc":
+            sample, nfe = self.get_pc_sampler(predictor, corrector, Y, N=N, corrector_steps=corrector_steps, snr=snr,
+                                              intermediate=False, conditioning=[Y], noise=noise, seed=seed)()
+        elif sampler_type == "ode":                                      # legacy model.py:384-385
+            sample, nfe = self.get_ode_sampler(Y, N=N, conditioning=[Y], noise=noise, seed=seed, **kwargs)()
+        else:
             raise NotImplementedError(f"{sampler_type} is not a valid sampler type!")
-        sample, nfe = self.get_pc_sampler(predictor, corrector, Y, N=N, corrector_steps=corrector_steps, snr=snr,
-                                          intermediate=False, conditioning=[Y], noise=noise, seed=seed)()
         if return_stft:
             return sample.squeeze(), Y.squeeze(), T_orig, norm_factor
         x_hat = (self._waveform(sample, T_orig) * norm_factor).squeeze().cpu()

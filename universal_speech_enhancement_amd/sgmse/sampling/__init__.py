@@ -1,12 +1,14 @@
-"""Predictor-corrector sampling with the reference's call surface
-(``sgmse/sampling/__init__.py:23-73`` ``get_pc_sampler``).
+"""Predictor-corrector and probability-flow ODE sampling with the reference's call surface
+(``sgmse/sampling/__init__.py:23-73`` ``get_pc_sampler``, ``:76-159`` ``get_ode_sampler``).
 
-Two execution paths, same numerics:
+Two execution paths each, same numerics:
   * fused  -- when ``score_fn`` is the HIP-backed ``ScoreModel`` and predictor / corrector are built-ins, the whole
               loop (prior sampling, N x (corrector, predictor), all score evaluations) runs inside
               ``use_sample`` and is replayed as one hipGraph;
   * seam   -- any other ``score_fn`` callable or user-registered predictor / corrector: the loop below drives
               ``update_fn`` exactly like the reference (corrector before predictor, returns ``x_mean``).
+The ODE sampler integrates with scipy's RK45 reproduced on the device (``use_sample_ode`` when fused, the ``use_ode_*`` stepper
+driven from here on the seam path); scipy is not needed at run time.
 """
 from __future__ import annotations
 
@@ -17,7 +19,7 @@ import torch
 from .correctors import Corrector, CorrectorRegistry, _HipCorrector, NoneCorrector
 from .predictors import Predictor, PredictorRegistry, _HipPredictor, NonePredictor
 
-__all__ = ["PredictorRegistry", "CorrectorRegistry", "Predictor", "Corrector", "get_pc_sampler"]
+__all__ = ["PredictorRegistry", "CorrectorRegistry", "Predictor", "Corrector", "get_pc_sampler", "get_ode_sampler"]
 
 _SDE_ENGINES: Dict[Tuple, object] = {}
 
@@ -28,7 +30,7 @@ def _sde_engine(sde, device):
     dev = torch.device(device).index
     dev = torch.cuda.current_device() if dev is None else dev
     key = (dev, float(sde.theta), float(sde.sigma_min), float(sde.sigma_max))
-    if key not in _SDE_ENGINES:
+    if key not in _SDE_ENGINES:   # (a weight-less handle: the stepper and the use_sde_* kernels only read its SDE constants)
         _SDE_ENGINES[key] = HipScoreEngine(device=dev, theta=sde.theta, sigma_min=sde.sigma_min, sigma_max=sde.sigma_max)
     return _SDE_ENGINES[key]
 
@@ -100,3 +102,83 @@ def get_pc_sampler(predictor_name, corrector_name, sde, score_fn, y, denoise=Tru
             return x_result, sde.N * (corrector.n_steps + 1)
 
     return pc_sampler
+
+
+_ODE_SOLVER_OPTIONS = ("first_step", "max_step", "max_nfe")
+
+
+def get_ode_sampler(sde, score_fn, y, inverse_scaler=None, denoise=True, rtol=1e-5, atol=1e-5, method="RK45", eps=3e-2,
+                    device="cuda", conditioning=None, noise=None, seed=0, minibatch=None, use_graph=True, **kwargs):
+    """Returns ``ode_sampler() -> (x, nfe)``: the probability-flow ODE of ``sde`` integrated from T = 1 down to ``eps`` by RK45
+    (scipy's ``solve_ivp(method="RK45")``, reproduced on the device), then with ``denoise`` one noise-free reverse-diffusion step.
+
+    Over the reference: ``conditioning`` (the score's conditioning, as for ``get_pc_sampler``; the reference's drift calls
+    ``score_model(x, t, y)``, which its own ``ScoreModel`` rejects - DESIGN.md section 7), ``noise`` (the prior's draw, complex64 like
+    ``y``), ``seed`` (device Philox stream), ``minibatch`` (items per step-size controller: each group is its own integration with its
+    own step sizes and NFE, as ``ScoreModel.get_ode_sampler(minibatch=k)`` runs them; ``None`` = one integration over the batch -
+    then ``nfe`` is an int, else a list per group), ``use_graph``.  Solver options: scalar ``rtol`` / ``atol``, ``first_step``,
+    ``max_step``, and ``max_nfe`` (evaluations per group before the integration stops with status -2, default 10000).  ``device`` is
+    accepted for the reference's signature: the sampler runs on ``y``'s device.  ``ode_sampler.stats`` holds NFE and status per group
+    after a call (0: reached ``eps``; -1: scipy's step-size failure, the last accepted state is returned; -2: ``max_nfe``), and on the
+    seam path the accepted times (``solution.t``).
+    """
+    if method != "RK45":
+        raise NotImplementedError(f"get_ode_sampler: method={method!r} is not implemented (RK45 only)")
+    extra = sorted(k for k in kwargs if k not in _ODE_SOLVER_OPTIONS)
+    if extra:
+        raise NotImplementedError(f"get_ode_sampler: solver option(s) {extra} are not implemented")
+    for name, v in (("rtol", rtol), ("atol", atol)):
+        if not isinstance(v, (int, float)) and not (hasattr(v, "ndim") and v.ndim == 0):
+            raise NotImplementedError(f"get_ode_sampler: {name} must be a scalar (vector tolerances are not implemented)")
+    if float(getattr(sde, "T", 1)) != 1.0:
+        raise NotImplementedError("get_ode_sampler: the device stepper integrates from T = 1")
+    opts = {k: kwargs[k] for k in _ODE_SOLVER_OPTIONS if k in kwargs}
+    group = 0 if minibatch is None else int(minibatch)
+    if noise is not None and noise.dim() == y.dim() + 1:
+        noise = noise[0]                     # the PC layout [n_draws, *y.shape]: the prior is draw 0
+
+    from ..sdes import OUVESDE
+    fused = (type(sde) is OUVESDE and getattr(score_fn, "supports_fused_sampler", False)
+             and (conditioning is None or (len(conditioning) in (1, 2) and all(c.shape == y.shape for c in conditioning))))
+
+    def _nfe(nfev):
+        return nfev[0] if minibatch is None else list(nfev)
+
+    if fused:
+        def ode_sampler():
+            with torch.no_grad():
+                cond = [None, None] if conditioning is None else list(conditioning) + [None]
+                x, nfev, status = score_fn.fused_sample_ode(y, N=sde.N, t_eps=eps, rtol=rtol, atol=atol, group=group, denoise=denoise,
+                                                            noise=noise, seed=seed, use_graph=use_graph, sde=sde, cond=cond[0],
+                                                            cond2=cond[1], **opts)
+                ode_sampler.stats = {"nfev": nfev, "status": status}
+                if inverse_scaler is not None:
+                    x = inverse_scaler(x)
+            return x, _nfe(nfev)
+        return ode_sampler
+
+    def ode_sampler():
+        from ...hip_engine import OdeStepper
+        from .predictors import ReverseDiffusionPredictor
+        with torch.no_grad():
+            x0 = (sde.prior_sampling(y.shape, y, noise=noise, seed=seed) if isinstance(sde, OUVESDE)
+                  else sde.prior_sampling(y.shape, y))
+            rsde = sde.reverse(score_fn, probability_flow=True)
+            kw = {} if conditioning is None else {"conditioning": conditioning}
+            consts = sde if all(hasattr(sde, a) for a in ("theta", "sigma_min", "sigma_max")) else OUVESDE()
+            stepper = OdeStepper(_sde_engine(consts, y.device), y, x0, rtol=rtol, atol=atol, t_eps=eps, N=sde.N, group=group,
+                                 denoise=False, use_graph=False, **opts)
+            try:
+                # the reference's drift_fn: the reverse SDE's drift with probability_flow=True (sampling/__init__.py:112-114)
+                x, nfev, status = stepper.run(lambda xs, t: rsde.sde(xs, t, y, **kw)[0])
+                ode_sampler.stats = {"times": stepper.times, "nfev": nfev, "status": status}   # solution.t / nfev / status per group
+            finally:
+                stepper.close()
+            if denoise:                      # one reverse-diffusion step at eps, x_mean (sampling/__init__.py:107-110)
+                predictor = ReverseDiffusionPredictor(sde, score_fn, probability_flow=False)
+                vec_eps = torch.ones(y.shape[0], device=y.device) * eps
+                _, x = predictor.update_fn(x, vec_eps, y, **kw)
+            if inverse_scaler is not None:
+                x = inverse_scaler(x)
+        return x, _nfe(nfev)
+    return ode_sampler
