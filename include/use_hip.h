@@ -163,7 +163,9 @@ int use_sample_ode(use_handle* h, const void* y, const void* cond, const void* c
  * both copied).  _request: 1 = evaluate the drift at (x, t) - x complex64 [n], t float32 [B] (device) - and _supply it; 0 = every
  * group is done (synchronises the stream once per step).  _supply: kind 0 = f is the drift, 1 = f is the OUVE score at (x, t)
  * (the drift is formed on the device).  _result: out = complex64 of the solution, per-group nfev / status (host, may be null).
- * _state: per-group t, h_abs, nfev, status, accepted steps (host arrays, may be null; synchronises). */
+ * _state: per-group t, h_abs, nfev, status, accepted steps (host arrays, may be null; synchronises).  As scipy's solver object:
+ * t and h_abs change only when a step is accepted (after status -1 or -2 they are the last accepted step's), and nfev counts the
+ * evaluations supplied so far. */
 typedef struct use_ode use_ode;
 int use_ode_create(use_handle* h, int B, int64_t n_per_item, const use_ode_config* cfg, use_ode** out);
 int use_ode_start(use_ode* o, const void* y_sde, const void* x0, use_stream_t stream);

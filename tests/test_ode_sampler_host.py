@@ -110,3 +110,27 @@ def test_golden_ode_fixture_is_reproduced_by_scipy(golden_dir, name):
     np.testing.assert_allclose(x, g["x"], rtol=1e-5, atol=1e-6)
     if name == "ode_items":
         assert int(g["rejected"].sum()) >= 1
+
+
+def test_ode_ref_drift_families_reach_their_branches_in_scipy():
+    """tests/test_hip_ode_stepper.py compares the device stepper with scipy on the drift families of tests/ode_ref.py; each family is
+    there for a branch of scipy's RK45, and this checks, without a device, that scipy still takes it."""
+    import ode_ref as R                                                         # scipy.integrate, imported by this test only
+    x = {name: fam.x0(5, 16) for name, fam in R.FAMILIES.items()}
+    run = {name: [R.scipy_rk45(R.FAMILIES[name].f, x[name][it], it, 1e-5, 1e-5) for it in R.groups_of(5, 2)] for name in R.FAMILIES}
+    for name, trs in run.items():
+        for tr in trs:
+            assert tr.calls == tr.nfev and tr.rejected == (tr.nfev - 2) // 6 - tr.steps
+            assert tr.status == (R.TOO_SMALL_STEP if name == "blowup" else 0), name
+    assert sum(tr.rejected for tr in run["jump"]) > 0                           # rejected steps
+    assert all(tr.rejected > 0 and tr.records[-1][0] > 0.7 for tr in run["blowup"])   # status -1 before the pole at t ~ 0.75
+    assert all(tr.capped > 0 for tr in run["blowup"])                           # retries where factor = min(1, factor) acts
+    for name in ("zero", "zerostart"):                                          # d0 < 1e-5: h0 = 1e-6, the probe at t0 - h0
+        assert all(tr.call_t[1] == 1.0 - 1e-6 for tr in run[name]), name
+    for tr in run["zero"]:                                                      # d1, d2 <= 1e-15: h1 = 1e-6; every error norm 0
+        assert tr.records[0][1] == 1e-6 and tr.err_norms and set(tr.err_norms) == {0.0}
+        # factor = MAX_FACTOR (of the attempt's h = t_new - t, which is h_abs up to the rounding of t_new)
+        assert all(abs(b[1] / a[1] - 10) < 1e-6 or b[3] == 0 for a, b in zip(tr.records, tr.records[1:]))
+    for tr in run["zerostart"]:                                                 # d1 > 0: h0 = 1e-6, h_abs = 100 h0
+        assert tr.records[0][1] == 100 * 1e-6 and min(tr.err_norms) > 0
+    assert len({tr.nfev for tr in run["linear"]}) == 3                          # the groups need different NFE

@@ -220,7 +220,8 @@ void launch_fill_noise(float2* out, RngRef rng, long n, hipStream_t s);
 
 // ---- probability-flow ODE sampler (use_ode.hip): scipy's RK45 on the device, one step-size controller per group of items ----
 struct OdeGroup {                          // controller state of one group (scipy's RungeKutta solver object)
-    double t, h_abs, h, t_new, min_step, h0, d1;
+    double t, h_abs;                       // scipy's solver.t and solver.h_abs: changed only when a step is accepted
+    double ha, h, t_new, min_step, h0, d1; // the current attempt (_step_impl's local h_abs, h, t_new, min_step); select_initial_step
     int status;                            // 1 running, 0 reached t_bound, -1 step below min_step (scipy's failure), -2 max_nfe reached
     int rejected, accepted, nfev, steps, nrej;
 };

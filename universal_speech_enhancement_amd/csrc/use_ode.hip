@@ -181,17 +181,17 @@ DEVI void ode_write_items(const OdeCtl& c, OdeDev& d, int g, double t, double h,
     }
 }
 
-// the start of an attempt (rk.py:118-141): clamp h to [min_step, max_step] at a new step, the failure below min_step, the last step
-// clamped onto t_bound; then the stage times.  A group that is done is frozen: h = 0 and every stage at its final t.
+// the start of an attempt (rk.py:118-141): at a new step, the attempt's step size q.ha is q.h_abs clamped to [min_step, max_step]
+// (q.h_abs itself, scipy's self.h_abs, is left alone); the failure below min_step, the last step clamped onto t_bound; then the stage
+// times.  A group that is done is frozen: h = 0 and every stage at its final t.
 DEVI void ode_prepare(const OdeCtl& c, OdeDev& d, int g) {
     OdeGroup& q = d.grp[g];
     if (q.status == 1) {
         if (!q.rejected) {
             q.min_step = 10.0 * fabs(nextafter(q.t, -INFINITY) - q.t);
-            if (q.h_abs > c.max_step) q.h_abs = c.max_step;
-            else if (q.h_abs < q.min_step) q.h_abs = q.min_step;
+            q.ha = q.h_abs > c.max_step ? c.max_step : q.h_abs < q.min_step ? q.min_step : q.h_abs;
         }
-        if (q.h_abs < q.min_step) q.status = -1;                                // scipy: TOO_SMALL_STEP, status -1
+        if (q.ha < q.min_step) q.status = -1;                                   // scipy: TOO_SMALL_STEP, status -1
         else if (q.nfev + 6 > c.max_nfe) q.status = -2;                          // the max_nfe guard
     }
     if (q.status != 1) {
@@ -199,12 +199,11 @@ DEVI void ode_prepare(const OdeCtl& c, OdeDev& d, int g) {
         ode_write_items(c, d, g, q.t, 0.0, 1, 6, kC);
         return;
     }
-    double t_new = q.t - q.h_abs;                                                // direction -1: from T down to eps
+    double t_new = q.t - q.ha;                                                   // direction -1: from T down to eps
     if (t_new < c.t_bound) t_new = c.t_bound;
     q.h = t_new - q.t;
-    q.h_abs = fabs(q.h);
+    q.ha = fabs(q.h);
     q.t_new = t_new;
-    q.nfev += 6;
     ode_write_items(c, d, g, q.t, q.h, 1, 6, kC);
 }
 
@@ -248,15 +247,16 @@ __global__ __launch_bounds__(256) void ode_ctrl_kernel(OdeCtl c, OdeDev d, int m
             ode_prepare(c, d, g);
         } else {                                                                   // ODE_STEP: accept / reject (rk.py:145-166)
             if (q.status == 1) {
+                q.nfev += 6;                                                       // counted once spent, as scipy's nfev
                 const double en = group_norm(c, d, 0, g);
                 if (en < 1) {
                     double factor = en == 0 ? MAX_FACTOR : fmin(MAX_FACTOR, SAFETY * pow(en, ERR_EXP));
                     if (q.rejected) factor = fmin(1.0, factor);
-                    q.h_abs *= factor;
+                    q.h_abs = q.ha * factor;
                     q.t = q.t_new; q.rejected = 0; q.accepted = 1; q.steps += 1;
                     if (q.t <= c.t_bound) q.status = 0;                            // base.py: direction * (t - t_bound) >= 0
                 } else {
-                    q.h_abs *= fmax(MIN_FACTOR, SAFETY * pow(en, ERR_EXP));
+                    q.ha *= fmax(MIN_FACTOR, SAFETY * pow(en, ERR_EXP));
                     q.rejected = 1; q.nrej += 1;
                 }
             }
