@@ -5,6 +5,7 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
     python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR     # + what the last timed step returned, DIR/enhanced_spec.npy
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full                 # + everything beside the headline figure (below)
 
 One "step" = one full pass of the hot path over one batch: the 30-step predictor-corrector sampler
 (reverse_diffusion + Langevin x1, snr 0.5 => 60 score-network evaluations) on B=8 synthetic 4 s / 24 kHz utterances
@@ -13,10 +14,13 @@ replayed as one hipGraph, device Philox noise.  Inputs (compressed STFT spectrog
 timed region; STFT/iSTFT are outside it.  Multi-GPU: utterances are sharded over ranks (weak scaling,
 no data-path collective; one weight-blob broadcast at start-up).
 
-Prints ONE JSON line on rank 0.  `roofline` is measured live with HIP events around every launch of the dominant
-kernel (the activation-dtype implicit-GEMM conv) during one eager score evaluation on the same stream;
-`cpu_baseline` times the CPU oracle (a port of the reference's path, validated against the reference's golden
-vectors) on a bounded sample on this box's host cores.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the
+headline figure; it measures nothing else.  With --full the line also carries: `power_probe`, amdsmi samples taken while
+the timed steps run; `roofline`, measured live with HIP events around every launch of the dominant kernel (the
+activation-dtype implicit-GEMM conv) during one eager score evaluation on the same stream; `secondary`, other sampler
+configurations, precisions and the training step, each timed after the headline steps; and `cpu_baseline`, which times
+the CPU oracle (a port of the reference's path, validated against the reference's golden vectors) on a bounded sample
+on the host cores.
 """
 import argparse
 import json
@@ -163,6 +167,89 @@ def train_step_bench(dev, steps=3):
             "steps_timed": steps, "note": "train_step forward + backward + Adam, the reference's training configuration (SGMSE_Large.yaml, batch 4 x 512 frames)"}
 
 
+def measure_roofline(eng, x, Y, precision, tflops_path):
+    """`roofline` of a --full line: the dominant kernel, and the kernels beside it, of one eager score evaluation of x."""
+    B, _, _, Tp = Y.shape
+    dev = x.device
+    # ---- roofline of the dominant kernel, HIP events per launch on the current stream ----
+    tvec = torch.full((B,), 0.5, device=dev)
+    eng.profile_score(x, Y, tvec)                                   # warm
+    conv_ms, conv_flops, conv_bytes, conv_launches, total_ms = eng.profile_score(x, Y, tvec)
+    # the HBM-bound kernels of the same evaluation (SURVEY.md section 8d: "glue kernels individually: HBM-bound"): algorithmic bytes
+    # (every operand once) / duration between HIP events / 8 TB/s, per kernel class and map, averaged over the launches
+    hbm_kernels = []
+    groups = {}
+    mfma_groups = {}
+    by_map = {}
+    for name, Hm, Wm, by, ms, fl in eng.profile_aux(with_flops=True):
+        if name == "conv_v4":                                       # the dominant kernel's own launches, for the per-map breakdown
+            by_map.setdefault((Hm, Wm), []).append((fl, ms))
+            continue
+        if fl > 0:
+            mfma_groups.setdefault((name, Hm, Wm), []).append((fl, ms))
+        else:
+            groups.setdefault((name, Hm, Wm), []).append((by, ms))
+    # the MFMA-bound kernels beside the dominant one, per kernel class and map: algorithmic FLOPs / HIP-event duration / dense peak
+    mfma_kernels = []
+    for (name, Hm, Wm), v in sorted(mfma_groups.items(), key=lambda kv: -sum(m for _, m in kv[1])):
+        fl = sum(f for f, _ in v); ms = sum(m for _, m in v)
+        mfma_kernels.append({"kernel": name, "map": f"{Hm}x{Wm}", "launches_per_score": len(v), "algorithmic_gflop_per_launch": round(fl / len(v) / 1e9, 2),
+                             "avg_launch_ms": round(ms / len(v), 4), "ms_per_score": round(ms, 3),
+                             "achieved_TFLOPs": round(fl / (ms * 1e-3) / 1e12, 1)})
+    for (name, Hm, Wm), v in sorted(groups.items(), key=lambda kv: (-kv[0][1] * kv[0][2], kv[0][0])):
+        if Hm * Wm < 256 * 320:                                     # the smaller maps are hidden behind the other sub-batch's convolutions
+            continue
+        by = sum(b for b, _ in v) / len(v); ms = sum(m for _, m in v) / len(v)
+        # what actually binds the kernel (DESIGN.md section 7.3): the fused GroupNorm + SiLU costs two quarter-rate transcendentals per
+        # staged element, which puts the FIR down-sampler (each input evaluated 2.25x) and the pyramid heads above their HBM time
+        binds = {"fir_down": "valu (fused SiLU: v_exp + v_rcp per element, 1.7x redundant in the strip walk)",
+                 "pyr_conv": "tile walk (65 us with SiLU and MFMAs ablated) + valu (fused SiLU, rolling halo 1.125x) on producer waves beside the MFMA waves",
+                 "conv_in": "hbm write (tile walk, per-workgroup GroupNorm partial totals)", "fir_up": "hbm"}.get(name, "hbm")
+        hbm_kernels.append({"kernel": name, "map": f"{Hm}x{Wm}", "launches_per_score": len(v), "algorithmic_bytes": round(by),
+                            "avg_ms": round(ms, 4), "achieved_GBps": round(by / (ms * 1e-3) / 1e9, 1),
+                            "frac": round(by / (ms * 1e-3) / (PEAK_HBM_TBPS * 1e12), 4), "binds": binds})
+    peak = PEAK_FP32_TFLOPS if precision == "fp32" else PEAK_BF16_TFLOPS      # bf16 and fp16 MFMA share the dense peak
+    achieved = conv_flops / (conv_ms * 1e-3) / 1e12
+    # HBM traffic per launch comes from rocprofv3 PMC passes (FETCH_SIZE x2 on gfx950 + WRITE_SIZE), which cannot be
+    # collected from inside the timed process: the committed summary of `scripts/profile.sh pmc <tag>` + `scripts/pmc_to_json.py` on this workload is quoted.
+    traffic, traffic_src = None, None
+    if precision == "bf16" and (B, Tp) == (8, 640):   # the PMC passes were collected on exactly this workload
+        import glob
+        import hashlib
+        pm = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_conv_v[45].json")), key=lambda f: (int(os.path.basename(f).split("_")[0][1:] or 0), f))
+        if pm:
+            rec = json.load(open(pm[-1]))
+            src = os.path.join(ROOT, rec.get("kernel_source", "universal_speech_enhancement_amd/csrc/use_conv_v4.hip"))
+            cur = hashlib.sha256(open(src, "rb").read()).hexdigest()[:16] if os.path.exists(src) else None
+            if rec.get("kernel_source_sha16") == cur:            # counters of THIS kernel source, else stale: report null
+                traffic = round(rec["hbm_bytes_per_launch"])
+                traffic_src = os.path.relpath(pm[-1], ROOT)
+            else:
+                traffic_src = f"stale ({os.path.relpath(pm[-1], ROOT)} was collected on another version of {rec.get('kernel_source')})"
+    roofline = {"bound": "mfma", "achieved": round(achieved, 1), "peak": peak, "unit": "TFLOP/s",
+                "frac": round(achieved / peak, 4), "traffic": traffic, "traffic_unit": "HBM bytes per launch",
+                "traffic_source": traffic_src,
+                "algorithmic_hbm_bytes_per_launch": round(conv_bytes / max(conv_launches, 1)),
+                # 16-bit storage: conv_v5_kernel (round 6: conv_v4's tile and pipeline on v_mfma_f32_16x16x32, less energy per FLOP); fp32: conv_v4_kernel
+                "kernel": ("use::conv_v5_kernel<%s> (wide-tile implicit-GEMM 3x3 conv of the large maps on 16x16x32 MFMAs, both ACT variants, five epilogue forms)"
+                           if precision != "fp32" else "use::conv_v4_kernel<%s> (wide-tile implicit-GEMM 3x3 conv of the large maps, both ACT variants)")
+                          % ({"bf16": "bf16,bf16,32", "fp16": "f16,f16,32"}.get(precision, "f32,f32,16")),
+                "measured": "HIP events around every launch of one eager score evaluation with the sub-batches run back to back "
+                            "(one launch on the chip at a time; `rocprofv3 --stats -- python bench.py --roofline-only` agrees); in "
+                            "the timed region the same launches share the chip with the other sub-batch's kernels",
+                "launches_per_score": conv_launches, "avg_launch_ms": round(conv_ms / max(conv_launches, 1), 4),
+                "algorithmic_gflop_per_launch": round(conv_flops / max(conv_launches, 1) / 1e9, 2),
+                "kernel_time_share_of_eager_score": round(conv_ms / total_ms, 3),   # of one un-pipelined evaluation (sub-batches back to back)
+                "whole_path_tflops_per_gpu": round(tflops_path, 1), "whole_path_frac": round(tflops_path / peak, 4),
+                "by_map": [{"map": f"{Hm}x{Wm}", "launches_per_score": len(v), "avg_launch_ms": round(sum(m for _, m in v) / len(v), 4),
+                            "achieved_TFLOPs": round(sum(f for f, _ in v) / (sum(m for _, m in v) * 1e-3) / 1e12, 1),
+                            "frac": round(sum(f for f, _ in v) / (sum(m for _, m in v) * 1e-3) / 1e12 / peak, 4)}
+                           for (Hm, Wm), v in sorted(by_map.items(), key=lambda kv: -kv[0][0] * kv[0][1])],
+                "hbm_peak_TBps": PEAK_HBM_TBPS, "hbm_kernels": hbm_kernels,
+                "kernels": [dict(k, frac=round(k["achieved_TFLOPs"] / peak, 4)) for k in mfma_kernels[:6]]}
+    return roofline
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -174,6 +261,9 @@ def main():
     ap.add_argument("--corrector", default="langevin")
     ap.add_argument("--precision", default="bf16")
     ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the power probe, the roofline of the dominant kernel, "
+                         "the secondary configurations and the CPU baseline (each can be left out with its --no-* option)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--subbatch", type=int, default=None, help="sub-batches per score evaluation (library default if unset)")
     ap.add_argument("--stagger-level", type=int, default=None)
@@ -187,13 +277,13 @@ def main():
     ap.add_argument("--opt", action="append", default=[], help="use_set_option name=value (repeatable; same-box A/B of a tuning knob)")
     ap.add_argument("--roofline-only", action="store_true",
                     help="skip the timed sampler steps; run only the per-launch measurement of the dominant kernel (for "
-                         "`rocprofv3 --kernel-trace --stats -- python bench.py --roofline-only`, see profiles/README.md)")
+                         "`rocprofv3 --kernel-trace --stats -- python bench.py --roofline-only`, see profiles/README.md); implies --full")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one returned (rank 0: the sampled spectrogram, complex64 "
                          "[B,1,F,T'] as float32 [..., 2]) as DIR/enhanced_spec.npy, at most 64 MB; same arguments, same inputs")
     a = ap.parse_args()
     if a.roofline_only:
-        a.steps, a.warmup, a.no_cpu_baseline, a.no_secondary = 0, 0, True, True
+        a.full, a.steps, a.warmup, a.no_cpu_baseline, a.no_secondary = True, 0, 0, True, True
     if a.dump_outputs and a.steps < 1:
         raise SystemExit("--dump-outputs needs at least one timed step")
     if a.config == 3:
@@ -280,7 +370,7 @@ def main():
             stop_probe.wait(0.5)
     pt = None
     torch.cuda.device_count()                                   # (cached before the sampling thread initialises amdsmi: torch's own count goes through amdsmi too)
-    if rank == 0 and not a.no_power_probe and a.steps:
+    if rank == 0 and a.full and not a.no_power_probe and a.steps:
         pt = threading.Thread(target=power_thread, daemon=True); pt.start()
     barrier()
     t0 = time.perf_counter()
@@ -333,90 +423,14 @@ def main():
     padded_frame_nfe_per_s = world * B * Tp * nfe * a.steps / dt
     tflops_path = padded_frame_nfe_per_s * FLOP_PER_FRAME_NFE / 1e12 / world     # per GPU
 
-    # ---- roofline of the dominant kernel, HIP events per launch on the current stream ----
-    x = out
-    tvec = torch.full((B,), 0.5, device=dev)
-    eng.profile_score(x, Y, tvec)                                   # warm
-    conv_ms, conv_flops, conv_bytes, conv_launches, total_ms = eng.profile_score(x, Y, tvec)
-    # the HBM-bound kernels of the same evaluation ("glue kernels individually: HBM-bound"): algorithmic bytes
-    # (every operand once) / duration between HIP events / 8 TB/s, per kernel class and map, averaged over the launches
-    hbm_kernels = []
-    groups = {}
-    mfma_groups = {}
-    by_map = {}
-    for name, Hm, Wm, by, ms, fl in eng.profile_aux(with_flops=True):
-        if name == "conv_v4":                                       # the dominant kernel's own launches, for the per-map breakdown
-            by_map.setdefault((Hm, Wm), []).append((fl, ms))
-            continue
-        if fl > 0:
-            mfma_groups.setdefault((name, Hm, Wm), []).append((fl, ms))
-        else:
-            groups.setdefault((name, Hm, Wm), []).append((by, ms))
-    # the MFMA-bound kernels beside the dominant one, per kernel class and map: algorithmic FLOPs / HIP-event duration / dense peak
-    mfma_kernels = []
-    for (name, Hm, Wm), v in sorted(mfma_groups.items(), key=lambda kv: -sum(m for _, m in kv[1])):
-        fl = sum(f for f, _ in v); ms = sum(m for _, m in v)
-        mfma_kernels.append({"kernel": name, "map": f"{Hm}x{Wm}", "launches_per_score": len(v), "algorithmic_gflop_per_launch": round(fl / len(v) / 1e9, 2),
-                             "avg_launch_ms": round(ms / len(v), 4), "ms_per_score": round(ms, 3),
-                             "achieved_TFLOPs": round(fl / (ms * 1e-3) / 1e12, 1)})
-    for (name, Hm, Wm), v in sorted(groups.items(), key=lambda kv: (-kv[0][1] * kv[0][2], kv[0][0])):
-        if Hm * Wm < 256 * 320:                                     # the smaller maps are hidden behind the other sub-batch's convolutions
-            continue
-        by = sum(b for b, _ in v) / len(v); ms = sum(m for _, m in v) / len(v)
-        # what actually binds the kernel: the fused GroupNorm + SiLU costs two quarter-rate transcendentals per
-        # staged element, which puts the FIR down-sampler (each input evaluated 2.25x) and the pyramid heads above their HBM time
-        binds = {"fir_down": "valu (fused SiLU: v_exp + v_rcp per element, 1.7x redundant in the strip walk)",
-                 "pyr_conv": "tile walk (65 us with SiLU and MFMAs ablated) + valu (fused SiLU, rolling halo 1.125x) on producer waves beside the MFMA waves",
-                 "conv_in": "hbm write (tile walk, per-workgroup GroupNorm partial totals)", "fir_up": "hbm"}.get(name, "hbm")
-        hbm_kernels.append({"kernel": name, "map": f"{Hm}x{Wm}", "launches_per_score": len(v), "algorithmic_bytes": round(by),
-                            "avg_ms": round(ms, 4), "achieved_GBps": round(by / (ms * 1e-3) / 1e9, 1),
-                            "frac": round(by / (ms * 1e-3) / (PEAK_HBM_TBPS * 1e12), 4), "binds": binds})
-    peak = PEAK_FP32_TFLOPS if a.precision == "fp32" else PEAK_BF16_TFLOPS      # bf16 and fp16 MFMA share the dense peak
-    achieved = conv_flops / (conv_ms * 1e-3) / 1e12
-    # HBM traffic per launch comes from rocprofv3 PMC passes (FETCH_SIZE x2 on gfx950 + WRITE_SIZE), which cannot be
-    # collected from inside the timed process: the committed summary of `scripts/profile.sh pmc <tag>` + `scripts/pmc_to_json.py` on this workload is quoted.
-    traffic, traffic_src = None, None
-    if a.precision == "bf16" and (B, Tp) == (8, 640):   # the PMC passes were collected on exactly this workload
-        import glob
-        import hashlib
-        pm = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_conv_v[45].json")), key=lambda f: (int(os.path.basename(f).split("_")[0][1:] or 0), f))
-        if pm:
-            rec = json.load(open(pm[-1]))
-            src = os.path.join(ROOT, rec.get("kernel_source", "universal_speech_enhancement_amd/csrc/use_conv_v4.hip"))
-            cur = hashlib.sha256(open(src, "rb").read()).hexdigest()[:16] if os.path.exists(src) else None
-            if rec.get("kernel_source_sha16") == cur:            # counters of THIS kernel source, else stale: report null
-                traffic = round(rec["hbm_bytes_per_launch"])
-                traffic_src = os.path.relpath(pm[-1], ROOT)
-            else:
-                traffic_src = f"stale ({os.path.relpath(pm[-1], ROOT)} was collected on another version of {rec.get('kernel_source')})"
-    roofline = {"bound": "mfma", "achieved": round(achieved, 1), "peak": peak, "unit": "TFLOP/s",
-                "frac": round(achieved / peak, 4), "traffic": traffic, "traffic_unit": "HBM bytes per launch",
-                "traffic_source": traffic_src,
-                "algorithmic_hbm_bytes_per_launch": round(conv_bytes / max(conv_launches, 1)),
-                # 16-bit storage: conv_v5_kernel (round 6: conv_v4's tile and pipeline on v_mfma_f32_16x16x32, less energy per FLOP); fp32: conv_v4_kernel
-                "kernel": ("use::conv_v5_kernel<%s> (wide-tile implicit-GEMM 3x3 conv of the large maps on 16x16x32 MFMAs, both ACT variants, five epilogue forms)"
-                           if a.precision != "fp32" else "use::conv_v4_kernel<%s> (wide-tile implicit-GEMM 3x3 conv of the large maps, both ACT variants)")
-                          % ({"bf16": "bf16,bf16,32", "fp16": "f16,f16,32"}.get(a.precision, "f32,f32,16")),
-                "measured": "HIP events around every launch of one eager score evaluation with the sub-batches run back to back "
-                            "(one launch on the chip at a time; `rocprofv3 --stats -- python bench.py --roofline-only` agrees); in "
-                            "the timed region the same launches share the chip with the other sub-batch's kernels",
-                "launches_per_score": conv_launches, "avg_launch_ms": round(conv_ms / max(conv_launches, 1), 4),
-                "algorithmic_gflop_per_launch": round(conv_flops / max(conv_launches, 1) / 1e9, 2),
-                "kernel_time_share_of_eager_score": round(conv_ms / total_ms, 3),   # of one un-pipelined evaluation (sub-batches back to back)
-                "whole_path_tflops_per_gpu": round(tflops_path, 1), "whole_path_frac": round(tflops_path / peak, 4),
-                "by_map": [{"map": f"{Hm}x{Wm}", "launches_per_score": len(v), "avg_launch_ms": round(sum(m for _, m in v) / len(v), 4),
-                            "achieved_TFLOPs": round(sum(f for f, _ in v) / (sum(m for _, m in v) * 1e-3) / 1e12, 1),
-                            "frac": round(sum(f for f, _ in v) / (sum(m for _, m in v) * 1e-3) / 1e12 / peak, 4)}
-                           for (Hm, Wm), v in sorted(by_map.items(), key=lambda kv: -kv[0][0] * kv[0][1])],
-                "hbm_peak_TBps": PEAK_HBM_TBPS, "hbm_kernels": hbm_kernels,
-                "kernels": [dict(k, frac=round(k["achieved_TFLOPs"] / peak, 4)) for k in mfma_kernels[:6]]}
+    roofline = measure_roofline(eng, out, Y, a.precision, tflops_path) if a.full else None
 
     # ---- secondary numbers of SURVEY.md section 8d (outside the timed region above; each its own graph capture + timed steps):
     # the predictor-only sampler at the benchmark's N, the reference's STOCK default (model_wrapper.py:39-40, 262-269: N = 50, corrector
     # "none"), and the fp32 parity mode (the mode the north_star tolerance is stated for) on the same workload
     secondary = None
     cfg_is_1 = (B, a.N, ncorr, a.precision, a.seconds) == (8, 30, 1, "bf16", 4.0)
-    if rank == 0 and world == 1 and not a.no_secondary and a.steps:
+    if rank == 0 and world == 1 and a.full and not a.no_secondary and a.steps:
         def timed(engine, N, corr, steps):
             engine.plan(B, Tp)
             engine.set_sampler(N, "reverse_diffusion", corr, 1, 0.5, 3e-2, use_graph=not a.no_graph)
@@ -491,13 +505,14 @@ def main():
             "distinct_devices": len({r["pci_bus_id"] for r in ranks_info}),
             "ms_per_step_min_over_ranks": min(r["ms_per_step"] for r in ranks_info), "ms_per_step_max_over_ranks": max(r["ms_per_step"] for r in ranks_info),
             "ranks": ranks_info,
-            "roofline": roofline,
         }
+        if roofline is not None:
+            res["roofline"] = roofline
         if power_probe is not None:
             res["power_probe"] = power_probe
         if secondary is not None:
             res["secondary"] = secondary
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(sd_np)
         print(json.dumps(res), flush=True)
     if torch.distributed.is_initialized():

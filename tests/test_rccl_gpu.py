@@ -56,10 +56,10 @@ def test_rccl_path_at_world_size_one():
     assert r.returncode == 0 and "RCCL_WORLD1_OK" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
 
 
-def test_bench_under_the_launcher_with_one_process(tmp_path):
+def _bench_under_the_launcher(tmp_path, *extra):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1",
-           "--batch", "2", "--seconds", "1", "--N", "2", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)]
+           "--batch", "2", "--seconds", "1", "--N", "2", "--dump-outputs", str(tmp_path), *extra]
     env = dict(os.environ); env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
@@ -68,6 +68,20 @@ def test_bench_under_the_launcher_with_one_process(tmp_path):
     assert res["n_gpus"] == 1 and res["value"] > 0 and res["config"]["parallelism"] == "utterance-sharded x1"
     out = np.load(tmp_path / "enhanced_spec.npy")         # what the timed step returned: the 2 utterances as float32 (real, imaginary)
     assert out.dtype == np.float32 and out.shape == (2, 1, 512, res["config"]["padded_frames_per_utt"], 2) and np.isfinite(out).all()
+    return res
+
+
+def test_bench_under_the_launcher_with_one_process(tmp_path):
+    res = _bench_under_the_launcher(tmp_path)
+    # a plain run measures the headline figure alone: everything else is behind --full
+    assert not {"roofline", "power_probe", "secondary", "cpu_baseline"} & set(res), sorted(res)
+
+
+def test_bench_full_under_the_launcher_with_one_process(tmp_path):
+    res = _bench_under_the_launcher(tmp_path, "--full", "--no-cpu-baseline")
+    assert res["roofline"]["launches_per_score"] > 0 and res["roofline"]["achieved"] > 0, res["roofline"]
+    assert {"predictor_only", "reference_stock_default", "fp32_parity_mode"} <= set(res["secondary"]), res["secondary"]
+    assert "cpu_baseline" not in res
 
 
 _TRAIN_WORKER = r"""
