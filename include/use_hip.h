@@ -264,7 +264,22 @@ int use_conv_bench(const use_conv_case* c, float* out_host, float* stats_host, d
  * use_op_fir: upsample_2d / downsample_2d with the [1,3,3,1] kernel (up_or_down_sampling.py:202-264); out_act = FIR(act(a x + b)),
  *   out_raw = FIR(x) (either may be null).
  * use_op_attention: softmax(q k^T / sqrt(C)) v per item (AttnBlockpp core, layerspp.py:84-88), q/k/v/out [B][N][C].
- * use_op_gn_finalize: GroupNorm totals (as accumulated in `stats`) of up to two concatenated sources -> coef[b][c] = (a, b). */
+ * use_op_gn_finalize: GroupNorm totals (as accumulated in `stats`) of up to two concatenated sources -> coef[b][c] = (a, b).
+ * use_op_fir and use_op_attention return USE_E_INVALID (nothing is launched) for an unknown dtype, for C that is not a whole number of
+ *   16-byte channel chunks (FIR: C % 8 in 16 bit, C % 4 in fp32) and for a row that does not fit the LDS (attention: (C + N) * 4 bytes).
+ * The remaining kernels of one score evaluation, one launch each on `stream`, argument check in front, no synchronisation:
+ * use_op_attn_block: the fused AttnBlockpp (layerspp.py:77-93) out = (x + NIN_3(softmax(q k^T / sqrt(C)) v)) / sqrt(2), q / k / v =
+ *   NIN_0..2(GroupNorm(x)); x / out [B][N][C] in a 16-bit `dtype`, C = 256, N <= 96 (anything else: USE_E_INVALID); gn_st = the
+ *   fixed-point totals of x ([B][C][2], as `stats` accumulates them); the four NIN matrices are DEVICE tensors in `dtype`, [Cout][Cin]
+ *   (the transpose of the reference's NIN.W), the four biases device fp32; stats (zeroed by the caller, or null) receives the totals of out.
+ * use_op_combine_add: Combine 'sum' of an 8-channel fp32 pyramid (layerspp.py:50-55) in place, h[b,p,:] += b8 + w8 . pyr[b,p,:] with
+ *   w8 [C][8], and the totals of the stored h into stats (zeroed by the caller, required); C <= 512, a multiple of the chunk.
+ * use_op_temb_mlp: t[b * t_stride] -> silu(Linear_2(silu(Linear_1(fourier(log t))))) [B][4 nf] (layerspp.py:37-39, ncsnpp.py:351-368;
+ *   the res-blocks consume act(temb)); use_op_temb_dense: out[b][r] = bias[r] + W[r] . silu_temb[b], every Dense_0 row at once.
+ * use_op_score_out: score[b,p] = sign * (bias + w . pyr[b,p,:] / t[b * t_stride]) as complex64 (ncsnpp.py:492-500; t null: no division;
+ *   pc = 4 or 8 pyramid channels, w [2][pc]).  use_op_pack_input: x4[p] = 2 (x, y[, y2]) - 1 (ncsnpp.py:333-347, 372-374; y null: 0).
+ * use_op_softmax_rows: in place over the last axis of [rows][cols]; use_op_transpose_nc: [B][N][C] -> [B][C][N] (the long-sequence
+ *   attention path's helpers). */
 typedef struct use_conv_op {
     int B, H, W, C0, C1, Cout, XC0, XC1, ntaps, act, dtype, out_dtype, variant;
     const void *src0, *src1;
@@ -301,6 +316,19 @@ int use_op_fir(const void* src, int dtype, const float* coef, int act, void* out
 int use_op_attention(const void* q, const void* k, const void* v, void* out, int dtype, int B, int N, int C, use_stream_t stream);
 int use_op_gn_finalize(const long long* st0, int C0, const long long* st1, int C1, const float* gamma, const float* beta, int groups,
                        int hw, float eps, float* coef, int B, use_stream_t stream);
+int use_op_attn_block(const void* x, const long long* gn_st, const float* gamma, const float* beta, int groups, float eps, const void* wq,
+                      const void* wk, const void* wv, const void* wo, const float* bq, const float* bk, const float* bv, const float* bo,
+                      void* out, long long* stats, int dtype, int B, int N, int C, use_stream_t stream);
+int use_op_combine_add(void* h, int dtype, const float* pyr, const float* w8, const float* b8, long long* stats, int B, int64_t pix_per_b, int C,
+                       use_stream_t stream);
+int use_op_temb_mlp(const float* t, int t_stride, const float* gfp_w, const float* w1, const float* b1, const float* w2, const float* b2,
+                    float* out_silu, int B, int nf, use_stream_t stream);
+int use_op_temb_dense(const float* silu_temb, const float* W, const float* bias, float* out, int B, int rows, int dim, use_stream_t stream);
+int use_op_score_out(const float* pyr, int pc, const float* t, int t_stride, const float* w, const float* bias, void* score, int B,
+                     int64_t pix_per_b, float sign, use_stream_t stream);
+int use_op_pack_input(const void* x, const void* y, const void* y2, float* x4, int64_t npix, use_stream_t stream);
+int use_op_softmax_rows(void* x, int dtype, int64_t rows, int cols, use_stream_t stream);
+int use_op_transpose_nc(const void* in, void* out, int dtype, int B, int N, int C, use_stream_t stream);
 /* ---- backward operators of one res-block (minimum slice of ScoreModel.train_step's gradients, reference
  * model_wrapper.py:147-208 / SGMSE_module.py:46-54).  NHWC device tensors; activations and their gradients in `dtype` (0 fp32 /
  * 1 bf16 / 2 fp16 storage: mixed-precision training keeps fp32 parameters, statistics and parameter gradients) where a dtype

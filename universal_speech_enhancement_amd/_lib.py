@@ -112,6 +112,14 @@ SYMBOLS = {
     "use_op_fir": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "use_op_attention": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "use_op_gn_finalize": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _f, _vp, _i, _vp]),
+    "use_op_attn_block": (_i, [_vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "use_op_combine_add": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i64, _i, _vp]),
+    "use_op_temb_mlp": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "use_op_temb_dense": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "use_op_score_out": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i64, _f, _vp]),
+    "use_op_pack_input": (_i, [_vp, _vp, _vp, _vp, _i64, _vp]),
+    "use_op_softmax_rows": (_i, [_vp, _i, _i64, _i, _vp]),
+    "use_op_transpose_nc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "use_op_wgrad_workspace": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i]),
     "use_op_wgrad": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, C.c_size_t, _vp]),
     "use_op_gn_workspace": (C.c_size_t, [_i, _i, _i]),

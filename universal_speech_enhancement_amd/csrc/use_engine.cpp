@@ -2201,16 +2201,101 @@ int use_op_conv_dev(const use_conv_op* c, int w_mode, void* work, size_t work_by
     HIPCHK(hipGetLastError());
     return USE_OK;
 }
+static bool op_dtype_ok(int dtype) { return dtype == DT_F32 || dtype == DT_BF16 || dtype == DT_F16; }
 int use_op_fir(const void* src, int dtype, const float* coef, int act, void* out_act, void* out_raw, int B, int H, int W, int C, int up,
                use_stream_t stream) {
     if (!src || (!out_act && !out_raw) || B < 1 || H < 1 || W < 1 || C < 1) return fail(USE_E_INVALID, "use_op_fir: bad argument");
+    if (!op_dtype_ok(dtype)) return fail(USE_E_INVALID, "use_op_fir: bad dtype %d", dtype);
+    // a thread owns one 16-byte channel chunk: a remainder would be left unwritten
+    const int vec = dtype == DT_F32 ? 4 : 8;
+    if (C % vec) return fail(USE_E_INVALID, "use_op_fir: C = %d is not a multiple of %d (16-byte channel chunks)", C, vec);
+    if (!up && (H < 2 || W < 2)) return fail(USE_E_INVALID, "use_op_fir: a %d x %d map has no x2 down-sampled output", H, W);
     if (up) launch_fir_up2(src, dtype, coef, act, out_act, out_raw, B, H, W, C, (hipStream_t)stream);
     else    launch_fir_down2(src, dtype, coef, act, out_act, out_raw, B, H, W, C, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
     return USE_OK;
 }
+// dynamic LDS a kernel gets without hipFuncAttributeMaxDynamicSharedMemorySize: 64 KB less the kernel's static LDS
+static const size_t OP_LDS_DEFAULT = 65536;
 int use_op_attention(const void* q, const void* k, const void* v, void* out, int dtype, int B, int N, int C, use_stream_t stream) {
-    if (!q || !k || !v || !out || B < 1 || N < 1 || C < 1) return fail(USE_E_INVALID, "use_op_attention: bad argument");
+    if (!q || !k || !v || !out || B < 1 || B > 65535 || N < 1 || C < 1) return fail(USE_E_INVALID, "use_op_attention: bad argument");
+    if (!op_dtype_ok(dtype)) return fail(USE_E_INVALID, "use_op_attention: bad dtype %d", dtype);
+    // one query row [C] and its scores [N] in LDS (fp32) beside 16 bytes of reduction scratch
+    if ((size_t)(C + N) * 4 + 16 > OP_LDS_DEFAULT)
+        return fail(USE_E_INVALID, "use_op_attention: (C + N) * 4 = %zu bytes of LDS per row, more than a launch gets", (size_t)(C + N) * 4);
     launch_attention(q, k, v, out, dtype, B, N, C, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return USE_OK;
+}
+int use_op_attn_block(const void* x, const long long* gn_st, const float* gamma, const float* beta, int groups, float eps, const void* wq,
+                      const void* wk, const void* wv, const void* wo, const float* bq, const float* bk, const float* bv, const float* bo,
+                      void* out, long long* stats, int dtype, int B, int N, int C, use_stream_t stream) {
+    if (!x || !gn_st || !gamma || !beta || !wq || !wk || !wv || !wo || !bq || !bk || !bv || !bo || !out || B < 1)
+        return fail(USE_E_INVALID, "use_op_attn_block: bad argument");
+    if (!op_dtype_ok(dtype)) return fail(USE_E_INVALID, "use_op_attn_block: bad dtype %d", dtype);
+    if (!attn_fused_eligible(dtype, N, C))
+        return fail(USE_E_INVALID, "use_op_attn_block: the fused block runs 16-bit storage, C = 256 and 1 <= N <= 96 (dtype %d, C %d, N %d)", dtype, C, N);
+    if (groups < 1 || C % groups) return fail(USE_E_INVALID, "use_op_attn_block: %d groups do not divide C = %d", groups, C);
+    AttnArgs a{};
+    a.x = x; a.out = out; a.N = N;
+    a.gn_st = gn_st; a.gn_gamma = gamma; a.gn_beta = beta; a.gn_groups = groups; a.gn_eps = eps;
+    a.wq = wq; a.wk = wk; a.wv = wv; a.wo = wo; a.bq = bq; a.bk = bk; a.bv = bv; a.bo = bo;
+    a.stats = stats;
+    launch_attn_fused(a, dtype, B, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return USE_OK;
+}
+int use_op_combine_add(void* h, int dtype, const float* pyr, const float* w8, const float* b8, long long* stats, int B, int64_t pix_per_b, int C,
+                       use_stream_t stream) {
+    if (!h || !pyr || !w8 || !b8 || !stats || B < 1 || B > 65535 || pix_per_b < 1 || pix_per_b > 64LL * 0x7fffffff)
+        return fail(USE_E_INVALID, "use_op_combine_add: bad argument");
+    if (!op_dtype_ok(dtype)) return fail(USE_E_INVALID, "use_op_combine_add: bad dtype %d", dtype);
+    const int vec = dtype == DT_F32 ? 4 : 8;
+    if (C < vec || C > 512 || C % vec) return fail(USE_E_INVALID, "use_op_combine_add: C = %d is not a multiple of %d up to 512", C, vec);
+    launch_combine_add(h, dtype, pyr, w8, b8, stats, B, (long)pix_per_b, C, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return USE_OK;
+}
+int use_op_temb_mlp(const float* t, int t_stride, const float* gfp_w, const float* w1, const float* b1, const float* w2, const float* b2,
+                    float* out_silu, int B, int nf, use_stream_t stream) {
+    if (!t || !gfp_w || !w1 || !b1 || !w2 || !b2 || !out_silu || B < 1 || nf < 1 || t_stride < 0) return fail(USE_E_INVALID, "use_op_temb_mlp: bad argument");
+    if ((size_t)6 * nf * 4 > OP_LDS_DEFAULT) return fail(USE_E_INVALID, "use_op_temb_mlp: nf = %d needs %zu bytes of LDS, more than a launch gets", nf, (size_t)6 * nf * 4);
+    launch_temb_mlp(t, t_stride, gfp_w, w1, b1, w2, b2, out_silu, B, nf, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return USE_OK;
+}
+int use_op_temb_dense(const float* silu_temb, const float* W, const float* bias, float* out, int B, int rows, int dim, use_stream_t stream) {
+    if (!silu_temb || !W || !bias || !out || B < 1 || B > 65535 || rows < 1 || dim < 1) return fail(USE_E_INVALID, "use_op_temb_dense: bad argument");
+    launch_temb_dense(silu_temb, W, bias, out, B, rows, dim, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return USE_OK;
+}
+int use_op_score_out(const float* pyr, int pc, const float* t, int t_stride, const float* w, const float* bias, void* score, int B,
+                     int64_t pix_per_b, float sign, use_stream_t stream) {
+    if (!pyr || !w || !bias || !score || B < 1 || B > 65535 || pix_per_b < 1 || t_stride < 0) return fail(USE_E_INVALID, "use_op_score_out: bad argument");
+    if (pc != 4 && pc != 8) return fail(USE_E_INVALID, "use_op_score_out: %d pyramid channels (4 or 8)", pc);
+    launch_score_out(pyr, pc, t, t_stride, w, bias, (float2*)score, B, (long)pix_per_b, sign, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return USE_OK;
+}
+int use_op_pack_input(const void* x, const void* y, const void* y2, float* x4, int64_t npix, use_stream_t stream) {
+    if (!x || !x4 || npix < 1 || (y2 && !y)) return fail(USE_E_INVALID, "use_op_pack_input: bad argument");
+    launch_pack_input((const float2*)x, (const float2*)y, (const float2*)y2, x4, (long)npix, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return USE_OK;
+}
+int use_op_softmax_rows(void* x, int dtype, int64_t rows, int cols, use_stream_t stream) {
+    if (!x || rows < 1 || rows > 0x7fffffff || cols < 1) return fail(USE_E_INVALID, "use_op_softmax_rows: bad argument");
+    if (!op_dtype_ok(dtype)) return fail(USE_E_INVALID, "use_op_softmax_rows: bad dtype %d", dtype);
+    launch_softmax_rows(x, dtype, (long)rows, cols, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return USE_OK;
+}
+int use_op_transpose_nc(const void* in, void* out, int dtype, int B, int N, int C, use_stream_t stream) {
+    if (!in || !out || B < 1 || B > 65535 || N < 1 || C < 1 || (C + 31) / 32 > 65535) return fail(USE_E_INVALID, "use_op_transpose_nc: bad argument");
+    if (!op_dtype_ok(dtype)) return fail(USE_E_INVALID, "use_op_transpose_nc: bad dtype %d", dtype);
+    launch_transpose_nc(in, out, dtype, B, N, C, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
     return USE_OK;
 }
 int use_op_gn_finalize(const long long* st0, int C0, const long long* st1, int C1, const float* gamma, const float* beta, int groups,

@@ -1204,69 +1204,6 @@ DEVI void store16_nt(T* p, const float (&v)[N]) {
     *reinterpret_cast<uint4*>(p) = u;
 #endif
 }
-template <typename T, bool UP>
-__global__ __launch_bounds__(256) void fir_kernel(const T* __restrict__ src, const float* __restrict__ coef, int act,
-                                                  T* __restrict__ out_act, T* __restrict__ out_raw, int B, int H,
-                                                  int W, int C) {
-    constexpr int VEC = Vec16<T>::N;
-    constexpr bool ACC = sizeof(T) == 4;
-    const int cv = C / VEC;
-    const int OH = UP ? 2 * H : H / 2, OW = UP ? 2 * W : W / 2;
-    const long total = (long)B * OH * OW * cv;
-    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
-        const int c = (int)(idx % cv) * VEC;
-        long pix = idx / cv;
-        const int ox = (int)(pix % OW); pix /= OW;
-        const int oy = (int)(pix % OH);
-        const int b = (int)(pix / OH);
-        float ca[VEC], cb[VEC];
-        const bool want_act = out_act != nullptr;
-        if (want_act && coef) {
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) { ca[k] = coef[((size_t)b * C + c + k) * 2]; cb[k] = coef[((size_t)b * C + c + k) * 2 + 1]; }
-        }
-        float ar[VEC], aa[VEC];
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) { ar[k] = 0.f; aa[k] = 0.f; }
-        constexpr int NT = UP ? 2 : 4;
-        int ys[NT], xs[NT]; float wy[NT], wx[NT];
-        if (UP) {
-            const int my = oy >> 1, mx = ox >> 1;
-            if (oy & 1) { ys[0] = my; wy[0] = 0.75f; ys[1] = my + 1; wy[1] = 0.25f; }
-            else        { ys[0] = my - 1; wy[0] = 0.25f; ys[1] = my; wy[1] = 0.75f; }
-            if (ox & 1) { xs[0] = mx; wx[0] = 0.75f; xs[1] = mx + 1; wx[1] = 0.25f; }
-            else        { xs[0] = mx - 1; wx[0] = 0.25f; xs[1] = mx; wx[1] = 0.75f; }
-        } else {
-            const float k4[4] = {0.125f, 0.375f, 0.375f, 0.125f};
-#pragma unroll
-            for (int a = 0; a < NT; ++a) { ys[a] = 2 * oy - 1 + a; wy[a] = k4[a]; xs[a] = 2 * ox - 1 + a; wx[a] = k4[a]; }
-        }
-#pragma unroll
-        for (int a = 0; a < NT; ++a) {
-            if (ys[a] < 0 || ys[a] >= H) continue;
-#pragma unroll
-            for (int e = 0; e < NT; ++e) {
-                if (xs[e] < 0 || xs[e] >= W) continue;
-                const float wgt = wy[a] * wx[e];
-                float v[VEC];
-                Vec16<T>::load(src + ((size_t)(b * H + ys[a]) * W + xs[e]) * C + c, v);
-#pragma unroll
-                for (int k = 0; k < VEC; ++k) {
-                    ar[k] = fmaf(wgt, v[k], ar[k]);
-                    if (want_act) {
-                        float u = coef ? fmaf(v[k], ca[k], cb[k]) : v[k];
-                        if (act) u = silu_f<ACC>(u);
-                        aa[k] = fmaf(wgt, u, aa[k]);
-                    }
-                }
-            }
-        }
-        const size_t o = ((size_t)(b * OH + oy) * OW + ox) * C + c;
-        if (out_raw) Vec16<T>::store(out_raw + o, ar);
-        if (want_act) Vec16<T>::store(out_act + o, aa);
-    }
-}
-
 // Up x2, one thread per 2x2 INPUT neighbourhood {m,m+1} x {n,n+1} (8 or 4 channels): it owns the 2x2 output block
 // rows {2m+1, 2m+2} x cols {2n+1, 2n+2}, which depends on exactly those four inputs -> each input is normalised and
 // activated 4x less often than in the output-stationary form (the kernel was VALU-bound on SiLU).
