@@ -344,6 +344,8 @@ int use_op_transpose_nc(const void* in, void* out, int dtype, int B, int N, int 
  * use_op_colsum:     out[b][c] = scale * sum_p x[b,p,c] (fp32 out; the gradient reaching Dense_0's output); work: 128 B C floats of
  *                    scratch (8-byte aligned) for the pixel-sliced kernel, or null (fp32 input only: one workgroup per 64 channels).
  * use_op_dense_bwd:  Dense_0(SiLU(temb)): g [B][Cout] -> dW [Cout][K], db [Cout], dtemb [B][K].
+ * Refusals (USE_E_INVALID, nothing launched): B, K or Cout < 1 in use_op_dense_bwd; B, HW or C < 1 in the two GroupNorm operators
+ * (besides C % groups != 0, an unaligned workspace, and 16-bit tensors with C % 8 != 0 or C / 8 > 256).
  * use_op_attention_bwd: the AttnBlockpp core, out = softmax(q k^T / sqrt(C)) v: dq, dk, dv from dO ([B][N][C] each; work: 2 B N N floats). */
 size_t use_op_wgrad_workspace(int B, int H, int W, int Cout, int Cin, int ntaps, int dtype);
 int use_op_wgrad(const void* dy, const void* x, int dtype, float* dw, float* db, int B, int H, int W, int Cout, int Cin, int ntaps, float alpha,

@@ -2323,7 +2323,8 @@ int use_op_wgrad(const void* dy, const void* x, int dtype, float* dw, float* db,
 size_t use_op_gn_workspace(int B, int C, int groups) { return (B < 1 || C < 1 || groups < 1) ? 0 : gn_workspace_floats(B, C, groups); }
 int use_op_gn_act_bwd(const void* x, const void* dy, int dtype, const float* gamma, const float* beta, int groups, float eps, int act, const void* add,
                       float add_scale, int B, int HW, int C, float* work, int have_stats, void* dx, float* dgamma, float* dbeta, use_stream_t stream) {
-    if (!x || !dy || !gamma || !beta || !work || !dx || !dgamma || !dbeta || groups < 1 || C % groups) return fail(USE_E_INVALID, "use_op_gn_act_bwd: bad argument");
+    if (!x || !dy || !gamma || !beta || !work || !dx || !dgamma || !dbeta || B < 1 || HW < 1 || C < 1 || groups < 1 || C % groups)
+        return fail(USE_E_INVALID, "use_op_gn_act_bwd: bad argument");
     if (dtype != DT_F32 && dtype != DT_BF16 && dtype != DT_F16) return fail(USE_E_INVALID, "use_op_gn_act_bwd: bad dtype");
     if ((uintptr_t)work % 8) return fail(USE_E_INVALID, "use_op_gn_act_bwd: workspace must be 8-byte aligned");
     hipStream_t s = (hipStream_t)stream;
@@ -2339,7 +2340,7 @@ int use_op_gn_act_bwd(const void* x, const void* dy, int dtype, const float* gam
 }
 int use_op_gn_act_fwd(const void* x, int dtype, const float* gamma, const float* beta, int groups, float eps, int act, int B, int HW, int C, float* work,
                       void* y, use_stream_t stream) {
-    if (!x || !gamma || !beta || !work || !y || groups < 1 || C % groups) return fail(USE_E_INVALID, "use_op_gn_act_fwd: bad argument");
+    if (!x || !gamma || !beta || !work || !y || B < 1 || HW < 1 || C < 1 || groups < 1 || C % groups) return fail(USE_E_INVALID, "use_op_gn_act_fwd: bad argument");
     if (dtype != DT_F32 && dtype != DT_BF16 && dtype != DT_F16) return fail(USE_E_INVALID, "use_op_gn_act_fwd: bad dtype");
     if ((uintptr_t)work % 8) return fail(USE_E_INVALID, "use_op_gn_act_fwd: workspace must be 8-byte aligned");
     hipStream_t s = (hipStream_t)stream;
@@ -2370,6 +2371,7 @@ int use_op_attention_bwd(const float* q, const float* k, const float* v, const f
 }
 int use_op_dense_bwd(const float* g, const float* temb, const float* Wd, int B, int K, int Cout, float* dW, float* db, float* dtemb, use_stream_t stream) {
     if (!g || !temb || !Wd || !dW || !db || !dtemb) return fail(USE_E_INVALID, "use_op_dense_bwd: null tensor");
+    if (B < 1 || K < 1 || Cout < 1) return fail(USE_E_INVALID, "use_op_dense_bwd: bad argument (B, K and Cout must be at least 1)");
     launch_dense_bwd(g, temb, Wd, B, K, Cout, dW, db, dtemb, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return USE_OK;
