@@ -215,6 +215,19 @@ int use_stft_fwd(const float* wav, void* Y, int B, int L, int n_fft, int hop, co
 int use_istft_back(const void* X, float* wav, int B, int L, int n_fft, int hop, const float* window, int Tpad, float factor,
                    float exponent, use_stream_t s);
 
+/* Chunked sampling of long recordings (no reference counterpart), handle-free: the frame axis of Y [B,1,F,Tp] (Tp the padded frame
+ * count, a multiple of 64) is cut into n windows of C frames (C a positive multiple of 64) that start hop = C - overlap frames apart,
+ * 0 <= overlap <= C / 2; the windows are the batch of use_plan / use_sample* at (B * n, C) - in groups of any size - and the
+ * enhanced windows are cross-faded back in front of use_istft_back.  use_chunk_count (host only): n = 1 for Tp <= C (nothing to
+ * cut), else ceil((Tp - overlap) / hop); USE_E_INVALID with the offending argument named in use_last_error() otherwise.
+ * use_chunk_split: chunks [B * n,1,F,C], window k of item b in row b * n + k = Y[b, 0, :, k * hop : k * hop + C], zero past Tp.
+ * use_chunk_merge: X [B,1,F,Tp]; the first `overlap` frames of window k >= 1 (j = 0 .. overlap - 1) are a_j * window k +
+ * (1 - a_j) * window k - 1 with a_j = (j + 1) / (overlap + 1), every other frame is a copy from the one window that owns it;
+ * one thread per output element, no atomics: deterministic.  Both are one launch on `s`, no synchronisation. */
+int use_chunk_count(int Tp, int C, int overlap);
+int use_chunk_split(const void* Y, void* chunks, int B, int F, int Tp, int C, int overlap, use_stream_t s);
+int use_chunk_merge(const void* chunks, void* X, int B, int F, int Tp, int C, int overlap, use_stream_t s);
+
 /* Counters of a handle: "graph_captures" (segments of the sampling loop captured so far), "plans_built", "plan_cache_hits", "ode_steps",
  * "ode_rejected", "ode_nfev_max" (of the last use_sample_ode),
  * "plans_parked", "plan_stale" (1: use_set_option was called since use_plan - the evaluation entry points will refuse the plan).  A handle keeps the plans - workspace, state, time-embedding tables, captured graphs - of the most recently used

@@ -18,9 +18,10 @@ from .SGMSE_module import _Base, _write_wav
 class GANModule(_Base):
     def __init__(self, G: torch.nn.Module, D=None, G_optimizer=None, D_optimizer=None, G_scheduler=None, D_scheduler=None,
                  G_criterion=None, D_criterion=None, compile: bool = False, accumulate_grad_batches: int = 1,
-                 rewrite_lr=False, G_lr=None, D_lr=None, wav_subtype: str = "PCM_16"):
+                 rewrite_lr=False, G_lr=None, D_lr=None, wav_subtype: str = "PCM_16", sampler_kwargs=None):
         super().__init__()
         self.G = G
+        self.sampler_kwargs = dict(sampler_kwargs or {})     # optional chunk_frames / chunk_overlap / chunk_batch for long recordings (as SGMSEModule)
         self.wav_subtype = wav_subtype
         self.compile = compile
 
@@ -35,7 +36,7 @@ class GANModule(_Base):
 
     @torch.no_grad()
     def predict_step(self, batch: dict, batch_idx: int = 0) -> dict:
-        batch = self.G(batch)
+        batch = self.G(batch, **self.sampler_kwargs)
         for i, fake in enumerate(batch["fake"]):
             if "audio_path" not in batch:
                 continue

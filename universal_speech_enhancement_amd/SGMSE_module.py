@@ -36,7 +36,7 @@ class SGMSEModule(_Base):
         self.Score = Score
         self.wav_subtype = wav_subtype                       # "PCM_16" = what the reference's sf.write produces; "FLOAT" = float32
         self.optimizer, self.scheduler, self.compile = optimizer, scheduler, compile
-        self.sampler_kwargs = dict(sampler_kwargs or {})     # optional N / corrector_steps / snr overrides, sampler_type="ode" (+ rtol / atol / minibatch)
+        self.sampler_kwargs = dict(sampler_kwargs or {})     # optional N / corrector_steps / snr overrides, sampler_type="ode" (+ rtol / atol / minibatch), chunk_frames (+ chunk_overlap / chunk_batch)
 
     def load_lightning_checkpoint(self, path: str, map_location="cpu"):
         """Loads ``ckpt['state_dict']`` with the reference's key layout (``Score.score_net.all_modules...``)."""

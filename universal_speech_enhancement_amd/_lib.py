@@ -94,6 +94,9 @@ SYMBOLS = {
     "use_spec_back": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_float, C.c_float, _vp]),
     "use_stft_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, C.c_float, C.c_float, _vp]),
     "use_istft_back": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, C.c_float, C.c_float, _vp]),
+    "use_chunk_count": (_i, [_i, _i, _i]),
+    "use_chunk_split": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "use_chunk_merge": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "use_sde_prior": (_i, [_vp, _vp, _vp, _u64, _vp, _i64, _vp]),
     "use_fill_noise": (_i, [_vp, _u64, _i, _vp, _i64, _vp]),
     "use_sde_predictor": (_i, [_vp, _i, _f, _i, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _i64, _vp]),

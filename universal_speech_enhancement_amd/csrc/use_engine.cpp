@@ -1838,6 +1838,43 @@ int use_spec_back(const void* X, void* stft, int B, int F, int T, int Tpad, floa
     return USE_OK;
 }
 
+// ---- chunked sampling: window geometry, device split and cross-fade merge (handle-free; no reference counterpart) -----------
+// n = 1 for Tp <= C (no chunking), else ceil((Tp - overlap) / hop) windows at k * hop, hop = C - overlap; the last may run past Tp
+static int chunk_geometry(int Tp, int C, int overlap, int* n) {
+    if (Tp < 64 || Tp % 64 != 0) return fail(USE_E_INVALID, "Tp=%d: the padded frame count must be a positive multiple of 64", Tp);
+    if (C < 64 || C % 64 != 0) return fail(USE_E_INVALID, "chunk_frames=%d must be a positive multiple of 64", C);
+    if (overlap < 0 || overlap > C / 2) return fail(USE_E_INVALID, "overlap=%d must lie in 0 ... chunk_frames / 2 = %d", overlap, C / 2);
+    const int hop = C - overlap;
+    *n = Tp <= C ? 1 : (Tp - overlap + hop - 1) / hop;
+    return USE_OK;
+}
+int use_chunk_count(int Tp, int C, int overlap) {
+    int n = 0;
+    const int rc = chunk_geometry(Tp, C, overlap, &n);
+    return rc ? rc : n;
+}
+static int chunk_args(const void* a, const void* b, int B, int F, int Tp, int C, int overlap, int* n) {
+    if (!a || !b) return fail(USE_E_INVALID, "null tensor");
+    if (B < 1 || F < 1) return fail(USE_E_INVALID, "B=%d and F=%d must be positive", B, F);
+    const int rc = chunk_geometry(Tp, C, overlap, n); if (rc) return rc;
+    if ((long long)B * *n * F > (1ll << 30)) return fail(USE_E_INVALID, "B * n * F = %lld rows exceed 2^30", (long long)B * *n * F);
+    return USE_OK;
+}
+int use_chunk_split(const void* Y, void* chunks, int B, int F, int Tp, int C, int overlap, use_stream_t s) {
+    int n = 0;
+    const int rc = chunk_args(Y, chunks, B, F, Tp, C, overlap, &n); if (rc) return rc;
+    launch_chunk_split((const float2*)Y, (float2*)chunks, B, F, n, Tp, C, overlap, (hipStream_t)s);
+    HIPCHK(hipGetLastError());
+    return USE_OK;
+}
+int use_chunk_merge(const void* chunks, void* X, int B, int F, int Tp, int C, int overlap, use_stream_t s) {
+    int n = 0;
+    const int rc = chunk_args(chunks, X, B, F, Tp, C, overlap, &n); if (rc) return rc;
+    launch_chunk_merge((const float2*)chunks, (float2*)X, B, F, n, Tp, C, overlap, (hipStream_t)s);
+    HIPCHK(hipGetLastError());
+    return USE_OK;
+}
+
 // ---- device STFT / iSTFT fused with the spectrogram glue (handle-free) -----------------------------------------
 namespace {
 std::mutex g_tw_mutex;

@@ -126,6 +126,11 @@ void launch_fir_down2(const void* src, int dtype, const float* coef, int act, vo
 void launch_spec_map(const float2* in, float2* out, long rows, int Tin, int Tin_stride, int Tout, float pre, float power,
                      float post, hipStream_t s);
 
+// Chunked sampling (use_chunk.hip): [B][F][Tp] <-> [B * n][F][C] windows hop = C - overlap frames apart; split zero-fills past Tp, merge
+// cross-fades the first `overlap` frames of chunk k >= 1 with the tail of chunk k - 1.  The caller has checked the geometry.
+void launch_chunk_split(const float2* Y, float2* chunks, int B, int F, int n, int Tp, int C, int overlap, hipStream_t s);
+void launch_chunk_merge(const float2* chunks, float2* X, int B, int F, int n, int Tp, int C, int overlap, hipStream_t s);
+
 // Device STFT / iSTFT fused with the compression glue (n_fft N even, F = N/2 + 1 bins, centred frames, reflect padding).
 // tw = table of (cos, sin)(2 pi m / N), m < N (launch_twiddle_table); win = analysis / synthesis window [N] (device).
 void launch_twiddle_table(float2* tw, int N, hipStream_t s);

@@ -89,6 +89,39 @@ def istft_decompress(X: torch.Tensor, window: torch.Tensor, n_fft: int, hop: int
     return wav
 
 
+def chunk_split(Y: torch.Tensor, chunk_frames: int, overlap: int) -> torch.Tensor:
+    """The overlapping windows of chunked sampling in one kernel (``use_chunk_split``): complex64 CUDA [B,1,F,T'] -> [B*n,1,F,chunk_frames],
+    window k of item b in row b*n + k, frames beyond T' zero; geometry: ``chunking.chunk_plan`` (``ValueError`` for what it refuses)."""
+    from .chunking import chunk_plan
+    if not Y.is_cuda or Y.dtype != torch.complex64 or Y.dim() != 4 or Y.shape[1] != 1:
+        raise UseHipError("chunk_split needs a complex64 CUDA tensor [B, 1, F, T']")
+    Y = Y.contiguous()
+    B, _, F, Tp = Y.shape
+    plan = chunk_plan(Tp, chunk_frames, overlap)
+    chunks = torch.empty((B * plan.n, 1, F, plan.chunk_frames), dtype=torch.complex64, device=Y.device)
+    check(_lib.lib().use_chunk_split(Y.data_ptr(), chunks.data_ptr(), B, F, Tp, plan.chunk_frames, plan.overlap, _stream_ptr(Y.device)),
+          "use_chunk_split")
+    return chunks
+
+
+def chunk_merge(chunks: torch.Tensor, B: int, Tp: int, chunk_frames: int, overlap: int) -> torch.Tensor:
+    """Its inverse with the cross-fade of ``chunking`` in one kernel (``use_chunk_merge``): complex64 CUDA [B*n,1,F,chunk_frames] ->
+    [B,1,F,T'].  One thread per output element, no atomics: deterministic."""
+    from .chunking import chunk_plan
+    plan = chunk_plan(Tp, chunk_frames, overlap)
+    if not chunks.is_cuda or chunks.dtype != torch.complex64 or chunks.dim() != 4 or chunks.shape[1] != 1:
+        raise UseHipError("chunk_merge needs a complex64 CUDA tensor [B*n, 1, F, chunk_frames]")
+    if int(B) < 1 or chunks.shape[0] != int(B) * plan.n or chunks.shape[3] != plan.chunk_frames:
+        raise ValueError(f"chunks has shape {tuple(chunks.shape)}, expected [{int(B) * plan.n}, 1, F, {plan.chunk_frames}] "
+                         f"(B={B}, {plan.n} windows per item)")
+    chunks = chunks.contiguous()
+    F = chunks.shape[2]
+    X = torch.empty((int(B), 1, F, plan.Tp), dtype=torch.complex64, device=chunks.device)
+    check(_lib.lib().use_chunk_merge(chunks.data_ptr(), X.data_ptr(), int(B), F, plan.Tp, plan.chunk_frames, plan.overlap,
+                                     _stream_ptr(chunks.device)), "use_chunk_merge")
+    return X
+
+
 class HipScoreEngine:
     """One handle per (process, device).  Not re-entrant."""
 

@@ -4,6 +4,8 @@
         data.data_folder=noisy/ data.target_folder=enhanced/ [model.Score.precision=fp32] [model.sampler_kwargs.N=30]
         [model.sampler_kwargs.sampler_type=ode [model.sampler_kwargs.rtol=1e-5 model.sampler_kwargs.atol=1e-5
          model.sampler_kwargs.minibatch=1]]      (the probability-flow ODE sampler: RK45, one step-size controller per utterance)
+        [model.sampler_kwargs.chunk_frames=512 [model.sampler_kwargs.chunk_overlap=64 model.sampler_kwargs.chunk_batch=8]]
+                                                 (long recordings in overlapping windows of 512 frames; also with model=LSGAN)
 
 Hydra and Lightning are not available on the target image, so this is a small stand-in: the same YAML groups
 (``configs/predict.yaml`` -> ``data/``, ``model/``), ``key=value`` / ``group=name`` overrides, ``_target_`` instantiation,

@@ -3,7 +3,8 @@
 score network and the whole reverse-SDE loop in libuse_hip.so.
 
 Additions over the reference (all optional, defaults reproduce stock behaviour): ``precision`` ("bf16" | "fp32"),
-``use_graph``, and ``noise`` / ``seed`` keywords on ``sample`` / ``enhance`` for reproducible runs.  ``sampler_type="ode"`` runs the
+``use_graph``, ``noise`` / ``seed`` keywords on ``sample`` / ``enhance`` for reproducible runs, and ``chunk_frames`` / ``chunk_overlap`` /
+``chunk_batch`` for chunked sampling of long recordings (``sample_spec_chunked``).  ``sampler_type="ode"`` runs the
 probability-flow ODE sampler (RK45 on the device) with the score's conditioning, which the reference's own ODE path does not pass
 (DESIGN.md section 7).
 ``train_step`` returns the loss with its tape once ``score_net.requires_grad_(True)`` was called (fp32 HIP operators forward and
@@ -173,10 +174,66 @@ class ScoreModel(SpectralGlue, nn.Module):
         kwargs = {"eps": self.t_eps, "use_graph": self.use_graph, **kwargs}
         return sampling.get_ode_sampler(sde, self, y=y, minibatch=minibatch, **kwargs)
 
-    def sample(self, batch, sampler_type="pc", N=50, corrector_steps=1, snr=0.5, noise=None, seed=0, **ode_kwargs):
+    def sample_spec_chunked(self, sde_input, conditioning, sampler_type="pc", N=50, corrector_steps=1, snr=0.5, noise=None, seed=0,
+                            chunk_frames=512, chunk_overlap=64, chunk_batch=8, predictor=None, corrector=None, **ode_kwargs):
+        """Chunked sampling at the spectrogram level (no reference counterpart; ``chunking``): ``sde_input`` [B,1,F,T'] and every tensor
+        of ``conditioning`` are cut into n windows of ``chunk_frames`` frames, ``chunk_overlap`` frames shared by neighbours
+        (``use_chunk_split``); the B * n windows run through the un-chunked sampler (``fused_sample`` / ``fused_sample_ode`` for the
+        built-in predictors and correctors) in groups of at most ``chunk_batch`` consecutive windows - the last group may be smaller -
+        and the results are cross-faded into one [B,1,F,T'] spectrogram (``use_chunk_merge``).  One plan and one captured graph per
+        (group size, chunk_frames) serve every file length.  T' <= ``chunk_frames``: one window, i.e. the un-chunked sampler itself.
+
+        Group ``g`` samples with ``seed + g``.  An injected ``noise`` has the sampler's usual layout over all B * n windows
+        ([n_draws, B*n, 1, F, chunk_frames] for "pc", the prior's draw [B*n, 1, F, chunk_frames] for "ode") and is sliced per group.
+        The step size of the Langevin / annealed-Langevin corrector is a mean over the group, as it is over any batch of the
+        un-chunked sampler (``sampling/correctors.py``: norms averaged over the batch): the windows of a group are coupled exactly as
+        the utterances of a batch are, so a window's result depends on ``chunk_batch`` and on its neighbours in the group.  Overlapping
+        frames of neighbouring windows draw independent noise.  ``self.last_nfe``: the NFE of every group."""
+        from ..chunking import chunk_plan, map_chunked
+        predictor = self.predictor if predictor is None else predictor
+        corrector = self.corrector if corrector is None else corrector
+        if sampler_type not in ("pc", "ode"):
+            raise NotImplementedError(f"{sampler_type} is not a valid sampler type!")
+        if sampler_type == "pc" and ode_kwargs:
+            raise TypeError(f"sample(sampler_type='pc') got ODE sampler options {sorted(ode_kwargs)}")
+
+        def run(g, lo, hi, windows):
+            y, cond = windows[0], windows[1:]
+            z = None if noise is None else (noise[:, lo:hi] if noise.dim() == y.dim() + 1 else noise[lo:hi])
+            if sampler_type == "pc":
+                return self.get_pc_sampler(predictor, corrector, y, N=N, corrector_steps=corrector_steps, snr=snr, intermediate=False,
+                                           conditioning=cond, noise=z, seed=seed + g)()
+            return self.get_ode_sampler(y, N=N, conditioning=cond, noise=z, seed=seed + g, **ode_kwargs)()
+
+        inputs = [sde_input] + list(conditioning)
+        plan = chunk_plan(int(sde_input.shape[3]), chunk_frames, chunk_overlap)
+        if plan.n == 1:
+            sample, nfe = run(0, 0, sde_input.shape[0], inputs)
+            self.last_nfe = [nfe]
+            return sample
+        total = sde_input.shape[0] * plan.n
+        if noise is not None and noise.shape[noise.dim() - 4] != total:
+            raise ValueError(f"noise has shape {tuple(noise.shape)}: chunked sampling takes the sampler's layout over all {total} windows "
+                             f"of {plan.chunk_frames} frames ({plan.n} per item)")
+        sample, self.last_nfe = map_chunked(run, inputs, chunk_frames, chunk_overlap, chunk_batch)
+        return sample
+
+    def _chunked(self, Tp, chunk_frames, chunk_overlap, chunk_batch):
+        """True when the call is to be chunked: ``chunk_frames`` given (its arguments are checked either way) and T' above it."""
+        if chunk_frames is None:
+            return False
+        from ..chunking import check_chunk_batch, chunk_plan
+        check_chunk_batch(chunk_batch)
+        return chunk_plan(int(Tp), chunk_frames, chunk_overlap).n > 1
+
+    def sample(self, batch, sampler_type="pc", N=50, corrector_steps=1, snr=0.5, noise=None, seed=0, chunk_frames=None,
+               chunk_overlap=64, chunk_batch=8, **ode_kwargs):
         """Reference :262-329: adds ``batch['enhanced']`` (float32 [B, L]) for condition / sde_input 'noisy'.
         ``sampler_type="ode"``: the probability-flow ODE sampler (``get_ode_sampler``; ``ode_kwargs``: ``rtol``, ``atol``,
-        ``minibatch`` (default 1), ``first_step``, ``max_step``, ``max_nfe``); its NFE is left in ``self.last_nfe``."""
+        ``minibatch`` (default 1), ``first_step``, ``max_step``, ``max_nfe``); its NFE is left in ``self.last_nfe``.
+        ``chunk_frames`` (a multiple of 64; default ``None``: off) samples recordings of more padded frames than that in overlapping
+        windows (``sample_spec_chunked``, which documents ``chunk_overlap``, ``chunk_batch``, the seed rule and the noise layout);
+        shorter ones take the un-chunked path, bit-identically."""
         y = batch["perturbed"]
         T_orig = y.size(1)
         Y = self._spectrogram(y)
@@ -197,6 +254,12 @@ class ScoreModel(SpectralGlue, nn.Module):
             sde_input = Y
         else:
             raise NotImplementedError(f"Don't know the sde input you have wished for: {self.sde_input}")
+        if self._chunked(sde_input.shape[3], chunk_frames, chunk_overlap, chunk_batch):
+            sample = self.sample_spec_chunked(sde_input, score_conditioning, sampler_type=sampler_type, N=N, corrector_steps=corrector_steps,
+                                              snr=snr, noise=noise, seed=seed, chunk_frames=chunk_frames, chunk_overlap=chunk_overlap,
+                                              chunk_batch=chunk_batch, **ode_kwargs)
+            batch["fake_sde_enhanced" if (self.sde_input == "denoised" and Y_denoised is not None) else "enhanced"] = self._waveform(sample, T_orig)
+            return batch
         if sampler_type == "pc":
             if ode_kwargs:
                 raise TypeError(f"sample(sampler_type='pc') got ODE sampler options {sorted(ode_kwargs)}")
@@ -214,9 +277,13 @@ class ScoreModel(SpectralGlue, nn.Module):
 
     @torch.no_grad()
     def enhance(self, y, sampler_type="pc", predictor="reverse_diffusion", corrector="ald", N=50, corrector_steps=1,
-                snr=0.5, timeit=False, return_stft=False, noise=None, seed=0, sr=24000, **kwargs):
+                snr=0.5, timeit=False, return_stft=False, noise=None, seed=0, sr=24000, chunk_frames=None, chunk_overlap=64,
+                chunk_batch=8, **kwargs):
         """One-call enhancement of noisy speech ``y`` [1, L] -- keyword surface of the legacy
-        ``ScoreModel.enhance`` (reference ``sgmse/model.py:351-402``)."""
+        ``ScoreModel.enhance`` (reference ``sgmse/model.py:351-402``).  ``chunk_frames`` / ``chunk_overlap`` / ``chunk_batch``: chunked
+        sampling of a long recording, as for ``sample`` (``sample_spec_chunked``).  As un-chunked, ``kwargs`` are the ODE sampler's options
+        and are ignored for "pc"; with ``timeit`` the NFE of a chunked "pc" run is the int every group took (the step count fixes it),
+        that of a chunked "ode" run a list with one entry per group, each what the un-chunked call returns."""
         import time
         start = time.time()
         T_orig = y.size(1)
@@ -225,7 +292,12 @@ class ScoreModel(SpectralGlue, nn.Module):
         if not y.is_cuda:
             y = y.cuda()
         Y = self._spectrogram(y)
-        if sampler_type == "pc":
+        if self._chunked(Y.shape[3], chunk_frames, chunk_overlap, chunk_batch):
+            sample = self.sample_spec_chunked(Y, [Y], sampler_type=sampler_type, N=N, corrector_steps=corrector_steps, snr=snr, noise=noise,
+                                              seed=seed, chunk_frames=chunk_frames, chunk_overlap=chunk_overlap, chunk_batch=chunk_batch,
+                                              predictor=predictor, corrector=corrector, **(kwargs if sampler_type == "ode" else {}))
+            nfe = self.last_nfe[0] if sampler_type == "pc" else self.last_nfe
+        elif sampler_type == "pc":
             sample, nfe = self.get_pc_sampler(predictor, corrector, Y, N=N, corrector_steps=corrector_steps, snr=snr,
                                               intermediate=False, conditioning=[Y], noise=noise, seed=seed)()
         elif sampler_type == "ode":                                      # legacy model.py:384-385
