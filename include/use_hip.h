@@ -228,6 +228,24 @@ int use_chunk_count(int Tp, int C, int overlap);
 int use_chunk_split(const void* Y, void* chunks, int B, int F, int Tp, int C, int overlap, use_stream_t s);
 int use_chunk_merge(const void* chunks, void* X, int B, int F, int Tp, int C, int overlap, use_stream_t s);
 
+/* Evaluation metrics of an enhanced batch against its clean signals, handle-free (reference sgmse/util/other.py:15-62:
+ * energy_ratios(s_hat, s, n) over si_sdr_components, and lsd(s_hat, s)).  est, clean, noise: float32 DEVICE [B][stride], item b valid for
+ * len_host[b] samples (HOST ints; the rest of a row - the batch's zero padding, or anything else - is never read); noise = noisy - clean,
+ * formed by the caller.  out_dev: fp64 DEVICE [B][USE_METRIC_COUNT].  SI-SDR / SI-SIR / SI-SAR = 10 log10(eps + |s_t|^2 / (eps + |e_n +
+ * e_a|^2, |e_n|^2, |e_a|^2)) with s_t = alpha_s s, e_n = alpha_n n, e_a = s_hat - s_t - e_n, in two passes and fp64, as the reference
+ * computes them; LSD = sqrt(mean |2 log(eps + |S_hat|) - 2 log(eps + |S|)|) over the 256 bins x (1 + len / 128) frames of the STFT with
+ * n_fft 510, hop 128, periodic Hann, centred, reflect padding - the reference's sqrt(mean(abs(.))), not the textbook distance -
+ * evaluated in fp64.  eps = 1e-10.  noise == NULL: LSD alone, the three ratios are NaN.  Every sum has a fixed order that depends on
+ * len[b] alone: an item's four values are the same bits in any batch, at any stride, in every run (no atomics).
+ * work: use_metrics_workspace(B, stride) bytes of device scratch, 8-byte aligned (0: bad arguments).  A handful of launches on `s`,
+ * no synchronisation, no allocation.  USE_E_INVALID (argument named in use_last_error(), nothing launched): B < 1 or > 65535, stride < 1,
+ * a null est / clean / len_host / work / out_dev, len[b] < 256 (reflect padding needs len > n_fft / 2 = 255) or > stride, work_bytes
+ * too small. */
+enum { USE_METRIC_SI_SDR = 0, USE_METRIC_SI_SIR = 1, USE_METRIC_SI_SAR = 2, USE_METRIC_LSD = 3, USE_METRIC_COUNT = 4 };
+size_t use_metrics_workspace(int B, int stride);
+int use_metrics(const float* est, const float* clean, const float* noise, const int* len_host, int B, int stride, void* work,
+                size_t work_bytes, double* out_dev, use_stream_t s);
+
 /* Counters of a handle: "graph_captures" (segments of the sampling loop captured so far), "plans_built", "plan_cache_hits", "ode_steps",
  * "ode_rejected", "ode_nfev_max" (of the last use_sample_ode),
  * "plans_parked", "plan_stale" (1: use_set_option was called since use_plan - the evaluation entry points will refuse the plan).  A handle keeps the plans - workspace, state, time-embedding tables, captured graphs - of the most recently used

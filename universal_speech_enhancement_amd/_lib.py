@@ -97,6 +97,8 @@ SYMBOLS = {
     "use_chunk_count": (_i, [_i, _i, _i]),
     "use_chunk_split": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "use_chunk_merge": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "use_metrics_workspace": (C.c_size_t, [_i, _i]),
+    "use_metrics": (_i, [_vp, _vp, _vp, C.POINTER(_i), _i, _i, _vp, C.c_size_t, _vp, _vp]),
     "use_sde_prior": (_i, [_vp, _vp, _vp, _u64, _vp, _i64, _vp]),
     "use_fill_noise": (_i, [_vp, _u64, _i, _vp, _i64, _vp]),
     "use_sde_predictor": (_i, [_vp, _i, _f, _i, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _i64, _vp]),

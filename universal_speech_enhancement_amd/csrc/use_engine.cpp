@@ -1875,6 +1875,32 @@ int use_chunk_merge(const void* chunks, void* X, int B, int F, int Tp, int C, in
     return USE_OK;
 }
 
+// ---- evaluation metrics: SI-SDR / SI-SIR / SI-SAR and LSD per item (handle-free; reference sgmse/util/other.py:15-62) -----------
+size_t use_metrics_workspace(int B, int stride) {
+    if (B < 1 || B > 65535 || stride < 1) return 0;
+    return metrics_layout(B, stride).bytes;
+}
+int use_metrics(const float* est, const float* clean, const float* noise, const int* len_host, int B, int stride, void* work,
+                size_t work_bytes, double* out_dev, use_stream_t s) {
+    if (B < 1 || B > 65535) return fail(USE_E_INVALID, "B=%d must lie in 1 ... 65535", B);
+    if (stride < 1) return fail(USE_E_INVALID, "stride=%d must be positive", stride);
+    if (!est) return fail(USE_E_INVALID, "est is null");
+    if (!clean) return fail(USE_E_INVALID, "clean is null");
+    if (!len_host) return fail(USE_E_INVALID, "len_host is null");
+    if (!work) return fail(USE_E_INVALID, "work is null");
+    if (!out_dev) return fail(USE_E_INVALID, "out_dev is null");
+    for (int b = 0; b < B; ++b)
+        if (len_host[b] < 256 || len_host[b] > stride)
+            return fail(USE_E_INVALID, "len[%d]=%d must lie in 256 ... stride = %d (reflect padding of the 510-point STFT needs more than 255 samples)",
+                        b, len_host[b], stride);
+    const size_t need = metrics_layout(B, stride).bytes;
+    if (work_bytes < need) return fail(USE_E_INVALID, "work_bytes=%zu is smaller than use_metrics_workspace(%d, %d) = %zu", work_bytes, B, stride, need);
+    if ((uintptr_t)work & 7) return fail(USE_E_INVALID, "work must be 8-byte aligned");
+    launch_metrics(est, clean, noise, len_host, B, stride, work, out_dev, (hipStream_t)s);
+    HIPCHK(hipGetLastError());
+    return USE_OK;
+}
+
 // ---- device STFT / iSTFT fused with the spectrogram glue (handle-free) -----------------------------------------
 namespace {
 std::mutex g_tw_mutex;

@@ -131,6 +131,16 @@ void launch_spec_map(const float2* in, float2* out, long rows, int Tin, int Tin_
 void launch_chunk_split(const float2* Y, float2* chunks, int B, int F, int n, int Tp, int C, int overlap, hipStream_t s);
 void launch_chunk_merge(const float2* chunks, float2* X, int B, int F, int n, int Tp, int C, int overlap, hipStream_t s);
 
+// Evaluation metrics (use_metrics.hip): SI-SDR / SI-SIR / SI-SAR and the reference's LSD per item of est / clean / noise [B][stride]
+// (float32 device, noise nullable: ratios NaN) with HOST lengths 256 <= len[b] <= stride; out [B][4] fp64 (device).  `work`:
+// metrics_layout(B, stride).bytes of 8-byte aligned scratch.  Six launches on `s` (+ one per 64 items for the lengths), no
+// synchronisation, no atomics.  The caller has checked the arguments (B <= 65535).
+constexpr int METRICS_SLICE = 2048;                        // samples per workgroup of the two streaming passes
+struct MetricsWork { size_t part1, part2, alpha, lsd, bytes; int nblk, Tmax; };    // byte offsets behind the int lens[B]
+MetricsWork metrics_layout(int B, int stride);
+void launch_metrics(const float* est, const float* clean, const float* noise, const int* len_host, int B, int stride, void* work,
+                    double* out, hipStream_t s);
+
 // Device STFT / iSTFT fused with the compression glue (n_fft N even, F = N/2 + 1 bins, centred frames, reflect padding).
 // tw = table of (cos, sin)(2 pi m / N), m < N (launch_twiddle_table); win = analysis / synthesis window [N] (device).
 void launch_twiddle_table(float2* tw, int N, hipStream_t s);

@@ -1,0 +1,118 @@
+"""Evaluation metrics on the device (``use_metrics``, csrc/use_metrics.hip): the reference's ``energy_ratios`` (SI-SDR, SI-SIR, SI-SAR
+over ``si_sdr_components``) and ``lsd`` of ``sgmse/util/other.py:15-62``, per item of a batch, in fp64, without a copy of the
+waveforms to the host.
+
+All functions take float32 CUDA tensors, 1-D (one signal) or ``[B, L]`` (a zero-padded batch), and ``lengths`` (``None``: the full
+width; else ``B`` ints, ``256 <= lengths[b] <= L``): samples past an item's length are never read.  Results are float64 CUDA tensors
+``[B]``.  There is no CPU implementation.
+
+``score_files`` / ``write_csv`` are the file-level step of ``predict ... data.clean_folder=DIR``."""
+from __future__ import annotations
+
+import csv
+import ctypes as C
+import os
+from typing import Dict, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import UseHipError, check
+
+NAMES = ("si_sdr", "si_sir", "si_sar", "lsd")              # USE_METRIC_SI_SDR ... USE_METRIC_LSD
+MIN_LENGTH = 256                                           # reflect padding of the 510-point STFT needs more than 255 samples
+
+
+def _signals(named) -> Tuple[list, int, int]:
+    out, shape = [], None
+    for name, t in named:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise UseHipError(f"{name} must be a CUDA (ROCm) tensor: the metrics have no CPU implementation")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name} must be float32, got {t.dtype}")
+        if t.dim() == 1:
+            t = t.unsqueeze(0)
+        if t.dim() != 2:
+            raise ValueError(f"{name} must be 1-D or [B, L], got shape {tuple(t.shape)}")
+        shape = shape or tuple(t.shape)
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {shape}")
+        out.append(t.contiguous())
+    return out, shape[0], shape[1]
+
+
+def _lengths(lengths, B: int, L: int):
+    lens = np.full(B, L, np.int32) if lengths is None else np.asarray(torch.as_tensor(lengths).cpu(), dtype=np.int64).reshape(-1)
+    if lens.shape[0] != B:
+        raise ValueError(f"lengths has {lens.shape[0]} entries for a batch of {B}")
+    if (lens < MIN_LENGTH).any() or (lens > L).any():
+        raise ValueError(f"lengths={lens.tolist()} must lie in {MIN_LENGTH} ... {L} (the width of the batch)")
+    return np.ascontiguousarray(lens, dtype=np.int32)
+
+
+def _run(est: torch.Tensor, clean: torch.Tensor, noise: Optional[torch.Tensor], lengths) -> torch.Tensor:
+    """-> float64 CUDA [B, 4] in the order of ``NAMES``; ``noise=None``: the three ratios are NaN."""
+    sig, B, L = _signals([("s_hat", est), ("s", clean)] + ([("n", noise)] if noise is not None else []))
+    lens = _lengths(lengths, B, L)
+    lib = _lib.lib()
+    dev = sig[0].device
+    nbytes = lib.use_metrics_workspace(B, L)
+    if not nbytes:
+        raise ValueError(f"use_metrics_workspace refuses B={B}, L={L}")
+    work = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+    out = torch.empty((B, len(NAMES)), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.use_metrics(sig[0].data_ptr(), sig[1].data_ptr(), sig[2].data_ptr() if noise is not None else None,
+                              lens.ctypes.data_as(C.POINTER(C.c_int)), B, L, work.data_ptr(), nbytes, out.data_ptr(),
+                              torch.cuda.current_stream(dev).cuda_stream), "use_metrics")
+    return out
+
+
+def energy_ratios(s_hat: torch.Tensor, s: torch.Tensor, n: torch.Tensor, lengths=None):
+    """``(si_sdr, si_sir, si_sar)`` in dB, the reference's ``energy_ratios(s_hat, s, n)`` per item."""
+    out = _run(s_hat, s, n, lengths)
+    return out[:, 0], out[:, 1], out[:, 2]
+
+
+def lsd(s_hat: torch.Tensor, s: torch.Tensor, lengths=None) -> torch.Tensor:
+    """The reference's ``lsd(s_hat, s)`` per item: ``sqrt(mean |2 log(eps + |S_hat|) - 2 log(eps + |S|)|)`` at n_fft 510, hop 128."""
+    return _run(s_hat, s, None, lengths)[:, 3]
+
+
+def evaluate(est: torch.Tensor, clean: torch.Tensor, noisy: torch.Tensor, lengths=None) -> Dict[str, torch.Tensor]:
+    """All four metrics of ``est`` against ``clean``; the noise is ``noisy - clean``.  -> ``{name: float64 [B]}``, names ``NAMES``."""
+    sig, _, _ = _signals([("est", est), ("clean", clean), ("noisy", noisy)])
+    out = _run(sig[0], sig[1], sig[2] - sig[1], lengths)
+    return {name: out[:, i] for i, name in enumerate(NAMES)}
+
+
+def score_files(enhanced_path: str, clean_path: str, noisy_path: str, sampling_rate: int = 24000, normalize: bool = True,
+                device="cuda") -> Dict[str, float]:
+    """One row of ``metrics.csv``: the written enhanced file (its samples as they are in the file) against the clean file, with the
+    noisy input as the noise source; clean and noisy through the inference loader (``wavio.load_utterance``: first channel,
+    resampled to ``sampling_rate``, peak-normalised when ``normalize``).  Files of different lengths are scored over the shortest,
+    as the reference's ``si_sdr_torch`` does (``other.py:111-113``)."""
+    from .wavio import load_utterance, read_wav
+    est, _ = read_wav(enhanced_path)
+    est = (est if est.ndim == 1 else est[:, 0]).astype(np.float32)
+    clean, _ = load_utterance(clean_path, sampling_rate, normalize)
+    noisy, _ = load_utterance(noisy_path, sampling_rate, normalize)
+    n = min(len(est), len(clean), len(noisy))
+    if n < MIN_LENGTH:
+        raise ValueError(f"{enhanced_path}: {n} common samples, the metrics need at least {MIN_LENGTH}")
+    t = [torch.from_numpy(np.ascontiguousarray(a[:n])).to(device) for a in (est, clean, noisy)]
+    return {k: float(v[0]) for k, v in evaluate(*t).items()}
+
+
+def write_csv(path: str, rows: Sequence[Tuple[str, Dict[str, float]]]) -> None:
+    """``file, si_sdr, si_sir, si_sar, lsd``: one row per file and a last row ``mean``; values with 17 significant digits (they
+    read back as the same float64)."""
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(("file",) + NAMES)
+        for name, r in rows:
+            w.writerow([name] + [repr(float(r[k])) for k in NAMES])
+        if rows:
+            w.writerow(["mean"] + [repr(float(np.mean([r[k] for _, r in rows]))) for k in NAMES])

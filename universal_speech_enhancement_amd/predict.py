@@ -6,6 +6,8 @@
          model.sampler_kwargs.minibatch=1]]      (the probability-flow ODE sampler: RK45, one step-size controller per utterance)
         [model.sampler_kwargs.chunk_frames=512 [model.sampler_kwargs.chunk_overlap=64 model.sampler_kwargs.chunk_batch=8]]
                                                  (long recordings in overlapping windows of 512 frames; also with model=LSGAN)
+        [data.clean_folder=clean/]               (score every enhanced file whose clean counterpart exists under clean/ at the same
+                                                  relative path: SI-SDR / SI-SIR / SI-SAR / LSD on the device -> enhanced/metrics.csv)
 
 Hydra and Lightning are not available on the target image, so this is a small stand-in: the same YAML groups
 (``configs/predict.yaml`` -> ``data/``, ``model/``), ``key=value`` / ``group=name`` overrides, ``_target_`` instantiation,
@@ -86,6 +88,21 @@ def instantiate(node, **extra):
     return node
 
 
+def _score_batch(batch: dict, clean_folder: str, data_cfg: dict, device):
+    """``data.clean_folder``: (relative path, metrics) of every file of the batch whose clean counterpart exists - the enhanced file as
+    ``predict_step`` wrote it against the clean file, the noisy input as the noise source (``metrics.score_files``)."""
+    from .metrics import score_files
+    rows = []
+    for noisy_path in batch["audio_path"]:
+        rel = os.path.relpath(noisy_path, batch["data_folder"])
+        clean_path = os.path.join(clean_folder, rel)
+        if os.path.isfile(clean_path):
+            enhanced_path = noisy_path.replace(batch["data_folder"], batch["target_folder"])
+            rows.append((rel, score_files(enhanced_path, clean_path, noisy_path, int(data_cfg.get("sampling_rate", 24000) or 0),
+                                          bool(data_cfg.get("normalize", True)), device)))
+    return rows
+
+
 def predict(cfg: dict):
     rank, world, local = D.init_from_env()
     torch.cuda.set_device(local)
@@ -105,10 +122,17 @@ def predict(cfg: dict):
     else:
         raise SystemExit("ckpt_path is required (or random_init_seed=<int> for a dry run)")
     n = 0
+    clean_folder = cfg["data"].get("clean_folder")           # off by default: nothing below runs, no CSV is written
+    rows = []
     with torch.no_grad():
         for i, batch in enumerate(data.predict_batches(device=torch.device("cuda", local))):
             model.predict_step(batch, i)
             n += len(batch["name"])
+            if clean_folder:
+                rows += _score_batch(batch, clean_folder, cfg["data"], torch.device("cuda", local))
+    if clean_folder:
+        from .metrics import write_csv
+        write_csv(os.path.join(cfg["data"]["target_folder"], "metrics.csv" if world == 1 else f"metrics_rank{rank}.csv"), rows)
     print(f"[rank {rank}] enhanced {n} file(s) -> {cfg['data']['target_folder']}")
     return n
 
