@@ -130,6 +130,23 @@ int use_sample_cond(use_handle* h, const void* y, const void* cond, const void* 
 int use_sample_cond2(use_handle* h, const void* y, const void* cond, const void* cond2, const void* noise, uint64_t seed, void* out,
                      use_stream_t stream);
 
+/* The batch-invariant form of the same loop (the sampler of use_set_sampler; plan, cond / cond2 rules and error codes of
+ * use_sample_cond2).  Two differences from use_sample*: item b draws from its own Philox stream, z[b][j] = Philox(seeds_host[b],
+ * draw, j) with j the element index INSIDE the item's F*T' complex elements - the stream use_sample gives a one-item batch with
+ * seed = seeds_host[b], draws numbered alike - and the Langevin step size is the item's own, eps_b = 2 (snr ||z_b|| / ||g_b||)^2
+ * (correctors.py:55-57 at batch size 1; no guard for a zero gradient norm, as there).  ALD and no corrector are per item anyway.
+ * At equal padded frame count T', an item's result then depends on its y, its conditioning, its seed and the sampler alone: not
+ * on its position in the batch, its companions, B, the sub-batch split, or graph versus eager.  Zero padding to another T'
+ * changes what the network sees, so batches padded to different lengths are outside the guarantee.  At B > 1 this reproduces the
+ * reference run per file (batch size 1), not the reference at batch size B.  (For this the per-item loop also makes the one
+ * batch-size-dependent kernel choice of the network, conv_sk's tile form, from the per-image shape - DESIGN.md section 1.)
+ * noise != NULL: injected draws in use_sample's layout (per item already).  Otherwise seeds_host: HOST array of B seeds, copied to
+ * a device array of the plan before the call returns and read there by the kernels, so captured graphs replay with new seeds.
+ * Both NULL: USE_E_INVALID.  The per-item loop has its own captured graphs beside those of use_sample*; neither form drops the
+ * other's, and "graph_captures" counts both. */
+int use_sample_items(use_handle* h, const void* y, const void* cond, const void* cond2, const void* noise,
+                     const uint64_t* seeds_host /* [B] */, void* out, use_stream_t stream);
+
 /* Probability-flow ODE sampler (reference sampling/__init__.py:76-159 get_ode_sampler; model_wrapper.py:238-260): the ODE
  * dx = [theta (y - x) - g(t)^2 score / 2] dt integrated from T = 1 down to t_eps by scipy's RK45 (Dormand-Prince 5(4), scipy 1.15
  * rk.py / common.py, reproduced on the device), then, with `denoise`, one noise-free reverse-diffusion step at t_eps with dt = 1/N.
@@ -190,6 +207,11 @@ int use_sde_corrector(use_handle* h, int corrector, float t, float snr, int B, c
  * consumption.  use_sample(noise = [use_fill_noise(seed, d) for d in 0..use_num_noise_draws-1]) is bit-identical to
  * use_sample(noise = NULL, seed): this is how the timed (device-noise) branch is pinned to the oracle in tests/. */
 int use_fill_noise(use_handle* h, uint64_t seed, int draw, void* out, int64_t n, use_stream_t s);
+
+/* The noise of use_sample_items, draw by draw: out (complex64, n elements = B items of n / B) = item b's z from seeds_host[b]
+ * (HOST array, B <= 1024).  Item b equals use_fill_noise(seeds_host[b], draw) over n / B elements.  Needs no plan. */
+int use_fill_noise_items(use_handle* h, const uint64_t* seeds_host /* [B] */, int B, int draw, void* out,
+                         int64_t n /* complex elements, a multiple of B */, use_stream_t s);
 
 /* Raw backbone output NCSNpp.forward(cat[x, y], t) (ncsnpp.py:324-501), i.e. without the sign flip of use_score.
  * x, y: complex64 [B,1,F,T'] device; y must be null when input_channels == 2 (the input is x alone), t must be null when

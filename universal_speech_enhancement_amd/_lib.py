@@ -75,6 +75,7 @@ SYMBOLS = {
     "use_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "use_score2": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "use_sample_cond2": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp]),
+    "use_sample_items": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_u64), _vp, _vp]),
     "use_set_sampler": (_i, [_vp, C.POINTER(UseSamplerConfig)]),
     "use_num_noise_draws": (_i, [_vp]),
     "use_get_timesteps": (_i, [_vp, C.POINTER(_f), _i]),
@@ -101,6 +102,7 @@ SYMBOLS = {
     "use_metrics": (_i, [_vp, _vp, _vp, C.POINTER(_i), _i, _i, _vp, C.c_size_t, _vp, _vp]),
     "use_sde_prior": (_i, [_vp, _vp, _vp, _u64, _vp, _i64, _vp]),
     "use_fill_noise": (_i, [_vp, _u64, _i, _vp, _i64, _vp]),
+    "use_fill_noise_items": (_i, [_vp, C.POINTER(_u64), _i, _i, _vp, _i64, _vp]),
     "use_sde_predictor": (_i, [_vp, _i, _f, _i, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _i64, _vp]),
     "use_sde_corrector": (_i, [_vp, _i, _f, _f, _i, _vp, _vp, _vp, _u64, _vp, _vp, _i64, _vp]),
     "use_debug_tensor": (_i, [_vp, C.c_char_p, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i)]),

@@ -374,6 +374,9 @@ void sk_launch(const ConvArgs& a, int th, int tw, hipStream_t s) {
 
 void conv_sk_set_max_px(long n) { g_sk_max_px = n; }
 
+static thread_local bool t_sk_per_image = false;
+void conv_sk_set_per_image(bool on) { t_sk_per_image = on; }
+
 bool conv_sk_eligible(const ConvArgs& a) {
     const int Ctot = a.C0 + a.C1, XC = a.XC0 + a.XC1;
     // outputs: full 32-channel tiles in the input's type, or the 4- / 8-channel fp32 pyramid heads (weight rows padded to 32)
@@ -388,7 +391,7 @@ bool conv_sk_eligible(const ConvArgs& a) {
 void launch_conv_sk(const ConvArgs& a, hipStream_t s) {
     int th, tw;
     sk_tile(a.H, a.W, a.ntaps == 9 ? 1 : 0, &th, &tw);
-    const long tiles = (long)((a.H + th - 1) / th) * ((a.W + tw - 1) / tw) * a.B;
+    const long tiles = (long)((a.H + th - 1) / th) * ((a.W + tw - 1) / tw) * (t_sk_per_image ? 1 : a.B);
     // 64-channel tiles once 32-channel ones would give more than two workgroups per CU (the halo staging is repeated per channel tile)
     const bool wide = a.Cout % 64 == 0 && tiles * (a.Cout / 32) > 512;
     if (a.in_dtype != a.out_dtype) {                             // pyramid heads of the 16-bit modes: fp32 out

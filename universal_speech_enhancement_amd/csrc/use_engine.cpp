@@ -140,6 +140,8 @@ struct use_handle {
     float2 *Cond = nullptr;                      // score conditioning of the sampler: == Y unless use_sample_cond gave another
     float *lang_partial = nullptr, *lang_step = nullptr;
     unsigned long long* rng_state = nullptr;
+    unsigned long long* item_seeds = nullptr;    // [B] per-item Philox seeds of use_sample_items (read by the kernels: graphs replay with new seeds)
+    float* item_step = nullptr;                  // [B] per-item Langevin steps
     int lang_blocks = 0;
     // sampler
     use_sampler_config sc{};
@@ -157,7 +159,7 @@ struct use_handle {
     hipEvent_t ev_fork = nullptr, ev_stagger[MAX_SUB] = {},
                ev_join[MAX_SUB] = {};
     int debug_B = 0;
-    std::vector<hipGraphExec_t> graph_exec[2];           // [0]: device RNG, [1]: injected noise; one graph per segment of steps
+    std::vector<hipGraphExec_t> graph_exec[4];           // [0]: device RNG, [1]: injected noise, [2], [3]: the same of the per-item loop; one graph per segment of steps
     hipGraphExec_t score_graph = nullptr;
     // probability-flow ODE sampler (use_set_ode / use_sample_ode): the configuration belongs to the plan, the stepper's buffers and the
     // captured step graph to the handle (re-made when the shape, the stepper or a pointer the graph holds changes)
@@ -175,7 +177,7 @@ struct use_handle {
     long long opt_gen_at_plan = -1;              // g_opt_gen when the current plan was built
     long long n_graph_captures = 0, n_plans_built = 0, n_plan_cache_hits = 0;
     // scratch for the stand-alone use_sde_* entry points (independent of weights / plan)
-    char* sde_buf = nullptr; unsigned long long* sde_rng = nullptr; float* sde_step = nullptr; float* sde_partial = nullptr;
+    char* sde_buf = nullptr; unsigned long long* sde_rng = nullptr; float* sde_step = nullptr; float* sde_partial = nullptr; unsigned long long* sde_seeds = nullptr;
     static constexpr int SDE_MAX_B = 1024, SDE_BLOCKS = 128;
     // per-launch HIP-event profiling of the dominant conv kernel (use_profile_score)
     bool profile = false, profile_all = false; std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events; std::vector<double> prof_flops, prof_bytes; std::vector<char> prof_main; std::vector<std::pair<int, int>> prof_hw;
@@ -828,21 +830,36 @@ static void predictor_coeffs(const use_config& c, int predictor, float t, int N,
 __global__ void set_rng_kernel(unsigned long long* st, unsigned long long seed, unsigned long long base) { st[0] = seed; st[1] = base; }
 __global__ void fill_f32_kernel(float* p, float v, int n) { for (int i = threadIdx.x; i < n; i += blockDim.x) p[i] = v; }
 
-// steps [i0, i1) of the loop (i0 == 0: preceded by the prior sampling); the whole loop is run_sampler(h, noise, s, 0, N)
-static void run_sampler(use_handle* h, const float2* noise, hipStream_t s, int i0, int i1) {
+// steps [i0, i1) of the loop (i0 == 0: preceded by the prior sampling); the whole loop is run_sampler(h, noise, s, 0, N).
+// per_item: the SDE updates in their per-item forms (use_sample_items) - item b's noise from h->item_seeds[b], its own
+// Langevin step; the score evaluations and the stream schedule are the same.
+static void run_sampler(use_handle* h, const float2* noise, hipStream_t s, int i0, int i1, bool per_item = false) {
     const use_sampler_config& sc = h->sc;
     const long n = (long)h->B * h->cfg.n_freq * h->T, n_per_b = (long)h->cfg.n_freq * h->T;
     const int ncorr = sc.corrector == USE_CORR_NONE ? 0 : sc.corrector_steps;
+    // the network's kernel choice must not see the (sub-)batch size either: an item of a sub-batch of 3 has to get the bits it gets alone
+    struct PerImage { bool on; PerImage(bool o) : on(o) { if (on) conv_sk_set_per_image(true); } ~PerImage() { if (on) conv_sk_set_per_image(false); } } per_image(per_item);
     auto nz = [&](unsigned d) { return noise ? noise + (size_t)d * n : nullptr; };
     unsigned d = 1 + (unsigned)i0 * (unsigned)(ncorr + (sc.predictor == USE_PRED_NONE ? 0 : 1));   // noise draws consumed so far
-    if (i0 == 0) launch_prior(h->Y, nz(0), RngRef{h->rng_state, 0}, ouve_std(h->cfg, 1.0f), h->X, n, s);
+    if (i0 == 0) {
+        if (per_item) launch_prior_items(h->Y, nz(0), ItemRng{h->item_seeds, 0}, ouve_std(h->cfg, 1.0f), h->X, h->B, n_per_b, s);
+        else launch_prior(h->Y, nz(0), RngRef{h->rng_state, 0}, ouve_std(h->cfg, 1.0f), h->X, n, s);
+    }
     for (int i = i0; i < i1; ++i) {
         const float t = h->timesteps[i];
         const float* temb = h->temb_table + (size_t)i * h->dense_rows;
         for (int k = 0; k < ncorr; ++k) {
             run_score(h, h->X, h->Cond, temb, 0, h->ts_dev + i, 0, h->score, s, -1.f, h->pcp == 8 ? h->cond2_buf : nullptr);
             RngRef rr{h->rng_state, d};
-            if (sc.corrector == USE_CORR_LANGEVIN) {
+            ItemRng ir{h->item_seeds, d};
+            if (per_item && sc.corrector == USE_CORR_LANGEVIN) {
+                launch_langevin_norms_items(h->score, nz(d), ir, h->lang_partial, h->B, n_per_b, h->lang_blocks, s);
+                launch_langevin_step_items(h->lang_partial, h->B, h->lang_blocks, sc.snr, h->item_step, s);
+                launch_corrector_items(h->X, h->score, nz(d), ir, h->item_step, 0.f, h->X, nullptr, h->B, n_per_b, s);
+            } else if (per_item) {
+                const float sd = sc.snr * ouve_std(h->cfg, t);
+                launch_corrector_items(h->X, h->score, nz(d), ir, nullptr, sd * sd * 2.f, h->X, nullptr, h->B, n_per_b, s);
+            } else if (sc.corrector == USE_CORR_LANGEVIN) {
                 launch_langevin_norms(h->score, nz(d), rr, h->lang_partial, h->B, n_per_b, h->lang_blocks, s);
                 launch_langevin_step(h->lang_partial, h->B, h->lang_blocks, sc.snr, h->lang_step, s);
                 launch_corrector(h->X, h->score, nz(d), rr, h->lang_step, 0.f, h->X, nullptr, n, s);
@@ -857,6 +874,10 @@ static void run_sampler(use_handle* h, const float2* noise, hipStream_t s, int i
         } else {
             run_score(h, h->X, h->Cond, temb, 0, h->ts_dev + i, 0, h->score, s, -1.f, h->pcp == 8 ? h->cond2_buf : nullptr);
             float cd, cs, cn; predictor_coeffs(h->cfg, sc.predictor, t, sc.N, cd, cs, cn);
+            if (per_item)
+                launch_predictor_items(h->X, h->Y, h->score, nz(d), ItemRng{h->item_seeds, d}, cd, cs, cn, h->X,
+                                       i == sc.N - 1 ? h->Xmean : nullptr, h->B, n_per_b, s);
+            else
             launch_predictor(h->X, h->Y, h->score, nz(d), RngRef{h->rng_state, d}, cd, cs, cn, h->X,
                              i == sc.N - 1 ? h->Xmean : nullptr, n, s);
             d++;
@@ -873,7 +894,7 @@ static void drop_graphs(use_handle* h) {
 // everything of the handle that belongs to ONE plan (the current plan lives in the handle's own fields)
 #define USE_PLAN_FIELDS(X)                                                                                            \
     X(B) X(T) X(nsub) X(arena) X(arena_alloc) X(arena_plan_bytes) X(persist) X(persist_bytes) X(persist_alloc) X(x4) X(silu_temb) X(tembias) X(t_dev) \
-    X(Y) X(X) X(Xmean) X(score) X(xin) X(cond_buf) X(cond2_buf) X(Cond) X(lang_partial) X(lang_step) X(rng_state) X(lang_blocks)   \
+    X(Y) X(X) X(Xmean) X(score) X(xin) X(cond_buf) X(cond2_buf) X(Cond) X(lang_partial) X(lang_step) X(rng_state) X(item_seeds) X(item_step) X(lang_blocks)   \
     X(sc) X(sampler_set) X(timesteps) X(ts_dev) X(temb_table) X(silu_table) X(noise_copy) X(noise_copy_bytes) X(score_graph)      \
     X(debug) X(debug_B) X(opt_gen_at_plan) X(oc) X(ode_set)
 struct use_handle::PlanState {
@@ -881,7 +902,7 @@ struct use_handle::PlanState {
     USE_PLAN_FIELDS(X)
 #undef X
     int sub_B[MAX_SUB]; Arena sub_arena[MAX_SUB], st_arena[MAX_SUB];
-    std::vector<hipGraphExec_t> graph_exec[2];
+    std::vector<hipGraphExec_t> graph_exec[4];
 };
 static long long g_opt_gen = 0;                  // bumped by every use_set_option: plans built under other options are not reused
 static int g_plan_cache = 4;                     // plans kept besides the current one
@@ -890,7 +911,7 @@ static void plan_stash(use_handle* h, use_handle::PlanState& p) {      // handle
     USE_PLAN_FIELDS(X)
 #undef X
     for (int i = 0; i < MAX_SUB; ++i) { p.sub_B[i] = h->sub_B[i]; p.sub_arena[i] = h->sub_arena[i]; p.st_arena[i] = h->st_arena[i]; }
-    for (int i = 0; i < 2; ++i) { p.graph_exec[i] = std::move(h->graph_exec[i]); h->graph_exec[i].clear(); }
+    for (int i = 0; i < 4; ++i) { p.graph_exec[i] = std::move(h->graph_exec[i]); h->graph_exec[i].clear(); }
     h->B = h->T = 0; h->arena = Arena{}; h->arena_alloc = 0; h->persist = nullptr; h->persist_bytes = h->persist_alloc = 0;
     h->ts_dev = h->temb_table = h->silu_table = nullptr; h->noise_copy = nullptr; h->noise_copy_bytes = 0; h->score_graph = nullptr;
     h->sampler_set = false; h->timesteps.clear(); h->debug.clear(); h->ode_set = false;
@@ -900,7 +921,7 @@ static void plan_restore(use_handle* h, use_handle::PlanState& p) {    // p -> h
     USE_PLAN_FIELDS(X)
 #undef X
     for (int i = 0; i < MAX_SUB; ++i) { h->sub_B[i] = p.sub_B[i]; h->sub_arena[i] = p.sub_arena[i]; h->st_arena[i] = p.st_arena[i]; }
-    for (int i = 0; i < 2; ++i) h->graph_exec[i] = std::move(p.graph_exec[i]);
+    for (int i = 0; i < 4; ++i) h->graph_exec[i] = std::move(p.graph_exec[i]);
 }
 static void plan_free(use_handle::PlanState* p) {
     for (auto& v : p->graph_exec) for (auto g : v) if (g) (void)hipGraphExecDestroy(g);
@@ -922,11 +943,12 @@ static int ensure_sde_scratch(use_handle* h) {
     if (!h) return fail(USE_E_INVALID, "null handle");
     HIPCHK(hipSetDevice(h->device));
     if (!h->sde_buf) {
-        const size_t bytes = 512 + (size_t)use_handle::SDE_MAX_B * use_handle::SDE_BLOCKS * 2 * 4;
+        const size_t part = (size_t)use_handle::SDE_MAX_B * use_handle::SDE_BLOCKS * 2 * 4;
+        const size_t bytes = 512 + part + (size_t)use_handle::SDE_MAX_B * 8;       // + the seeds of use_fill_noise_items
         HIPCHK(hipMalloc((void**)&h->sde_buf, bytes));
         HIPCHK(hipMemset(h->sde_buf, 0, bytes));
         h->sde_rng = (unsigned long long*)h->sde_buf; h->sde_step = (float*)(h->sde_buf + 256);
-        h->sde_partial = (float*)(h->sde_buf + 512);
+        h->sde_partial = (float*)(h->sde_buf + 512); h->sde_seeds = (unsigned long long*)(h->sde_buf + 512 + part);
     }
     return USE_OK;
 }
@@ -1248,7 +1270,8 @@ int use_plan(use_handle* h, int B, int Tpad) {
     auto take = [&](size_t bytes) { off = (off + 255) & ~(size_t)255; size_t o = off; off += bytes; return o; };
     const size_t o_x4 = take(n * 4 * h->pcp), o_c2 = take(h->pcp == 8 ? n * 8 : 0), o_Y = take(n * 8), o_X = take(n * 8), o_Xm = take(n * 8), o_sc = take(n * 8),
                  o_xin = take(n * 8), o_cond = take(n * 8), o_st = take((size_t)B * 4 * h->cfg.nf * 4), o_tb = take((size_t)B * h->dense_rows * 4),
-                 o_t = take((size_t)B * 4), o_lp = take((size_t)B * h->lang_blocks * 2 * 4), o_ls = take(256), o_rng = take(256);
+                 o_t = take((size_t)B * 4), o_lp = take((size_t)B * h->lang_blocks * 2 * 4), o_ls = take(256), o_rng = take(256),
+                 o_is = take((size_t)B * 8), o_ist = take((size_t)B * 4);
     h->persist_bytes = off;
     if (!h->persist || off > h->persist_alloc) {
         if (h->persist) { HIPCHK(hipFree(h->persist)); h->persist = nullptr; h->persist_alloc = 0; }
@@ -1266,6 +1289,7 @@ int use_plan(use_handle* h, int B, int Tpad) {
     h->silu_temb = (float*)(h->persist + o_st); h->tembias = (float*)(h->persist + o_tb); h->t_dev = (float*)(h->persist + o_t);
     h->lang_partial = (float*)(h->persist + o_lp); h->lang_step = (float*)(h->persist + o_ls);
     h->rng_state = (unsigned long long*)(h->persist + o_rng);
+    h->item_seeds = (unsigned long long*)(h->persist + o_is); h->item_step = (float*)(h->persist + o_ist);
     HIPCHK(hipMemset(h->persist, 0, off));
     return USE_OK;
 }
@@ -1454,8 +1478,23 @@ static int load_sampler_inputs(use_handle* h, const void* y, const void* cond, c
     return USE_OK;
 }
 
-int use_sample_cond2(use_handle* h, const void* y, const void* cond, const void* cond2, const void* noise, uint64_t seed, void* out,
-                     use_stream_t stream) {
+}  // extern "C"
+
+// up to 32 per-item seeds per launch, passed by value: the host array is free again when the call returns, and nothing synchronises
+struct SeedPack { unsigned long long v[32]; };
+__global__ void set_item_seeds_kernel(unsigned long long* dst, SeedPack p, int n) { if ((int)threadIdx.x < n) dst[threadIdx.x] = p.v[threadIdx.x]; }
+static void upload_item_seeds(unsigned long long* dst, const uint64_t* seeds_host, int B, hipStream_t s) {
+    for (int b0 = 0; b0 < B; b0 += 32) {
+        SeedPack p{};
+        const int k = std::min(32, B - b0);
+        for (int i = 0; i < k; ++i) p.v[i] = (unsigned long long)seeds_host[b0 + i];
+        hipLaunchKernelGGL(set_item_seeds_kernel, dim3(1), dim3(32), 0, s, dst + b0, p, k);
+    }
+}
+
+// use_sample_cond2 (seeds_host == null, per_item false) and use_sample_items (per_item)
+static int sample_impl(use_handle* h, const void* y, const void* cond, const void* cond2, const void* noise, uint64_t seed,
+                       const uint64_t* seeds_host, bool per_item, void* out, use_stream_t stream) {
     int rc = check_ready(h); if (rc) return rc;
     if (!h->sampler_set) return fail(USE_E_STATE, "use_set_sampler has not been called");
     if (!y || !out) return fail(USE_E_INVALID, "null tensor");
@@ -1465,12 +1504,13 @@ int use_sample_cond2(use_handle* h, const void* y, const void* cond, const void*
     hipStream_t s = (hipStream_t)stream;
     const size_t n = (size_t)h->B * h->cfg.n_freq * h->T;
     rc = load_sampler_inputs(h, y, cond, cond2, s); if (rc) return rc;
-    hipLaunchKernelGGL(set_rng_kernel, dim3(1), dim3(1), 0, s, h->rng_state, (unsigned long long)seed, 0ull);
+    if (per_item) { if (seeds_host) upload_item_seeds(h->item_seeds, seeds_host, h->B, s); }
+    else hipLaunchKernelGGL(set_rng_kernel, dim3(1), dim3(1), 0, s, h->rng_state, (unsigned long long)seed, 0ull);
     if (!h->sc.use_graph) {
-        run_sampler(h, (const float2*)noise, s, 0, h->sc.N);
+        run_sampler(h, (const float2*)noise, s, 0, h->sc.N, per_item);
         rc = eval_status(h); if (rc) return rc;
     } else {
-        const int gi = noise ? 1 : 0;
+        const int gi = (noise ? 1 : 0) + (per_item ? 2 : 0);
         const float2* nz = nullptr;
         if (noise) {
             const size_t nb = (size_t)use_num_noise_draws(h) * n * 8;
@@ -1478,8 +1518,10 @@ int use_sample_cond2(use_handle* h, const void* y, const void* cond, const void*
                 HIPCHK(hipStreamSynchronize(s));
                 if (h->noise_copy) HIPCHK(hipFree(h->noise_copy));
                 h->noise_copy = nullptr; h->noise_copy_bytes = 0;
-                for (auto g : h->graph_exec[1]) if (g) (void)hipGraphExecDestroy(g);
-                h->graph_exec[1].clear();
+                for (int k = 1; k < 4; k += 2) {                           // both forms' injected-noise graphs hold the address
+                    for (auto g : h->graph_exec[k]) if (g) (void)hipGraphExecDestroy(g);
+                    h->graph_exec[k].clear();
+                }
                 if (hipMalloc((void**)&h->noise_copy, nb) != hipSuccess) return fail(USE_E_NOMEM, "cannot allocate %.1f MB noise staging", nb / 1e6);
                 h->noise_copy_bytes = nb;
             }
@@ -1497,7 +1539,7 @@ int use_sample_cond2(use_handle* h, const void* y, const void* cond, const void*
                 hipGraph_t g = nullptr;
                 hipGraphExec_t ge = nullptr;
                 HIPCHK(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
-                run_sampler(h, nz, h->cap_stream, i0, std::min(h->sc.N, i0 + per_seg));
+                run_sampler(h, nz, h->cap_stream, i0, std::min(h->sc.N, i0 + per_seg), per_item);
                 // (nothing returns between begin and end: a failed launch invalidates the capture and surfaces here, with the
                 // stream out of capture mode either way)
                 hipError_t e = hipStreamEndCapture(h->cap_stream, &g);
@@ -1520,6 +1562,19 @@ int use_sample_cond2(use_handle* h, const void* y, const void* cond, const void*
     HIPCHK(hipMemcpyAsync(out, h->Xmean, n * 8, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipGetLastError());
     return USE_OK;
+}
+
+extern "C" {
+
+int use_sample_cond2(use_handle* h, const void* y, const void* cond, const void* cond2, const void* noise, uint64_t seed, void* out,
+                     use_stream_t stream) {
+    return sample_impl(h, y, cond, cond2, noise, seed, nullptr, false, out, stream);
+}
+
+int use_sample_items(use_handle* h, const void* y, const void* cond, const void* cond2, const void* noise, const uint64_t* seeds_host,
+                     void* out, use_stream_t stream) {
+    if (!noise && !seeds_host) return fail(USE_E_INVALID, "use_sample_items needs per-item seeds or injected noise");
+    return sample_impl(h, y, cond, cond2, noise, 0, seeds_host, true, out, stream);
 }
 
 // ---- probability-flow ODE sampler (reference sampling/__init__.py:76-159): the RK45 stepper of use_ode.hip -------------------
@@ -1954,6 +2009,17 @@ int use_sde_prior(use_handle* h, const void* y, const void* noise, uint64_t seed
     int rc = ensure_sde_scratch(h); if (rc) return rc;
     hipLaunchKernelGGL(set_rng_kernel, dim3(1), dim3(1), 0, (hipStream_t)s, h->sde_rng, (unsigned long long)seed, 0ull);
     launch_prior((const float2*)y, (const float2*)noise, RngRef{h->sde_rng, 0}, ouve_std(h->cfg, 1.0f), (float2*)x, n, (hipStream_t)s);
+    HIPCHK(hipGetLastError());
+    return USE_OK;
+}
+
+int use_fill_noise_items(use_handle* h, const uint64_t* seeds_host, int B, int draw, void* out, int64_t n, use_stream_t s) {
+    if (!seeds_host || !out || B < 1 || draw < 0 || n < 0 || n % B != 0) return fail(USE_E_INVALID, "use_fill_noise_items: null argument, or n is no multiple of B");
+    if (B > use_handle::SDE_MAX_B) return fail(USE_E_INVALID, "B=%d exceeds %d", B, use_handle::SDE_MAX_B);
+    int rc = ensure_sde_scratch(h); if (rc) return rc;
+    if (n == 0) return USE_OK;
+    upload_item_seeds(h->sde_seeds, seeds_host, B, (hipStream_t)s);
+    launch_fill_noise_items((float2*)out, ItemRng{h->sde_seeds, (unsigned)draw}, B, (long)(n / B), (hipStream_t)s);
     HIPCHK(hipGetLastError());
     return USE_OK;
 }

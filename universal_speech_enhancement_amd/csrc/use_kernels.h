@@ -95,6 +95,10 @@ inline int conv_v4_tiles(int H, int W) { return ((H + 15) / 16) * ((W + 31) / 32
 bool conv_sk_eligible(const ConvArgs& a);
 void conv_sk_set_max_px(long n);                         // largest map (H*W) it is used for (default 16x20)
 void launch_conv_sk(const ConvArgs& a, hipStream_t s);
+// Launches of the calling thread choose conv_sk's tile form from the per-image shape alone (as for a batch of one) while this is
+// on: the two forms add K in passes of different width, so the default choice - by the workgroup count of the whole (sub-)batch -
+// makes an item's bits depend on how many items are evaluated with it.  The per-item sampler (use_sample_items) turns it on.
+void conv_sk_set_per_image(bool on);
 void launch_conv_generic(const ConvArgs& a, hipStream_t s);   // conv_kernel / pyr_conv_kernel / conv_in_kernel only (no specialised schedule)
 void pyr_conv_set_ws(int n);                            // wave-specialised form of the same layer (0: off, 1: on, n > 1: workgroups per launch)
 bool conv_v4_eligible(const ConvArgs& a);
@@ -232,6 +236,23 @@ void launch_langevin_step(const float* partial, int B, int blocks_per_b, float s
 void launch_corrector(const float2* x, const float2* score, const float2* noise, RngRef rng, const float* step_dev,
                       float step_host, float2* x_out, float2* x_mean, long n, hipStream_t s);
 void launch_fill_noise(float2* out, RngRef rng, long n, hipStream_t s);
+// The per-item forms (use_sample_items): grid (blocks, B); item b's z at element j of its n_per_b elements is
+// noise[b*n_per_b + j] when noise != null, else Philox(seeds[b], draw, j) - the stream of a one-item batch with that seed.
+struct ItemRng { const unsigned long long* seeds; unsigned draw; };  // seeds: device [B]
+void launch_prior_items(const float2* y, const float2* noise, ItemRng rng, float std1, float2* x, int B, long n_per_b,
+                        hipStream_t s);
+void launch_predictor_items(const float2* x, const float2* y, const float2* score, const float2* noise, ItemRng rng,
+                            float c_drift, float c_score, float c_noise, float2* x_out, float2* x_mean, int B,
+                            long n_per_b, hipStream_t s);
+void launch_langevin_norms_items(const float2* score, const float2* noise, ItemRng rng, float* partial, int B,
+                                 long n_per_b, int blocks_per_b, hipStream_t s);
+// step[b] = 2*(snr * ||z_b|| / ||g_b||)^2, one wave per item
+void launch_langevin_step_items(const float* partial, int B, int blocks_per_b, float snr, float* step, hipStream_t s);
+// eps = step_dev[b] if step_dev else step_host
+void launch_corrector_items(const float2* x, const float2* score, const float2* noise, ItemRng rng,
+                            const float* step_dev, float step_host, float2* x_out, float2* x_mean, int B, long n_per_b,
+                            hipStream_t s);
+void launch_fill_noise_items(float2* out, ItemRng rng, int B, long n_per_b, hipStream_t s);
 
 // ---- probability-flow ODE sampler (use_ode.hip): scipy's RK45 on the device, one step-size controller per group of items ----
 struct OdeGroup {                          // controller state of one group (scipy's RungeKutta solver object)

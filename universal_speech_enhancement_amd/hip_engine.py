@@ -325,10 +325,13 @@ class HipScoreEngine:
         return np.array(buf[:], dtype=np.float32)
 
     def sample(self, y: torch.Tensor, noise: Optional[torch.Tensor] = None, seed: int = 0,
-               cond: Optional[torch.Tensor] = None, cond2: Optional[torch.Tensor] = None) -> torch.Tensor:
+               cond: Optional[torch.Tensor] = None, cond2: Optional[torch.Tensor] = None, item_seeds=None,
+               per_item: bool = False) -> torch.Tensor:
         """Run the configured PC sampler on y (complex64 [B,1,F,T']); returns x_mean of the last step.  ``cond``: score
         conditioning when it is not y itself (``use_sample_cond``); ``cond2``: the second conditioning spectrogram of a
-        6-channel network (``use_sample_cond2``)."""
+        6-channel network (``use_sample_cond2``).  ``item_seeds`` (B integers) or ``per_item``: the batch-invariant form
+        (``use_sample_items``) - every item draws from its own noise stream (``item_seeds[b]``, or its slice of ``noise``) and
+        takes its own Langevin step, so that at equal T' its result does not depend on the batch it rides in."""
         y = _require_cuda_c64("y", y)
         cptr = None if cond is None or cond is y else _require_cuda_c64("cond", cond, y.shape).data_ptr()
         c2ptr = None if cond2 is None else _require_cuda_c64("cond2", cond2, y.shape).data_ptr()
@@ -338,6 +341,18 @@ class HipScoreEngine:
         if noise is not None:
             noise = _require_cuda_c64("noise", noise, (self.num_noise_draws(),) + tuple(y.shape))
             nptr = noise.data_ptr()
+        if per_item or item_seeds is not None:
+            sptr = None
+            if item_seeds is not None:
+                if len(item_seeds) != y.shape[0]:
+                    raise ValueError(f"item_seeds must have {y.shape[0]} entries, got {len(item_seeds)}")
+                sptr = (C.c_uint64 * y.shape[0])(*[int(v) & (2**64 - 1) for v in item_seeds])
+            elif nptr is None:
+                raise ValueError("per_item sampling needs item_seeds or injected noise")
+            out = torch.empty_like(y)
+            check(self.L.use_sample_items(self.h, y.data_ptr(), cptr, c2ptr, nptr, sptr, out.data_ptr(), _stream_ptr(y.device)),
+                  "use_sample_items")
+            return out
         out = torch.empty_like(y)
         check(self.L.use_sample_cond2(self.h, y.data_ptr(), cptr, c2ptr, nptr, int(seed) & (2**64 - 1), out.data_ptr(),
                                       _stream_ptr(y.device)), "use_sample_cond2")
@@ -373,6 +388,18 @@ class HipScoreEngine:
         predictor draw.  Replaying these through ``sample(noise=...)`` reproduces the device-noise run bit for bit."""
         out = torch.empty(tuple(shape), dtype=torch.complex64, device=f"cuda:{self.device}")
         check(self.L.use_fill_noise(self.h, int(seed) & (2**64 - 1), int(draw), out.data_ptr(), out.numel(), _stream_ptr(out.device)), "use_fill_noise")
+        return out
+
+    def fill_noise_items(self, seeds, draw: int, shape) -> torch.Tensor:
+        """Draw ``draw`` of the per-item noise streams of ``sample(item_seeds=seeds)`` as a complex64 tensor of ``shape``
+        [B,1,F,T'] (``use_fill_noise_items``): item b is ``fill_noise(seeds[b], draw, shape[1:])``."""
+        shape = tuple(shape)
+        if len(seeds) != shape[0]:
+            raise ValueError(f"{len(seeds)} seeds for {shape[0]} items")
+        out = torch.empty(shape, dtype=torch.complex64, device=f"cuda:{self.device}")
+        sp = (C.c_uint64 * shape[0])(*[int(v) & (2**64 - 1) for v in seeds])
+        check(self.L.use_fill_noise_items(self.h, sp, shape[0], int(draw), out.data_ptr(), out.numel(), _stream_ptr(out.device)),
+              "use_fill_noise_items")
         return out
 
     def debug_tensor(self, name: str) -> torch.Tensor:

@@ -6,6 +6,10 @@
          model.sampler_kwargs.minibatch=1]]      (the probability-flow ODE sampler: RK45, one step-size controller per utterance)
         [model.sampler_kwargs.chunk_frames=512 [model.sampler_kwargs.chunk_overlap=64 model.sampler_kwargs.chunk_batch=8]]
                                                  (long recordings in overlapping windows of 512 frames; also with model=LSGAN)
+        [model.sampler_kwargs.per_item=true [model.sampler_kwargs.seed=S]]
+                                                 (batch-invariant sampling: every file draws from its own noise stream, seeded from S and
+                                                  its path relative to data_folder, and takes its own Langevin step - the output does not
+                                                  depend on batch order, world size, or data.batch_size at equal padded length; off by default)
         [data.clean_folder=clean/]               (score every enhanced file whose clean counterpart exists under clean/ at the same
                                                   relative path: SI-SDR / SI-SIR / SI-SAR / LSD on the device -> enhanced/metrics.csv)
 

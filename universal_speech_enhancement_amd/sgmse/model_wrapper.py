@@ -124,13 +124,16 @@ class ScoreModel(SpectralGlue, nn.Module):
 
     # ---- samplers (reference :210-260) -------------------------------------------------------------------
     def fused_sample(self, y, N, predictor, corrector, corrector_steps, snr, t_eps, noise=None, seed=0, use_graph=True,
-                     sde=None, cond=None, cond2=None):
+                     sde=None, cond=None, cond2=None, item_seeds=None):
         """Whole PC loop inside libuse_hip.so (``use_sample_cond2``), with the OUVE constants of ``sde`` (default: ``self.sde``);
-        ``cond``: the score conditioning when it is not ``y`` itself; ``cond2``: the second one of condition="both"."""
+        ``cond``: the score conditioning when it is not ``y`` itself; ``cond2``: the second one of condition="both".
+        ``item_seeds`` (B integers): the batch-invariant form (``use_sample_items``; an injected ``noise`` takes their place)."""
         sde = self.sde if sde is None else sde
         eng = self.score_net.engine(y.shape[2], y.device, sde_constants=(sde.theta, sde.sigma_min, sde.sigma_max))
         eng.plan(y.shape[0], y.shape[3])
         eng.set_sampler(N, predictor, corrector, corrector_steps, snr, t_eps, use_graph=use_graph)
+        if item_seeds is not None:
+            return eng.sample(y, noise=noise, cond=cond, cond2=cond2, item_seeds=item_seeds, per_item=True)
         return eng.sample(y, noise=noise, seed=seed, cond=cond, cond2=cond2)
 
     def get_pc_sampler(self, predictor_name, corrector_name, y, N=None, minibatch=None, **kwargs):
@@ -142,12 +145,18 @@ class ScoreModel(SpectralGlue, nn.Module):
             return sampling.get_pc_sampler(predictor_name, corrector_name, sde=sde, score_fn=self, y=y, **kwargs)
         M = y.shape[0]
         cond = kwargs.pop("conditioning", None)
+        seeds = kwargs.pop("item_seeds", None)
+        if kwargs.get("per_item") and seeds is None:        # named by the item's index in the whole batch, not in its minibatch
+            from ..seeding import item_seeds as derive_item_seeds
+            seeds = derive_item_seeds(kwargs.get("seed", 0), M)
 
         def batched_sampling_fn():
             samples, ns = [], []
             for i in range(int(ceil(M / minibatch))):
                 y_mini = y[i * minibatch:(i + 1) * minibatch]
                 c_mini = None if cond is None else [y_mini if c is y else c[i * minibatch:(i + 1) * minibatch] for c in cond]
+                if seeds is not None:
+                    kwargs["item_seeds"] = list(seeds[i * minibatch:(i + 1) * minibatch])
                 sample, n = sampling.get_pc_sampler(predictor_name, corrector_name, sde=sde, score_fn=self, y=y_mini,
                                                     conditioning=c_mini, **kwargs)()
                 samples.append(sample); ns.append(n)
@@ -155,14 +164,17 @@ class ScoreModel(SpectralGlue, nn.Module):
         return batched_sampling_fn
 
     def fused_sample_ode(self, y, N, t_eps, group=0, rtol=1e-5, atol=1e-5, denoise=True, noise=None, seed=0, use_graph=True, sde=None,
-                         cond=None, cond2=None, first_step=None, max_step=None, max_nfe=0):
+                         cond=None, cond2=None, first_step=None, max_step=None, max_nfe=0, item_seeds=None):
         """Probability-flow ODE sampler inside libuse_hip.so (``use_sample_ode``): RK45 with one step-size controller per ``group``
-        items (0: the batch); returns (x, nfev per group, status per group)."""
+        items (0: the batch); returns (x, nfev per group, status per group).  ``item_seeds``: the prior of item b is draw 0 of its
+        own noise stream (``use_fill_noise_items``), injected as ``noise``."""
         sde = self.sde if sde is None else sde
         eng = self.score_net.engine(y.shape[2], y.device, sde_constants=(sde.theta, sde.sigma_min, sde.sigma_max))
         eng.plan(y.shape[0], y.shape[3])
         eng.set_ode(rtol=rtol, atol=atol, t_eps=t_eps, N=N, group=group, denoise=denoise, first_step=first_step, max_step=max_step,
                     max_nfe=max_nfe, use_graph=use_graph)
+        if item_seeds is not None and noise is None:
+            noise = eng.fill_noise_items(item_seeds, 0, y.shape)
         return eng.sample_ode(y, noise=noise, seed=seed, cond=cond, cond2=cond2)
 
     def get_ode_sampler(self, y, N=None, minibatch=1, **kwargs):
@@ -175,7 +187,8 @@ class ScoreModel(SpectralGlue, nn.Module):
         return sampling.get_ode_sampler(sde, self, y=y, minibatch=minibatch, **kwargs)
 
     def sample_spec_chunked(self, sde_input, conditioning, sampler_type="pc", N=50, corrector_steps=1, snr=0.5, noise=None, seed=0,
-                            chunk_frames=512, chunk_overlap=64, chunk_batch=8, predictor=None, corrector=None, **ode_kwargs):
+                            chunk_frames=512, chunk_overlap=64, chunk_batch=8, predictor=None, corrector=None, per_item=False,
+                            item_seeds=None, **ode_kwargs):
         """Chunked sampling at the spectrogram level (no reference counterpart; ``chunking``): ``sde_input`` [B,1,F,T'] and every tensor
         of ``conditioning`` are cut into n windows of ``chunk_frames`` frames, ``chunk_overlap`` frames shared by neighbours
         (``use_chunk_split``); the B * n windows run through the un-chunked sampler (``fused_sample`` / ``fused_sample_ode`` for the
@@ -188,7 +201,12 @@ class ScoreModel(SpectralGlue, nn.Module):
         The step size of the Langevin / annealed-Langevin corrector is a mean over the group, as it is over any batch of the
         un-chunked sampler (``sampling/correctors.py``: norms averaged over the batch): the windows of a group are coupled exactly as
         the utterances of a batch are, so a window's result depends on ``chunk_batch`` and on its neighbours in the group.  Overlapping
-        frames of neighbouring windows draw independent noise.  ``self.last_nfe``: the NFE of every group."""
+        frames of neighbouring windows draw independent noise.  ``self.last_nfe``: the NFE of every group.
+
+        ``per_item=True`` removes that coupling (``use_sample_items``): window k of item b samples with
+        ``seeding.window_seed(item_seeds[b], k)`` (``item_seeds`` default: ``seeding.item_seed(seed, b)``) and takes its own Langevin
+        step, and every window has the same T' = ``chunk_frames``, so an item's merged result does not depend on ``chunk_batch`` nor
+        on the other items of the call.  With one window (T' <= ``chunk_frames``) the items sample with ``item_seeds`` themselves."""
         from ..chunking import chunk_plan, map_chunked
         predictor = self.predictor if predictor is None else predictor
         corrector = self.corrector if corrector is None else corrector
@@ -197,16 +215,28 @@ class ScoreModel(SpectralGlue, nn.Module):
         if sampler_type == "pc" and ode_kwargs:
             raise TypeError(f"sample(sampler_type='pc') got ODE sampler options {sorted(ode_kwargs)}")
 
+        inputs = [sde_input] + list(conditioning)
+        plan = chunk_plan(int(sde_input.shape[3]), chunk_frames, chunk_overlap)
+        if per_item:
+            from ..seeding import item_seeds as derive_item_seeds, window_seed
+            if item_seeds is None:
+                item_seeds = derive_item_seeds(seed, sde_input.shape[0])
+            if len(item_seeds) != sde_input.shape[0]:
+                raise ValueError(f"item_seeds has {len(item_seeds)} entries for a batch of {sde_input.shape[0]}")
+            # window w of the split is window w % n of item w // n
+            wseeds = list(item_seeds) if plan.n == 1 else [window_seed(s, k) for s in item_seeds for k in range(plan.n)]
+        elif item_seeds is not None:
+            raise ValueError("item_seeds needs per_item=True")
+
         def run(g, lo, hi, windows):
             y, cond = windows[0], windows[1:]
             z = None if noise is None else (noise[:, lo:hi] if noise.dim() == y.dim() + 1 else noise[lo:hi])
+            kw = {"seed": seed + g} if not per_item else {"seed": seed, "per_item": True, "item_seeds": wseeds[lo:hi]}
             if sampler_type == "pc":
                 return self.get_pc_sampler(predictor, corrector, y, N=N, corrector_steps=corrector_steps, snr=snr, intermediate=False,
-                                           conditioning=cond, noise=z, seed=seed + g)()
-            return self.get_ode_sampler(y, N=N, conditioning=cond, noise=z, seed=seed + g, **ode_kwargs)()
+                                           conditioning=cond, noise=z, **kw)()
+            return self.get_ode_sampler(y, N=N, conditioning=cond, noise=z, **kw, **ode_kwargs)()
 
-        inputs = [sde_input] + list(conditioning)
-        plan = chunk_plan(int(sde_input.shape[3]), chunk_frames, chunk_overlap)
         if plan.n == 1:
             sample, nfe = run(0, 0, sde_input.shape[0], inputs)
             self.last_nfe = [nfe]
@@ -227,13 +257,20 @@ class ScoreModel(SpectralGlue, nn.Module):
         return chunk_plan(int(Tp), chunk_frames, chunk_overlap).n > 1
 
     def sample(self, batch, sampler_type="pc", N=50, corrector_steps=1, snr=0.5, noise=None, seed=0, chunk_frames=None,
-               chunk_overlap=64, chunk_batch=8, **ode_kwargs):
+               chunk_overlap=64, chunk_batch=8, per_item=False, item_seeds=None, **ode_kwargs):
         """Reference :262-329: adds ``batch['enhanced']`` (float32 [B, L]) for condition / sde_input 'noisy'.
         ``sampler_type="ode"``: the probability-flow ODE sampler (``get_ode_sampler``; ``ode_kwargs``: ``rtol``, ``atol``,
         ``minibatch`` (default 1), ``first_step``, ``max_step``, ``max_nfe``); its NFE is left in ``self.last_nfe``.
         ``chunk_frames`` (a multiple of 64; default ``None``: off) samples recordings of more padded frames than that in overlapping
         windows (``sample_spec_chunked``, which documents ``chunk_overlap``, ``chunk_batch``, the seed rule and the noise layout);
-        shorter ones take the un-chunked path, bit-identically."""
+        shorter ones take the un-chunked path, bit-identically.
+        ``per_item`` (default off) / ``item_seeds``: batch-invariant sampling (``sampling.get_pc_sampler``) - every item has its own noise
+        stream and its own Langevin step, so that at equal padded frame count T' its result does not depend on the batch it rides in.
+        Zero padding to the batch's longest item changes T' and with it what the network sees: un-chunked batches of unequal lengths
+        stay composition-dependent through T'."""
+        item_kw = {"per_item": True, "item_seeds": item_seeds} if per_item else {}
+        if item_seeds is not None and not per_item:
+            raise ValueError("item_seeds needs per_item=True")
         y = batch["perturbed"]
         T_orig = y.size(1)
         Y = self._spectrogram(y)
@@ -257,16 +294,16 @@ class ScoreModel(SpectralGlue, nn.Module):
         if self._chunked(sde_input.shape[3], chunk_frames, chunk_overlap, chunk_batch):
             sample = self.sample_spec_chunked(sde_input, score_conditioning, sampler_type=sampler_type, N=N, corrector_steps=corrector_steps,
                                               snr=snr, noise=noise, seed=seed, chunk_frames=chunk_frames, chunk_overlap=chunk_overlap,
-                                              chunk_batch=chunk_batch, **ode_kwargs)
+                                              chunk_batch=chunk_batch, **item_kw, **ode_kwargs)
             batch["fake_sde_enhanced" if (self.sde_input == "denoised" and Y_denoised is not None) else "enhanced"] = self._waveform(sample, T_orig)
             return batch
         if sampler_type == "pc":
             if ode_kwargs:
                 raise TypeError(f"sample(sampler_type='pc') got ODE sampler options {sorted(ode_kwargs)}")
             sampler = self.get_pc_sampler(self.predictor, self.corrector, sde_input, N=N, corrector_steps=corrector_steps, snr=snr,
-                                          intermediate=False, conditioning=score_conditioning, noise=noise, seed=seed)
+                                          intermediate=False, conditioning=score_conditioning, noise=noise, seed=seed, **item_kw)
         elif sampler_type == "ode":                                      # reference :314-316
-            sampler = self.get_ode_sampler(sde_input, N=N, conditioning=score_conditioning, noise=noise, seed=seed, **ode_kwargs)
+            sampler = self.get_ode_sampler(sde_input, N=N, conditioning=score_conditioning, noise=noise, seed=seed, **item_kw, **ode_kwargs)
         else:
             raise NotImplementedError(f"{sampler_type} is not a valid sampler type!")
         sample, nfe = sampler()
@@ -278,12 +315,16 @@ class ScoreModel(SpectralGlue, nn.Module):
     @torch.no_grad()
     def enhance(self, y, sampler_type="pc", predictor="reverse_diffusion", corrector="ald", N=50, corrector_steps=1,
                 snr=0.5, timeit=False, return_stft=False, noise=None, seed=0, sr=24000, chunk_frames=None, chunk_overlap=64,
-                chunk_batch=8, **kwargs):
+                chunk_batch=8, per_item=False, item_seeds=None, **kwargs):
         """One-call enhancement of noisy speech ``y`` [1, L] -- keyword surface of the legacy
         ``ScoreModel.enhance`` (reference ``sgmse/model.py:351-402``).  ``chunk_frames`` / ``chunk_overlap`` / ``chunk_batch``: chunked
         sampling of a long recording, as for ``sample`` (``sample_spec_chunked``).  As un-chunked, ``kwargs`` are the ODE sampler's options
         and are ignored for "pc"; with ``timeit`` the NFE of a chunked "pc" run is the int every group took (the step count fixes it),
-        that of a chunked "ode" run a list with one entry per group, each what the un-chunked call returns."""
+        that of a chunked "ode" run a list with one entry per group, each what the un-chunked call returns.  ``per_item`` /
+        ``item_seeds``: batch-invariant sampling, as for ``sample``."""
+        item_kw = {"per_item": True, "item_seeds": item_seeds} if per_item else {}
+        if item_seeds is not None and not per_item:
+            raise ValueError("item_seeds needs per_item=True")
         import time
         start = time.time()
         T_orig = y.size(1)
@@ -295,13 +336,13 @@ class ScoreModel(SpectralGlue, nn.Module):
         if self._chunked(Y.shape[3], chunk_frames, chunk_overlap, chunk_batch):
             sample = self.sample_spec_chunked(Y, [Y], sampler_type=sampler_type, N=N, corrector_steps=corrector_steps, snr=snr, noise=noise,
                                               seed=seed, chunk_frames=chunk_frames, chunk_overlap=chunk_overlap, chunk_batch=chunk_batch,
-                                              predictor=predictor, corrector=corrector, **(kwargs if sampler_type == "ode" else {}))
+                                              predictor=predictor, corrector=corrector, **item_kw, **(kwargs if sampler_type == "ode" else {}))
             nfe = self.last_nfe[0] if sampler_type == "pc" else self.last_nfe
         elif sampler_type == "pc":
             sample, nfe = self.get_pc_sampler(predictor, corrector, Y, N=N, corrector_steps=corrector_steps, snr=snr,
-                                              intermediate=False, conditioning=[Y], noise=noise, seed=seed)()
+                                              intermediate=False, conditioning=[Y], noise=noise, seed=seed, **item_kw)()
         elif sampler_type == "ode":                                      # legacy model.py:384-385
-            sample, nfe = self.get_ode_sampler(Y, N=N, conditioning=[Y], noise=noise, seed=seed, **kwargs)()
+            sample, nfe = self.get_ode_sampler(Y, N=N, conditioning=[Y], noise=noise, seed=seed, **item_kw, **kwargs)()
         else:
             raise NotImplementedError(f"{sampler_type} is not a valid sampler type!")
         if return_stft:

@@ -37,12 +37,15 @@ def _sde_engine(sde, device):
 
 def get_pc_sampler(predictor_name, corrector_name, sde, score_fn, y, denoise=True, eps=3e-2, snr=0.1,
                    corrector_steps=1, probability_flow: bool = False, conditioning=None, intermediate=False,
-                   noise=None, seed=0, use_graph=True, **kwargs):
+                   noise=None, seed=0, use_graph=True, per_item=False, item_seeds=None, **kwargs):
     """Returns ``pc_sampler() -> (x_result, nfe)``.
 
     Extra keyword arguments over the reference: ``noise`` (complex64 [n_draws, *y.shape], consumed prior-first
     then per step corrector draws followed by the predictor draw) for bit-reproducible parity runs, ``seed`` for
-    the device Philox generator, ``use_graph``.
+    the device Philox generator, ``use_graph``.  ``per_item`` (default off): the batch-invariant form of the fused loop
+    (``use_sample_items``) - item b draws from its own Philox stream seeded ``item_seeds[b]`` (default
+    ``seeding.item_seed(seed, b)``) and takes its own Langevin step, so that at equal T' its result does not depend on
+    the batch it rides in; at B > 1 this is the reference run per file (batch size 1), not the reference at batch size B.
     """
     predictor_cls = PredictorRegistry.get_by_name(predictor_name)
     corrector_cls = CorrectorRegistry.get_by_name(corrector_name)
@@ -59,13 +62,31 @@ def get_pc_sampler(predictor_name, corrector_name, sde, score_fn, y, denoise=Tru
              and getattr(score_fn, "supports_fused_sampler", False)
              and conditioning is not None and len(conditioning) in (1, 2) and all(c.shape == y.shape for c in conditioning))
 
+    item_kw = {}
+    if per_item:
+        # the seam path below goes through use_sde_*, whose noise and Langevin step are those of the whole batch
+        if not builtin:
+            raise NotImplementedError(f"per_item sampling: predictor {predictor_name!r} / corrector {corrector_name!r} are not both "
+                                      "built-in fused ones; the loop driven through update_fn stays batch-coupled")
+        if not fused:
+            raise NotImplementedError("per_item sampling runs in the fused loop only (HIP-backed ScoreModel, the OUVE SDE, denoise=True, "
+                                      "no probability flow, conditioning of y's shape)")
+        if item_seeds is None:
+            from ...seeding import item_seeds as _derive
+            item_seeds = _derive(seed, y.shape[0])
+        if len(item_seeds) != y.shape[0]:
+            raise ValueError(f"item_seeds has {len(item_seeds)} entries for a batch of {y.shape[0]}")
+        item_kw = {"item_seeds": list(item_seeds)}
+    elif item_seeds is not None:
+        raise ValueError("item_seeds needs per_item=True")
+
     if fused:
         def pc_sampler():
             with torch.no_grad():
                 x = score_fn.fused_sample(y, N=sde.N, predictor=predictor_name, corrector=corrector_name,
                                           corrector_steps=corrector_steps, snr=snr, t_eps=eps, noise=noise, seed=seed,
                                           use_graph=use_graph, sde=sde, cond=conditioning[0],
-                                          cond2=conditioning[1] if len(conditioning) == 2 else None)
+                                          cond2=conditioning[1] if len(conditioning) == 2 else None, **item_kw)
             return x, sde.N * (corrector.n_steps + 1)
         return pc_sampler
 
@@ -108,7 +129,8 @@ _ODE_SOLVER_OPTIONS = ("first_step", "max_step", "max_nfe")
 
 
 def get_ode_sampler(sde, score_fn, y, inverse_scaler=None, denoise=True, rtol=1e-5, atol=1e-5, method="RK45", eps=3e-2,
-                    device="cuda", conditioning=None, noise=None, seed=0, minibatch=None, use_graph=True, **kwargs):
+                    device="cuda", conditioning=None, noise=None, seed=0, minibatch=None, use_graph=True, per_item=False,
+                    item_seeds=None, **kwargs):
     """Returns ``ode_sampler() -> (x, nfe)``: the probability-flow ODE of ``sde`` integrated from T = 1 down to ``eps`` by RK45
     (scipy's ``solve_ivp(method="RK45")``, reproduced on the device), then with ``denoise`` one noise-free reverse-diffusion step.
 
@@ -120,7 +142,9 @@ def get_ode_sampler(sde, score_fn, y, inverse_scaler=None, denoise=True, rtol=1e
     ``max_step``, and ``max_nfe`` (evaluations per group before the integration stops with status -2, default 10000).  ``device`` is
     accepted for the reference's signature: the sampler runs on ``y``'s device.  ``ode_sampler.stats`` holds NFE and status per group
     after a call (0: reached ``eps``; -1: scipy's step-size failure, the last accepted state is returned; -2: ``max_nfe``), and on the
-    seam path the accepted times (``solution.t``).
+    seam path the accepted times (``solution.t``).  ``per_item`` (default off): the prior of item b is draw 0 of its own Philox
+    stream (``item_seeds[b]``, default ``seeding.item_seed(seed, b)``), drawn with ``use_fill_noise_items`` and injected; needs
+    ``minibatch=1`` and the fused path.
     """
     if method != "RK45":
         raise NotImplementedError(f"get_ode_sampler: method={method!r} is not implemented (RK45 only)")
@@ -141,6 +165,22 @@ def get_ode_sampler(sde, score_fn, y, inverse_scaler=None, denoise=True, rtol=1e
     fused = (type(sde) is OUVESDE and getattr(score_fn, "supports_fused_sampler", False)
              and (conditioning is None or (len(conditioning) in (1, 2) and all(c.shape == y.shape for c in conditioning))))
 
+    item_kw = {}
+    if per_item:
+        if minibatch != 1:
+            raise ValueError(f"per_item ODE sampling needs minibatch=1, got {minibatch!r}: the items of a group share one step-size "
+                             "controller and one error norm, so an item's steps would depend on its companions")
+        if not fused:
+            raise NotImplementedError("per_item ODE sampling runs in the fused path only (HIP-backed ScoreModel and the OUVE SDE)")
+        if item_seeds is None:
+            from ...seeding import item_seeds as _derive
+            item_seeds = _derive(seed, y.shape[0])
+        if len(item_seeds) != y.shape[0]:
+            raise ValueError(f"item_seeds has {len(item_seeds)} entries for a batch of {y.shape[0]}")
+        item_kw = {"item_seeds": list(item_seeds)}
+    elif item_seeds is not None:
+        raise ValueError("item_seeds needs per_item=True")
+
     def _nfe(nfev):
         return nfev[0] if minibatch is None else list(nfev)
 
@@ -150,7 +190,7 @@ def get_ode_sampler(sde, score_fn, y, inverse_scaler=None, denoise=True, rtol=1e
                 cond = [None, None] if conditioning is None else list(conditioning) + [None]
                 x, nfev, status = score_fn.fused_sample_ode(y, N=sde.N, t_eps=eps, rtol=rtol, atol=atol, group=group, denoise=denoise,
                                                             noise=noise, seed=seed, use_graph=use_graph, sde=sde, cond=cond[0],
-                                                            cond2=cond[1], **opts)
+                                                            cond2=cond[1], **opts, **item_kw)
                 ode_sampler.stats = {"nfev": nfev, "status": status}
                 if inverse_scaler is not None:
                     x = inverse_scaler(x)
