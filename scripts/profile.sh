@@ -5,11 +5,13 @@
 #   round <tag>            bench lines (configs[1], [3], [4]) + rocprofv3 --kernel-trace --stats of the bench command and of
 #                          `bench.py --roofline-only` (one launch on the chip at a time: what roofline.avg_launch_ms must agree with)
 #   pmc <tag> [prec B T]   PMC passes (counters only, separate --pmc runs, --kernel-trace) of one score evaluation; then
-#                          `python scripts/pmc_to_json.py gpurun_out/<tag> conv_v4 profiles/<name>.json` (FETCH_SIZE x2 on gfx950)
+#                          `python scripts/pmc_to_json.py <output dir of the passes> Wide16x16 profiles/<name>.json` (FETCH_SIZE x2 on gfx950;
+#                          the filter is a substring of the kernel name: Wide16x16 for conv_v5 = conv_wide_kernel<use::Wide16x16, ...>,
+#                          Wide32x32 for conv_v4 = conv_wide_kernel<use::Wide32x32, ...>)
 #   power [opts] [iters]   socket power + shader clock once a second while the evaluation runs back to back
 #   train [fp32|bf16]      training-step timing + per-kernel statistics; `train-pmc <tag> [prec]` its PMC passes
 #   ab <libA.so> <libB.so> same-box A/B of library builds (scripts/ab_libs.py: harness timings, bit-identity, end to end)
-#   trace <lib> <wg> <case> cycle stamps of one workgroup of conv_v4 (trace build: make EXTRA=-DUSE_HIP_TRACE_BUILD)
+#   trace <lib> <wg> <case> cycle stamps of one workgroup of conv_v4 / conv_v5 (trace build: make EXTRA=-DUSE_HIP_TRACE_BUILD)
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 WHAT=${1:-round}; shift
 PMC_SETS=(

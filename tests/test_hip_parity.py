@@ -75,7 +75,7 @@ def test_score_matches_reference_golden(golden_dir, engines, prec, tol):
 
 @pytest.mark.parametrize("prec,tol", [("fp32", 5e-4), ("bf16", lp.fwd_bound("bf16")), ("fp16", lp.fwd_bound("fp16"))])   # 16-bit: the reference's own autocast error (tests/lowprec.py)
 def test_score_golden_with_wide_tile_kernel_forced(golden_dir, engines, prec, tol):
-    """conv_v4_kernel is normally reserved for maps of >= 128 workgroups per image; force it onto the golden-vector shapes."""
+    """conv_wide_kernel (conv_v4 / conv_v5) is normally reserved for maps of >= 128 workgroups per image; force it onto the golden-vector shapes."""
     from universal_speech_enhancement_amd.hip_engine import set_option
     g = dict(np.load(os.path.join(golden_dir, "forward_large.npz")))
     x = torch.from_numpy(g["x"]).cuda()
@@ -1008,8 +1008,8 @@ def test_partial_totals_and_atomic_totals_give_the_same_score_bit_for_bit(engine
 
 @pytest.mark.parametrize("prec", ["bf16", "fp16"])
 def test_conv_v5_and_conv_v4_give_the_same_score_bit_for_bit(engines, prec):
-    """Round 6: the large-map convolution on v_mfma_f32_16x16x32 (conv_v5_kernel: less energy per FLOP, the default for 16-bit storage) against the
-    same pipeline on v_mfma_f32_32x32x16 (conv_v4_kernel, use_set_option("conv_v5", 0)).  Same products, same fp32 accumulation per 32-channel chunk
+    """Round 6: the large-map convolution on v_mfma_f32_16x16x32 (conv_wide_kernel<Wide16x16>, conv_v5: less energy per FLOP, the default for 16-bit storage) against the
+    same pipeline on v_mfma_f32_32x32x16 (conv_wide_kernel<Wide32x32>, conv_v4: use_set_option("conv_v5", 0)).  Same products, same fp32 accumulation per 32-channel chunk
     and tap, same epilogue arithmetic: the whole evaluation agrees bit for bit (as the single-convolution harness does on random data, maxdiff 0).
     T' = 128 at B = 5 (3 + 2 sub-batches): the 512 x 128 and 256 x 64 levels run on the kernel, with residuals, fused shortcuts, concatenated
     inputs and the Combine epilogue; the wide-tile threshold lowered to also put the smaller maps on it."""

@@ -1,4 +1,4 @@
-// conv_v4_kernel: the wide-tile variant of conv_v2_kernel for the large feature maps.  Same arithmetic, schedule idea
+// conv_wide_kernel (conv_v4 / conv_v5): the wide-tile variant of conv_v2_kernel for the large feature maps.  Same arithmetic, schedule idea
 // and argument struct; different geometry, chosen to cut the per-MFMA cost of everything that is not an MFMA:
 //
 //   * one workgroup = 8 waves computes a 16-row x 32-column pixel tile x 128 output channels; every wave owns two full
@@ -14,6 +14,27 @@
 // Ping-pong as in conv_v2: waves 0-3 and 4-7 (one of each per SIMD) alternate between an "LDS phase" (12 fragment
 // reads, the staging stores and global-load issue) and an "MFMA phase" (16 MFMAs with the GroupNorm+SiLU transform of
 // one halo piece on the VALU in their shadow), one s_barrier per phase.
+//
+// One kernel template, conv_wide_kernel, on two MFMA shapes (its leading template argument; launch_conv_v4 / launch_conv_v5):
+//   Wide32x32 ("conv_v4"): everything above, v_mfma_f32_32x32x16 for the 16-bit types and v_mfma_f32_32x32x2f32 for fp32 storage.
+//   Wide16x16 ("conv_v5", round 6; 16-bit storage only, the default there): same tile, same pipeline, same epilogue, same arguments on
+//   v_mfma_f32_16x16x32_{bf16,f16}.  Why: under a convolution's matrix duty both shapes run at the same clock, and the 16x16x32 shape
+//   draws 0.16 pJ less per FLOP (scripts/microbench/mfma_dtype_power, profiles/r6_mfma_shape_power.txt: at ~37 % duty and 2.39 GHz
+//   1 036 W vs 888 W for the same 0.9 PFLOP/s; back to back it holds 2.06 GHz where the 32x32x16 stream is held at 1.75 GHz) - it moves
+//   half the accumulator registers per FLOP.  The evaluation is limited by the package power limit, so joules are time.
+// What Wide16x16 changes (each an `if constexpr (S16)` or a member of the shape type in the kernel, nothing else differs):
+//   * a (32 pixel x 32 channel, K = 32) product = four 16x16x32 MFMAs (pixel half a, channel half b), K = 32 in ONE instruction:
+//     32 MFMAs per (tap, chunk) phase and wave instead of 16, the same 12 fragment reads (A: tile row i x pixel half a, B: block j x half b);
+//   * lane -> (row m = lane & 15, 8-channel k group g = lane >> 4).  Row m of a fragment is physical row pi(m) of its group of 16 (pixels of
+//     A, output channels of B), pi = (0-3, 8-15, 4-7): the 16-lane groups of a ds_read_b128 - lanes {0-3, 12-15, 20-27} and so on - then
+//     read rows 0-7 with k group g and rows 8-15 with g ^ 1, and with the halo's slot swizzle s(P) = 2 ((P >> 2) & 1) (Wide32x32: (P >> 2) & 3)
+//     they hit 16 distinct bank quads for every column shift of a tap; the weight slab keeps the blob's swizzle (row >> 2) & 3, which
+//     is conflict-free for the unshifted rows of B;
+//   * accumulator (i, a, j, b) register r of lane l: pixel column 16 a + 4 Q(l >> 4) + r of tile row i, Q = (0, 2, 3, 1); channel
+//     16 (2 j + b) + pi(l & 15).  The epilogue stages half rounds (i, a) exactly as Wide32x32 does, with its own row layout (v5_stage8).
+// The whole body stays inside the __global__ function: a shared __device__ body is optimised on its own before it is inlined, which changed
+// every kernel and spilled the fp32 ones; a branch discarded at instantiation never reaches the optimiser (scripts/kernel_isa_diff.py,
+// profiles/conv_wide_merge_isa.txt: every instantiation is instruction for instruction what the two separate kernels were).
 #include "use_kernels.h"
 #include "use_device.h"
 
@@ -45,9 +66,121 @@ constexpr int V4_BN = 128;
 #define V4_DEAD_LOADS 1
 #endif
 
-template <typename TIN, typename TOUT, int CK, bool ACT, int EPI>
-__global__ __launch_bounds__(512) void conv_v4_kernel(ConvArgs p) {
-    typedef Mfma<TIN> MF;
+// ---- Wide16x16's own pieces (Wide32x32's - Mfma, XfAsm / mfma16_with_transform, v4_stage8 - are conv_v2's too: use_device.h) -----------------
+DEVI int v5_pi(int m) { return m < 4 ? m : m < 12 ? m + 4 : m - 8; }   // logical MFMA row / column -> physical row of its group of 16
+#define V5_SW(P) ((((P) >> 2) & 1) << 1)                               /* slot swizzle of halo pixel P: piece q at slot q ^ V5_SW(P) */
+
+// Epilogue staging of one channel block J of a half round: accumulators (., ., J, 0) and (., ., J, 1), four registers each = rows (jb, r),
+// jb = 2 J + b, at float (jb * 4 + r) * 64 + 8 jb of the wave's region (ds_write_addtid_b32: M0 + offset + 4 lane, see v4_stage8)
+constexpr int v5_stg_off(int jb, int r) { return ((jb * 4 + r) * 64 + 8 * jb) * 4; }
+constexpr int V5_STG_BYTES = 8448;                           // (31 * 64 + 56 + 64) floats = 8 416 B, rounded up to 64 bytes
+template <int J>
+DEVI void v5_stage8(unsigned lds_base, const f32x4& x0, const f32x4& x1) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %[keep], m0\n\ts_mov_b32 m0, %[base]\n\ts_nop 0\n\t"
+                 "ds_write_addtid_b32 %[a0] offset:%[o0]\n\tds_write_addtid_b32 %[a1] offset:%[o1]\n\tds_write_addtid_b32 %[a2] offset:%[o2]\n\t"
+                 "ds_write_addtid_b32 %[a3] offset:%[o3]\n\tds_write_addtid_b32 %[a4] offset:%[o4]\n\tds_write_addtid_b32 %[a5] offset:%[o5]\n\t"
+                 "ds_write_addtid_b32 %[a6] offset:%[o6]\n\tds_write_addtid_b32 %[a7] offset:%[o7]\n\t"
+                 "s_mov_b32 m0, %[keep]"
+                 : [keep] "=&s"(keep)
+                 : [base] "s"(lds_base), [a0] "v"(x0[0]), [a1] "v"(x0[1]), [a2] "v"(x0[2]), [a3] "v"(x0[3]), [a4] "v"(x1[0]), [a5] "v"(x1[1]), [a6] "v"(x1[2]), [a7] "v"(x1[3]),
+                   [o0] "n"(v5_stg_off(2 * J, 0)), [o1] "n"(v5_stg_off(2 * J, 1)), [o2] "n"(v5_stg_off(2 * J, 2)), [o3] "n"(v5_stg_off(2 * J, 3)),
+                   [o4] "n"(v5_stg_off(2 * J + 1, 0)), [o5] "n"(v5_stg_off(2 * J + 1, 1)), [o6] "n"(v5_stg_off(2 * J + 1, 2)), [o7] "n"(v5_stg_off(2 * J + 1, 3))
+                 : "memory");
+}
+
+// 32 MFMAs (acc[i][a][j][b] += A[i][a] B[j][b], g = (2 i + a) * 8 + 2 j + b) carrying the GroupNorm + SiLU transform of one 16-byte halo piece, as
+// asm statements (conv_v4's XfAsm, use_device.h, re-cut for the 16-cycle instruction: the first eight MFMAs bare - the piece arrives late -,
+// then per dword six MFMAs with the 15-instruction chain 3 2 3 2 3 2 in their gaps; the chain and its order per element are stage_transform's:
+// bit-identical results).  Hazards inside the asm: a transcendental's result is read two instructions later; every accumulator is used once.
+template <typename TIN> struct V5Xf;
+#define USE_V5XF(T, MFMA, LO, HI, PK)                                                                                    \
+    template <> struct V5Xf<T> {                                                                                         \
+        typedef typename Mfma<T>::frag frag;                                                                             \
+        DEVI static void bare8(f32x4& c0, f32x4& c1, f32x4& c2, f32x4& c3, f32x4& c4, f32x4& c5, f32x4& c6, f32x4& c7, const frag& a,       \
+                               const frag& b0, const frag& b1, const frag& b2, const frag& b3, const frag& b4, const frag& b5, const frag& b6, const frag& b7) { \
+            asm volatile(MFMA " %0, %8, %9, %0\n\t" MFMA " %1, %8, %10, %1\n\t" MFMA " %2, %8, %11, %2\n\t" MFMA " %3, %8, %12, %3\n\t" \
+                         MFMA " %4, %8, %13, %4\n\t" MFMA " %5, %8, %14, %5\n\t" MFMA " %6, %8, %15, %6\n\t" MFMA " %7, %8, %16, %7"    \
+                         : "+v"(c0), "+v"(c1), "+v"(c2), "+v"(c3), "+v"(c4), "+v"(c5), "+v"(c6), "+v"(c7)                         \
+                         : "v"(a), "v"(b0), "v"(b1), "v"(b2), "v"(b3), "v"(b4), "v"(b5), "v"(b6), "v"(b7));                        \
+        }                                                                                                                \
+        /* six MFMAs (accumulator ck with operands (ak, bk)) + the transform of dword d (in place) */                     \
+        template <bool ACT>                                                                                              \
+        DEVI static void dword6(f32x4& c0, f32x4& c1, f32x4& c2, f32x4& c3, f32x4& c4, f32x4& c5, const frag& a0, const frag& a1, const frag& a2,    \
+                                const frag& a3, const frag& a4, const frag& a5, const frag& b0, const frag& b1, const frag& b2, const frag& b3,     \
+                                const frag& b4, const frag& b5, unsigned& d, float al, float bl, float ah, float bh) {   \
+            float xl, xh, ul, uh;                                                                                        \
+            if (ACT)                                                                                                     \
+                asm volatile(MFMA " %0, %11, %17, %0\n\t"                                                                \
+                             LO("%7", "%6") "\n\t" HI("%8", "%6") "\n\tv_fma_f32 %9, %7, %23, %24\n\t"                    \
+                             MFMA " %1, %12, %18, %1\n\t"                                                                \
+                             "v_fma_f32 %10, %8, %25, %26\n\tv_mul_f32 %7, 0xbfb8aa3b, %9\n\t"                            \
+                             MFMA " %2, %13, %19, %2\n\t"                                                                \
+                             "v_mul_f32 %8, 0xbfb8aa3b, %10\n\tv_exp_f32 %7, %7\n\tv_exp_f32 %8, %8\n\t"                  \
+                             MFMA " %3, %14, %20, %3\n\t"                                                                \
+                             "v_add_f32 %7, 1.0, %7\n\tv_add_f32 %8, 1.0, %8\n\t"                                        \
+                             MFMA " %4, %15, %21, %4\n\t"                                                                \
+                             "v_rcp_f32 %7, %7\n\tv_rcp_f32 %8, %8\n\tv_mul_f32 %9, %9, %7\n\t"                           \
+                             MFMA " %5, %16, %22, %5\n\t"                                                                \
+                             "v_mul_f32 %10, %10, %8\n\t" PK("%6", "%9", "%10")                                          \
+                             : "+v"(c0), "+v"(c1), "+v"(c2), "+v"(c3), "+v"(c4), "+v"(c5), "+v"(d), "=&v"(xl), "=&v"(xh), "=&v"(ul), "=&v"(uh) \
+                             : "v"(a0), "v"(a1), "v"(a2), "v"(a3), "v"(a4), "v"(a5), "v"(b0), "v"(b1), "v"(b2), "v"(b3), "v"(b4), "v"(b5),   \
+                               "v"(al), "v"(bl), "v"(ah), "v"(bh));                                                      \
+            else                                                                                                         \
+                asm volatile(MFMA " %0, %11, %17, %0\n\t"                                                                \
+                             LO("%7", "%6") "\n\t" HI("%8", "%6") "\n\t"                                                 \
+                             MFMA " %1, %12, %18, %1\n\t"                                                                \
+                             "v_fma_f32 %9, %7, %23, %24\n\tv_fma_f32 %10, %8, %25, %26\n\t"                              \
+                             MFMA " %2, %13, %19, %2\n\t"                                                                \
+                             MFMA " %3, %14, %20, %3\n\t"                                                                \
+                             PK("%6", "%9", "%10") "\n\t"                                                                \
+                             MFMA " %4, %15, %21, %4\n\t"                                                                \
+                             MFMA " %5, %16, %22, %5"                                                                    \
+                             : "+v"(c0), "+v"(c1), "+v"(c2), "+v"(c3), "+v"(c4), "+v"(c5), "+v"(d), "=&v"(xl), "=&v"(xh), "=&v"(ul), "=&v"(uh) \
+                             : "v"(a0), "v"(a1), "v"(a2), "v"(a3), "v"(a4), "v"(a5), "v"(b0), "v"(b1), "v"(b2), "v"(b3), "v"(b4), "v"(b5),   \
+                               "v"(al), "v"(bl), "v"(ah), "v"(bh));                                                      \
+        }                                                                                                                \
+    };
+USE_V5XF(__bf16, "v_mfma_f32_16x16x32_bf16", USE_XF_BF16_LO, USE_XF_BF16_HI, USE_XF_BF16_PK)
+USE_V5XF(_Float16, "v_mfma_f32_16x16x32_f16", USE_XF_F16_LO, USE_XF_F16_HI, USE_XF_F16_PK)
+#undef USE_V5XF
+
+template <typename TIN, bool ACT, typename ACC, typename AF, typename BF>
+DEVI uint4 v5_mfma32_with_transform(ACC& acc, const AF& af, const BF& bf, const uint4 raw, const float (&ca)[8], const float (&cb)[8]) {
+    typedef V5Xf<TIN> X;
+    unsigned d[4] = {raw.x, raw.y, raw.z, raw.w};
+    // g = (2 i + a) * 8 + (2 j + b): accumulator acc[i][a][j][b], operands af[i][a], bf[j][b]
+#define V5_C(G) acc[((G) >> 4) & 1][((G) >> 3) & 1][((G) >> 1) & 3][(G)&1]
+#define V5_A(G) af[((G) >> 4) & 1][((G) >> 3) & 1]
+#define V5_B(G) bf[((G) >> 1) & 3][(G)&1]
+    X::bare8(V5_C(0), V5_C(1), V5_C(2), V5_C(3), V5_C(4), V5_C(5), V5_C(6), V5_C(7), V5_A(0), V5_B(0), V5_B(1), V5_B(2), V5_B(3), V5_B(4), V5_B(5), V5_B(6), V5_B(7));
+#define V5_D6(G0, K)                                                                                                                          \
+    X::template dword6<ACT>(V5_C(G0), V5_C(G0 + 1), V5_C(G0 + 2), V5_C(G0 + 3), V5_C(G0 + 4), V5_C(G0 + 5), V5_A(G0), V5_A(G0 + 1), V5_A(G0 + 2), V5_A(G0 + 3), \
+                            V5_A(G0 + 4), V5_A(G0 + 5), V5_B(G0), V5_B(G0 + 1), V5_B(G0 + 2), V5_B(G0 + 3), V5_B(G0 + 4), V5_B(G0 + 5), d[K], ca[2 * K],      \
+                            cb[2 * K], ca[2 * K + 1], cb[2 * K + 1]);
+    V5_D6(8, 0) V5_D6(14, 1) V5_D6(20, 2) V5_D6(26, 3)
+#undef V5_D6
+#undef V5_C
+#undef V5_A
+#undef V5_B
+    return make_uint4(d[0], d[1], d[2], d[3]);
+}
+
+// MFMA shape of conv_wide_kernel: register-tile types of a wave (2 tile rows x 4 channel blocks of 32; F = fragment type, K = MFMA k steps per chunk)
+struct Wide32x32 {                                           // "conv_v4": one 32x32 MFMA per (tile row, channel block, k step)
+    static constexpr int MN = 32;
+    template <typename F, int K> struct Tile { typedef f32x16 acc_t[2][4]; typedef F af_t[K][2]; typedef F bf_t[K][4]; };
+};
+struct Wide16x16 {                                           // "conv_v5": four 16x16x32 MFMAs (pixel half a, channel half b), K = 32 in one
+    static constexpr int MN = 16;
+    template <typename F, int K> struct Tile { typedef f32x4 acc_t[2][2][4][2]; typedef F af_t[2][2]; typedef F bf_t[4][2]; };
+};
+
+template <typename SHAPE, typename TIN, typename TOUT, int CK, bool ACT, int EPI>
+__global__ __launch_bounds__(512) void conv_wide_kernel(ConvArgs p) {
+    typedef Mfma<TIN> MF;                                    // (Wide16x16: fragment type and loads only; its MFMAs are V5Xf's)
+    constexpr bool S16 = SHAPE::MN == 16;
+    static_assert(!S16 || (sizeof(TIN) == 2 && sizeof(TOUT) == 2 && CK == 32 && EPI >= 0), "Wide16x16: 16-bit storage, 32-channel chunks, specialised epilogues");
     constexpr int VEC = 16 / sizeof(TIN);
     constexpr int PARTS = CK / VEC;                          // 16-byte pieces per pixel row of a chunk (4)
     constexpr int PXB = CK * (int)sizeof(TIN);               // 64 bytes per pixel row of a chunk (and per weight row of a slab)
@@ -88,10 +221,13 @@ __global__ __launch_bounds__(512) void conv_v4_kernel(ConvArgs p) {
     // launch run in lock step and every tile's 128 KB of output stores meet the memory system in the same few microseconds: with up to 32 k
     // cycles of spread a launch repeated back to back is 3 % shorter, but in the three-stream evaluation, where other launches already
     // scramble the phases, every cycle of delay is lost: +2 % at 32 k.  profiles/r6_conv_v4_epilogue_ab.txt.  Not kept.)
-    float addv[TN];                                          // bias + time-embedding bias of this lane's channels
+    // this lane's row of an MFMA operand / column of its result (pixel of A, output channel of B and D): lane & 31, or the physical row pi(lane & 15)
+    const int lrow = S16 ? v5_pi(lane & 15) : lane & 31;
+    constexpr int NADD = TN * 32 / SHAPE::MN;
+    float addv[NADD];                                        // bias + time-embedding bias of this lane's channels: MN j + lrow
 #pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int co = n0 + j * 32 + (lane & 31);
+    for (int j = 0; j < NADD; ++j) {
+        const int co = n0 + j * SHAPE::MN + lrow;
         float add = 0.f;
         if (co < p.Cout) {
             if (p.bias) add += p.bias[co];
@@ -127,23 +263,27 @@ __global__ __launch_bounds__(512) void conv_v4_kernel(ConvArgs p) {
 #define V4_TRACE_FORCE(R)
 #endif
     V4_STAMP(1)
-    f32x16 acc[TM][TN];
+    typedef typename SHAPE::template Tile<typename MF::frag, KSTEPS> RT;
+    typename RT::acc_t acc;                                  // Wide32x32 [tile row i][channel block j]; Wide16x16 [i][pixel half a][j][half b]
 
     V4_STAMP(11)
-    // LDS byte offsets of this lane's fragments.  k index of a lane's first element inside the 64-byte row: (kk, h = lane >> 5) ->
-    // piece q and offset o inside it: 16-bit types q = 2 kk + h, o = 0 (8 elements = one piece per lane); fp32 q = kk >> 1,
-    // o = 4 ((kk & 1) 2 + h).  Address = row * 64 + ((q ^ swz) << 4) + o = (lane-constant base) ^ KX(kk) + KO(kk).
+    // LDS byte offsets of this lane's fragments: row lrow, k group h = lane / MN.  Wide32x32: k index of a lane's first element inside the
+    // 64-byte row: (kk, h) -> piece q and offset o inside it: 16-bit types q = 2 kk + h, o = 0 (8 elements = one piece per lane); fp32
+    // q = kk >> 1, o = 4 ((kk & 1) 2 + h).  Address = row * 64 + ((q ^ swz) << 4) + o = (lane-constant base) ^ KX(kk) + KO(kk).
+    // Wide16x16: piece q = h of the row, no k steps.  A: pixel column lrow + dx of tile row 2 wave (+ 16 a columns = + 1024 B, + i / dy rows
+    // = + HPITCH: immediates); B: weight row 16 (2 j + b) + lrow (+ (2 j + b) * 1024 B).
     constexpr bool W16 = sizeof(TIN) == 2;
-    const int h_ = lane >> 5, col_ = lane & 31;
+    const int h_ = lane >> (S16 ? 4 : 5);
+#define V4_SW(P) (S16 ? V5_SW(P) : ((P) >> 2) & 3)           /* slot swizzle of halo pixel P: piece q at slot q ^ V4_SW(P) */
 #define V4_KX(KK) (W16 ? ((KK) * 2) << 4 : ((KK) >> 1) << 4)
 #define V4_KO(KK) (W16 ? 0 : ((KK)&1) * 8)
-    int a_dx[3];                                             // per column shift dx of the tap: pixel (row 2 wave, column col_ + dx)
+    int a_dx[3];                                             // per column shift dx of the tap: pixel (row 2 wave, column lrow + dx)
 #pragma unroll
     for (int dx = 0; dx < 3; ++dx) {
-        const int P = col_ + dx;                             // (+ row * 48: does not change (P >> 2) & 3)
-        a_dx[dx] = wave * 2 * HPITCH + P * PXB + (((W16 ? h_ : 0) ^ ((P >> 2) & 3)) << 4) + (W16 ? 0 : h_ * 4);
+        const int P = lrow + dx;                             // (+ 16 a, + row * 48: do not change V4_SW(P))
+        a_dx[dx] = wave * 2 * HPITCH + P * PXB + (((W16 ? h_ : 0) ^ V4_SW(P)) << 4) + (W16 ? 0 : h_ * 4);
     }
-    const int b_0 = 2 * HALO_BYTES + col_ * PXB + (((W16 ? h_ : 0) ^ ((col_ >> 2) & 3)) << 4) + (W16 ? 0 : h_ * 4);   // weight row j * 32 + col_: + j * 2048
+    const int b_0 = 2 * HALO_BYTES + lrow * PXB + (((W16 ? h_ : 0) ^ ((lrow >> 2) & 3)) << 4) + (W16 ? 0 : h_ * 4);   // weight row j * 32 + lrow: + j * 2048
 
     // ---- segment-0 halo pieces: this thread's piece j (0..4) of every chunk --------------------------------------------
     // Per piece: the pixel offset of its global load and the byte offset of its LDS row - kept in two LDS tables (read back by the
@@ -201,7 +341,7 @@ __global__ __launch_bounds__(512) void conv_v4_kernel(ConvArgs p) {
     auto piece1_dst = [&](int q, int hb) -> int {
         const int pix = (q * 512 + tid) / PARTS;
         const int P = ((pix >> 5) + 1) * HROW + (pix & 31) + 1;
-        return hb * HALO_BYTES + P * PXB + ((part ^ ((P >> 2) & 3)) << 4);
+        return hb * HALO_BYTES + P * PXB + ((part ^ V4_SW(P)) << 4);
     };
 
     // ---- weights: slab-major copy [tap][chunk][cout_pad][CK]; one 16-byte piece per thread per slab ----------------------
@@ -266,7 +406,7 @@ __global__ __launch_bounds__(512) void conv_v4_kernel(ConvArgs p) {
 #endif
             raw[j] = (V4_ABL & 32) ? zero4 : src_ld0(0, pp);
             const int P = hy * HROW + hx;
-            slot[j] = P * PXB + ((part ^ ((P >> 2) & 3)) << 4);
+            slot[j] = P * PXB + ((part ^ V4_SW(P)) << 4);
             ppv[j] = pp; inbv[j] = inb;
             if (idx >= NPIECE) slot[j] = -1;
         }
@@ -284,11 +424,14 @@ __global__ __launch_bounds__(512) void conv_v4_kernel(ConvArgs p) {
             dst_tab[idx] = slot[j];
         }
 #pragma unroll
-        for (int i = 0; i < TM; ++i)
+        for (int i = 0; i < TM; ++i)                         // bias + time-embedding bias: the sum starts there
 #pragma unroll
             for (int j = 0; j < TN; ++j)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = addv[j];   // bias + time-embedding bias: the sum starts there
+                for (int r = 0; r < 16; ++r) {
+                    if constexpr (S16) acc[i][(r >> 3) & 1][j][(r >> 2) & 1][r & 3] = addv[2 * j + ((r >> 2) & 1)];
+                    else acc[i][j][r] = addv[j];
+                }
         if (tid < Ctot) coef_lds[tid] = cfv;
         V4_STAMP(14)
         __syncthreads();                                     // coef_lds complete
@@ -301,9 +444,9 @@ __global__ __launch_bounds__(512) void conv_v4_kernel(ConvArgs p) {
             *reinterpret_cast<uint4*>(smem + slot[j]) = (V4_ABL & 32) ? raw[j] : stage_transform<TIN, ACT>(raw[j], 0xffffffffu, ca, cb);
     }
 
-    typename MF::frag af[KSTEPS][TM], bf[KSTEPS][TN];
+    typename RT::af_t af; typename RT::bf_t bf;              // Wide32x32 af[k step][i], bf[k step][j]; Wide16x16 af[i][a], bf[j][b]
     int dst_ = 0;                                            // LDS address of the piece the next MFMA phase transforms
-    uint4 tkeep = zero4; int dkeep = 0;                      // (ablation 512 only)
+    uint4 tkeep = zero4; int dkeep = 0;                      // (ablation 512 only: Wide32x32)
 #ifdef USE_HIP_SETPRIO
 #define V4_SETPRIO(N) __builtin_amdgcn_s_setprio(N);
 #else
@@ -323,6 +466,22 @@ __global__ __launch_bounds__(512) void conv_v4_kernel(ConvArgs p) {
 #define V4_LD_PHASE(T) (V4_STG && (T) >= V4_P0 && (T) < PIECE_ITERS + V4_P0)            /* LDS(T) issues the load of piece T - V4_P0 */
 #define V4_XF_PHASE(T) (V4_STG && (T) >= V4_P0 + 2 && (T) < PIECE_ITERS + V4_P0 + 2)   /* MFMA(T) carries the transform of piece T - V4_P0 - 2 */
 #define V4_XF_IDX(T) (V4_XF_PHASE(T) ? (T) - V4_P0 - 2 : 0)
+    // the 12 fragment reads of a (tap, chunk): A from the halo rows at HA_ with column shift DX, B from the slab at WB_
+#define V4_LD_FRAGS(HA_, WB_, DX, GUARD)                                                                             \
+    if constexpr (S16) {                                                                                             \
+        _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                               \
+            _Pragma("unroll") for (int a = 0; a < 2; ++a) af[i][a] = MF::ld((HA_) + a_dx[DX] + i * HPITCH + a * 16 * PXB); \
+        _Pragma("unroll") for (int j = 0; j < TN; ++j)                                                               \
+            _Pragma("unroll") for (int bb = 0; bb < 2; ++bb) bf[j][bb] = MF::ld((WB_) + b_0 + (2 * j + bb) * 16 * PXB); \
+    } else {                                                                                                         \
+        _Pragma("unroll") for (int kk = 0; kk < KSTEPS; ++kk) {                                                      \
+            int ak_ = a_dx[DX], bk_ = b_0;                                                                           \
+            if ((GUARD) && !W16) asm volatile("" : "+v"(ak_), "+v"(bk_));   /* fp32: 4 XOR variants x 4 bases hoisted out of the loop spill */ \
+            ak_ ^= V4_KX(kk); bk_ ^= V4_KX(kk);                                                                      \
+            _Pragma("unroll") for (int i = 0; i < TM; ++i) af[kk][i] = MF::ld((HA_) + ak_ + i * HPITCH + V4_KO(kk)); \
+            _Pragma("unroll") for (int j = 0; j < TN; ++j) bf[kk][j] = MF::ld((WB_) + bk_ + j * 32 * PXB + V4_KO(kk)); \
+        }                                                                                                            \
+    }
 #define V4_LDS(CC, T)                                                                                                \
     {                                                                                                                \
         const int cc_ = (CC);                                                                                        \
@@ -335,17 +494,10 @@ __global__ __launch_bounds__(512) void conv_v4_kernel(ConvArgs p) {
         {                                                                                                            \
             const char* ha_ = smem + par_ * HALO_BYTES + ((T) / 3) * HPITCH;                                         \
             const char* wbuf_ = smem + (par_ ^ ((T)&1)) * W_BYTES;                                                   \
-            if (!(V4_ABL & 8) || ((CC) == 0 && (T) == 0))                                                            \
-            _Pragma("unroll") for (int kk = 0; kk < KSTEPS; ++kk) {                                                  \
-                int ak_ = a_dx[(T) % 3], bk_ = b_0;                                                                  \
-                if (!W16) asm volatile("" : "+v"(ak_), "+v"(bk_));   /* fp32: 4 XOR variants x 4 bases hoisted out of the loop spill */ \
-                ak_ ^= V4_KX(kk); bk_ ^= V4_KX(kk);                                                                  \
-                _Pragma("unroll") for (int i = 0; i < TM; ++i) af[kk][i] = MF::ld(ha_ + ak_ + i * HPITCH + V4_KO(kk)); \
-                _Pragma("unroll") for (int j = 0; j < TN; ++j) bf[kk][j] = MF::ld(wbuf_ + bk_ + j * 32 * PXB + V4_KO(kk)); \
-            }                                                                                                        \
+            if (!(V4_ABL & 8) || ((CC) == 0 && (T) == 0)) { V4_LD_FRAGS(ha_, wbuf_, (T) % 3, true) }                 \
         }                                                                                                            \
         __builtin_amdgcn_sched_barrier(0);                                                                           \
-        if ((V4_ABL & 512) && (T) >= 3 + V4_P0 && (T) < PIECE_ITERS + 3 + V4_P0) *reinterpret_cast<uint4*>(smem + dkeep) = tkeep;    \
+        if (!S16 && (V4_ABL & 512) && (T) >= 3 + V4_P0 && (T) < PIECE_ITERS + 3 + V4_P0) *reinterpret_cast<uint4*>(smem + dkeep) = tkeep;    \
         if (V4_XF_PHASE(T)) dst_ += (par_ ^ 1) * HALO_BYTES; /* where MFMA(T) puts its transformed piece */          \
         if ((V4_ABL & 256) && V4_XF_PHASE(T)) dst_ = (par_ ^ 1) * HALO_BYTES + tid * 16;                             \
         if (!(V4_ABL & 4)) {                                                                                         \
@@ -358,37 +510,46 @@ __global__ __launch_bounds__(512) void conv_v4_kernel(ConvArgs p) {
             hL[((T) - V4_P0) % 3] = src_ld0(cn_, pix_, V4_DEAD_LOADS ? (cc_ + 1 < nchunks) : 1);                                                         \
         }                                                                                                            \
     }
+    // the bare MFMAs of a (tap, chunk).  Wide16x16 as asm as well: through the builtin hipcc gives every 16x16x32 MFMA a fresh destination tuple -
+    // 79 spilled registers; the tied "+v" operands keep the accumulators in place
+#define V4_MMA_ALL()                                                                                                 \
+    if constexpr (S16) {                                                                                             \
+        _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                               \
+            _Pragma("unroll") for (int a = 0; a < 2; ++a)                                                            \
+                V5Xf<TIN>::bare8(acc[i][a][0][0], acc[i][a][0][1], acc[i][a][1][0], acc[i][a][1][1], acc[i][a][2][0], acc[i][a][2][1], acc[i][a][3][0], acc[i][a][3][1], \
+                                 af[i][a], bf[0][0], bf[0][1], bf[1][0], bf[1][1], bf[2][0], bf[2][1], bf[3][0], bf[3][1]); \
+    } else {                                                                                                         \
+        _Pragma("unroll") for (int kk = 0; kk < KSTEPS; ++kk)                                                        \
+            _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                           \
+                _Pragma("unroll") for (int j = 0; j < TN; ++j) acc[i][j] = MF::mma(af[kk][i], bf[kk][j], acc[i][j]); \
+    }
 #define V4_MFMA(CC, T)                                                                                               \
     {                                                                                                                \
         V4_SETPRIO(1)                                                                                                \
-        if constexpr (sizeof(TIN) == 2) {                    /* (fp32: stage_transform and sched_group_barrier below) */ \
-            if (V4_XF_PHASE(T)) {                            /* unconditional at run time: same basic block as the MFMAs */ \
-                /* 16 MFMAs, slice g of the GroupNorm + SiLU transform of one halo piece behind MFMA g, one asm statement */ \
-                /* each (use_device.h, XfAsm: left to itself hipcc runs the transform with the matrix pipe idle)          */ \
-                V4_PSTAMP_C(CC, 300 + (T))                        /* trace builds: 3xx -> 4xx = the exposed wait for the halo piece */ \
-                V4_TRACE_FORCE(hL[V4_XF_IDX(T) % 3])                                                 \
-                V4_PSTAMP_C(CC, 400 + (T))                                                                               \
+        if constexpr (sizeof(TIN) == 2) { /* (fp32: stage_transform and sched_group_barrier below) */                \
+            if (V4_XF_PHASE(T)) { /* unconditional at run time: same basic block as the MFMAs */                     \
+                /* the MFMAs with the GroupNorm + SiLU transform of one halo piece in their gaps, as asm statements (XfAsm in use_device.h, \
+                   V5Xf above): left to itself hipcc runs the transform with the matrix pipe idle */                 \
+                V4_PSTAMP_C(CC, 300 + (T)) /* trace builds: 3xx -> 4xx = the exposed wait for the halo piece */      \
+                V4_TRACE_FORCE(hL[V4_XF_IDX(T) % 3])                                                                 \
+                V4_PSTAMP_C(CC, 400 + (T))                                                                           \
                 if (V4_ABL & 1) {                                                                                    \
-                    _Pragma("unroll") for (int kk = 0; kk < KSTEPS; ++kk)                                            \
-                        _Pragma("unroll") for (int i = 0; i < TM; ++i)                                               \
-                            _Pragma("unroll") for (int j = 0; j < TN; ++j) acc[i][j] = MF::mma(af[kk][i], bf[kk][j], acc[i][j]);  \
-                    if (!(V4_ABL & 64)) *reinterpret_cast<uint4*>(smem + dst_) = hL[V4_XF_IDX(T) % 3];  \
+                    V4_MMA_ALL()                                                                                     \
+                    if (!(V4_ABL & 64)) *reinterpret_cast<uint4*>(smem + dst_) = hL[V4_XF_IDX(T) % 3];               \
                 } else {                                                                                             \
-                const uint4 t0 = mfma16_with_transform<TIN, ACT>(acc, af, bf, hL[V4_XF_IDX(T) % 3], ca, cb); \
-                if (V4_ABL & 512) { tkeep = t0; asm volatile("" : "+v"(tkeep.x), "+v"(tkeep.y), "+v"(tkeep.z), "+v"(tkeep.w)); dkeep = dst_; } \
-                else if (!(V4_ABL & 64)) *reinterpret_cast<uint4*>(smem + dst_) = t0; /* the other halo buffer: nobody reads it during this chunk */ \
+                    uint4 t0;                                                                                        \
+                    if constexpr (S16) t0 = v5_mfma32_with_transform<TIN, ACT>(acc, af, bf, hL[V4_XF_IDX(T) % 3], ca, cb); \
+                    else t0 = mfma16_with_transform<TIN, ACT>(acc, af, bf, hL[V4_XF_IDX(T) % 3], ca, cb);            \
+                    if (!S16 && (V4_ABL & 512)) { tkeep = t0; asm volatile("" : "+v"(tkeep.x), "+v"(tkeep.y), "+v"(tkeep.z), "+v"(tkeep.w)); dkeep = dst_; } \
+                    else if (!(V4_ABL & 64)) *reinterpret_cast<uint4*>(smem + dst_) = t0; /* the other halo buffer: nobody reads it during this chunk */ \
                 }                                                                                                    \
             } else {                                                                                                 \
-                _Pragma("unroll") for (int kk = 0; kk < KSTEPS; ++kk)                                                \
-                    _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                   \
-                        _Pragma("unroll") for (int j = 0; j < TN; ++j) acc[i][j] = MF::mma(af[kk][i], bf[kk][j], acc[i][j]);  \
+                V4_MMA_ALL()                                                                                         \
             }                                                                                                        \
         } else {                                                                                                     \
-            _Pragma("unroll") for (int kk = 0; kk < KSTEPS; ++kk)                                                    \
-                _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                       \
-                    _Pragma("unroll") for (int j = 0; j < TN; ++j) acc[i][j] = MF::mma(af[kk][i], bf[kk][j], acc[i][j]);  \
+            V4_MMA_ALL()                                                                                             \
             if (V4_XF_PHASE(T)) {                                                                                    \
-                const uint4 t0 = stage_transform<TIN, ACT>(hL[V4_XF_IDX(T) % 3], 0xffffffffu, ca, cb); \
+                const uint4 t0 = stage_transform<TIN, ACT>(hL[V4_XF_IDX(T) % 3], 0xffffffffu, ca, cb);               \
                 *reinterpret_cast<uint4*>(smem + dst_) = t0;                                                         \
                 _Pragma("unroll") for (int g = 0; g < 16; ++g) {                                                     \
                     __builtin_amdgcn_sched_group_barrier(0x008, TM * TN * KSTEPS / 16, 0);   /* MFMA  */             \
@@ -472,7 +633,10 @@ __global__ __launch_bounds__(512) void conv_v4_kernel(ConvArgs p) {
 #pragma unroll
             for (int j = 0; j < TN; ++j)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) sum += acc[i][j][r];
+                for (int r = 0; r < 16; ++r) {
+                    if constexpr (S16) sum += acc[i][(r >> 3) & 1][j][(r >> 2) & 1][r & 3];
+                    else sum += acc[i][j][r];
+                }
         if (sum == 1.2345f) ((float*)p.out)[tid] = sum;
         return;
     }
@@ -497,13 +661,7 @@ __global__ __launch_bounds__(512) void conv_v4_kernel(ConvArgs p) {
             if (c2 + 1 < nchunks2) V4_SC_LOAD(c2 + 1)
             const char* ha_ = smem + buf * HALO_BYTES + HPITCH;               // centre tap: row shift 1, column shift 1 (a_dx[1])
             const char* wb2_ = smem + buf * W_BYTES;
-#pragma unroll
-            for (int kk = 0; kk < KSTEPS; ++kk) {
-#pragma unroll
-                for (int i = 0; i < TM; ++i) af[kk][i] = MF::ld(ha_ + (a_dx[1] ^ V4_KX(kk)) + i * HPITCH + V4_KO(kk));
-#pragma unroll
-                for (int j = 0; j < TN; ++j) bf[kk][j] = MF::ld(wb2_ + (b_0 ^ V4_KX(kk)) + j * 32 * PXB + V4_KO(kk));
-            }
+            V4_LD_FRAGS(ha_, wb2_, 1, false)
             V4_MFMA(nchunks, 0)
         }
 #undef V4_SC_LOAD
@@ -512,10 +670,13 @@ __global__ __launch_bounds__(512) void conv_v4_kernel(ConvArgs p) {
     __syncthreads();                                         // the epilogue re-uses the LDS
     V4_STAMP(6)
 #undef V4_MFMA
+#undef V4_MMA_ALL
 #undef V4_XF_PHASE
 #undef V4_STORE_W
+#undef V4_LD_FRAGS
 #undef V4_KX
 #undef V4_KO
+#undef V4_SW
 
     // ------------------------------ epilogue: per-wave LDS transpose, 16-byte I/O ------------------------------------------
     // VALU diet (the epilogue used to be 47 % of the kernel's VALU instructions, all of them outside the MFMAs' shadow):
@@ -524,10 +685,11 @@ __global__ __launch_bounds__(512) void conv_v4_kernel(ConvArgs p) {
     // the accumulators, the multiply by out_scale is skipped when it is 1, and the GroupNorm partial sums are taken from the
     // fp32 values (of which the stored ones are the roundings) instead of re-expanding the packed result.
     constexpr int STG_LD = BN + 4;
-    constexpr bool ATID = EPI >= 0 && !(EPI & 4) && sizeof(TOUT) == 2;   // lane-linear staging of half rounds by ds_write_addtid_b32 (v4_stage8)
-    constexpr int STG_WAVE = ATID ? V4_STG_ATID_BYTES : 32 * STG_LD * 4;   // 8,384 B per wave and half round / 16,896 B per wave and round
+    // lane-linear staging of half rounds by ds_write_addtid_b32: Wide16x16 every form (v5_stage8), Wide32x32 the 16-bit forms without the Combine set (v4_stage8)
+    constexpr bool ATID = S16 || (EPI >= 0 && !(EPI & 4) && sizeof(TOUT) == 2);
+    constexpr int STG_WAVE = S16 ? V5_STG_BYTES : ATID ? V4_STG_ATID_BYTES : 32 * STG_LD * 4;   // 8,448 / 8,384 B per wave and half round / 16,896 B per wave and round
     // M0[15:0] holds the staging base of ds_write_addtid_b32: wave 7's base must fit in 16 bits (the dynamic block starts at LDS offset 0)
-    static_assert(!ATID || 7 * STG_WAVE < 65536, "conv_v4: wave-7 staging base exceeds M0[15:0]");
+    static_assert(!ATID || 7 * STG_WAVE < 65536, "conv_wide: wave-7 staging base exceeds M0[15:0]");
     constexpr int CH = 16 / (int)sizeof(TOUT);
     constexpr int CPR = BN / CH;                             // 16-byte chunks per pixel row: 16 (bf16) / 32 (fp32)
     constexpr int QN = 32 * CPR / 64;                        // passes per round: 8 / 16
@@ -570,9 +732,21 @@ __global__ __launch_bounds__(512) void conv_v4_kernel(ConvArgs p) {
     // read-back address of pass q (pixel column x = q * PPP + lane / CPR of the round's tile row, channels ch * CH ...), 16-byte half c4:
     //   padded rows:  stg[x][ch * CH + 4 c4]
     //   add-TID form (half rounds of 16 columns, q = 0 .. 3 inside one): x = (r & 3) + 8 (r >> 2) + 4 h  ->  r' = lane / 16 + 4 (q >> 1), h = q & 1
-    const float* const stg_rd = ATID ? stg + (ch >> 2) * 512 + (lane >> 4) * 64 + 4 * (((ch >> 2) & 1) + 8 * (ch >> 3)) + (ch & 3) * 8
-                                     : stg + (lane / CPR) * STG_LD + ch * CH;
-    auto stg_rd_off = [&](int q, int c4) -> int { return ATID ? ((q >> 1) & 1) * 256 + (q & 1) * 32 + c4 * 4 : q * PPP * STG_LD + c4 * 4; };   // floats
+    // Wide16x16, pass q of a half round (pixel column 4 q + lane / 16 of the half, channels 8 ch ... 8 ch + 7): the half's register (jb, r) is the
+    // lane-linear row [lane group g' = 16 floats][logical column n] at float (jb * 4 + r) * 64 + 8 jb (v5_stage8); lane group g' holds pixel
+    // quad Q(g') = (0, 2, 3, 1), so pass q reads g' = (0, 3, 1, 2)[q], r = lane / 16; physical channels 0-3 / 4-7 / 8-11 / 12-15 of a group of 16
+    // sit at logical columns 0 / 12 / 4 / 8 (pi): the two 16-byte halves of a lane's 8 channels are two separate pieces of the row (stg_rd, stg_rd1).
+    // The shift by 2 jb bank quads makes a ds_read_b128's 16-lane groups hit 16 distinct quads.
+    const float* const stg_rd = S16    ? stg + ((ch >> 1) * 4 + (lane >> 4)) * 64 + 8 * (ch >> 1) + ((ch & 1) ? 4 : 0)
+                                : ATID ? stg + (ch >> 2) * 512 + (lane >> 4) * 64 + 4 * (((ch >> 2) & 1) + 8 * (ch >> 3)) + (ch & 3) * 8
+                                       : stg + (lane / CPR) * STG_LD + ch * CH;
+    const float* const stg_rd1 = stg + ((ch >> 1) * 4 + (lane >> 4)) * 64 + 8 * (ch >> 1) + ((ch & 1) ? 8 : 12);   // (Wide16x16)
+    auto stg_rd_ptr = [&](int q, int c4) -> const float* {
+        const int ql = q & 3;
+        return S16    ? (c4 ? stg_rd1 : stg_rd) + 16 * (ql == 0 ? 0 : ql == 1 ? 3 : ql == 2 ? 1 : 2)
+               : ATID ? stg_rd + ((q >> 1) & 1) * 256 + (q & 1) * 32 + c4 * 4
+                      : stg_rd + q * PPP * STG_LD + c4 * 4;
+    };
     const unsigned stg_lds = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem + (unsigned)(wave_u * STG_WAVE);
     auto row_bytes = [&](int i) -> unsigned {                // byte offset of this wave's tile row i inside the image (uniform)
         return (unsigned)(((ty0 + wave_u * 2 + i) * p.W + tx0) * p.Cout) * (unsigned)sizeof(TOUT);
@@ -583,27 +757,33 @@ __global__ __launch_bounds__(512) void conv_v4_kernel(ConvArgs p) {
         for (int q = 0; q < QN; ++q)
             rv[q] = (V4_ABL & 8192) ? make_uint4(q, q, q, q) : __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs_res, voff + row_b + (unsigned)q * pass_b, 0, V4_AUX_RES));
     };
-    auto stage_write = [&](int i) {
+    auto stage_write = [&](int i) {                          // padded rows (the forms without ATID: Wide32x32 only)
+        if constexpr (!S16) {
 #pragma unroll
-        for (int j = 0; j < TN; ++j)
+            for (int j = 0; j < TN; ++j)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                stg[row * STG_LD + j * 32 + (lane & 31)] = acc[i][j][r];
-            }
+                for (int r = 0; r < 16; ++r) {
+                    const int row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                    stg[row * STG_LD + j * 32 + (lane & 31)] = acc[i][j][r];
+                }
+        }
     };
     // passes read back / finished together: all of a round (specialised forms), a quarter of a round with the Combine set (its weights take 40
     // registers), one at a time with run-time flags (fp32 parity kernels: 16 passes of a round would not fit the register file)
-    constexpr int NQ = EPI_RT ? 1 : (EPI & 4) ? QN / 4 : ATID ? QN / 2 : QN;
+    // (Wide16x16: the four passes of a half round, every form)
+    constexpr int NQ = S16 ? QN / 2 : EPI_RT ? 1 : (EPI & 4) ? QN / 4 : ATID ? QN / 2 : QN;
     auto stage_write_half = [&](int i, int hb) {             // add-TID form: pixel columns 16 hb ... 16 hb + 15 of tile row i
-        if (hb == 0) { v4_stage8<0, 0>(stg_lds, acc[i][0]); v4_stage8<1, 0>(stg_lds, acc[i][1]); v4_stage8<2, 0>(stg_lds, acc[i][2]); v4_stage8<3, 0>(stg_lds, acc[i][3]); }
-        else         { v4_stage8<0, 8>(stg_lds, acc[i][0]); v4_stage8<1, 8>(stg_lds, acc[i][1]); v4_stage8<2, 8>(stg_lds, acc[i][2]); v4_stage8<3, 8>(stg_lds, acc[i][3]); }
+        if constexpr (S16) {                                 // = accumulators (i, a = hb, *, *)
+            v5_stage8<0>(stg_lds, acc[i][hb][0][0], acc[i][hb][0][1]); v5_stage8<1>(stg_lds, acc[i][hb][1][0], acc[i][hb][1][1]);
+            v5_stage8<2>(stg_lds, acc[i][hb][2][0], acc[i][hb][2][1]); v5_stage8<3>(stg_lds, acc[i][hb][3][0], acc[i][hb][3][1]);
+        } else if (hb == 0) { v4_stage8<0, 0>(stg_lds, acc[i][0]); v4_stage8<1, 0>(stg_lds, acc[i][1]); v4_stage8<2, 0>(stg_lds, acc[i][2]); v4_stage8<3, 0>(stg_lds, acc[i][3]); }
+        else                { v4_stage8<0, 8>(stg_lds, acc[i][0]); v4_stage8<1, 8>(stg_lds, acc[i][1]); v4_stage8<2, 8>(stg_lds, acc[i][2]); v4_stage8<3, 8>(stg_lds, acc[i][3]); }
     };
     auto stage_read = [&](int q0, f32x4 (&t)[NQ][CH / 4]) {
 #pragma unroll
         for (int q = 0; q < NQ; ++q)
 #pragma unroll
-            for (int c4 = 0; c4 < CH / 4; ++c4) t[q][c4] = *reinterpret_cast<const f32x4*>(stg_rd + stg_rd_off(q0 + q, c4));
+            for (int c4 = 0; c4 < CH / 4; ++c4) t[q][c4] = *reinterpret_cast<const f32x4*>(stg_rd_ptr(q0 + q, c4));
     };
     auto finish = [&](int i, int q0, const f32x4 (&t)[NQ][CH / 4], const uint4 (&rv)[QN]) {
         const int gy = ty0 + wave_u * 2 + i;                 // this round's tile row (uniform)
@@ -675,8 +855,9 @@ __global__ __launch_bounds__(512) void conv_v4_kernel(ConvArgs p) {
                 __builtin_amdgcn_sched_barrier(0);
             };
             auto fence = [&]() { asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); };
+            constexpr bool RV2 = !(EPI & 4);                 // with the Combine set (40 registers of weights; ATID: Wide16x16 only) the second tile row's residual re-uses rv0
             stage_write_half(0, 0);
-            stage_read(0, t); if (has_res) res_load(1, rv1); pin();
+            stage_read(0, t); if (has_res && RV2) res_load(1, rv1); pin();
             stage_write_half(0, 1); fence();
             finish(0, 0, t, rv0); fence();
             stage_read(NQ, t); pin();
@@ -684,11 +865,12 @@ __global__ __launch_bounds__(512) void conv_v4_kernel(ConvArgs p) {
             finish(0, NQ, t, rv0);
             V4_STAMP(7)
             fence();
+            if (has_res && !RV2) res_load(1, rv0);
             stage_read(0, t); pin();
             stage_write_half(1, 1); fence();
-            finish(1, 0, t, rv1); fence();
+            finish(1, 0, t, RV2 ? rv1 : rv0); fence();
             stage_read(NQ, t); pin();
-            finish(1, NQ, t, rv1);
+            finish(1, NQ, t, RV2 ? rv1 : rv0);
         } else {
             stage_write(0);
             __builtin_amdgcn_wave_barrier();
@@ -749,10 +931,10 @@ __global__ __launch_bounds__(512) void conv_v4_kernel(ConvArgs p) {
 #endif
 }
 
-template <typename TIN, typename TOUT, int CK, bool ACT, int EPI>
+template <typename SHAPE, typename TIN, typename TOUT, int CK, bool ACT, int EPI>
 static void v4_launch_e(const ConvArgs& a, hipStream_t s) {
     constexpr int MAIN = 2 * V4_HH * 48 * 64 + 2 * V4_BN * 64 + 512 * 8 + 2 * 5 * 512 * 4;   // halo + weight buffers, GroupNorm table, piece tables
-    constexpr int EPIB = 8 * 32 * (V4_BN + 4) * 4 + 8 * V4_BN * 2 * 4;
+    constexpr int EPIB = (SHAPE::MN == 16 ? 8 * V5_STG_BYTES : 8 * 32 * (V4_BN + 4) * 4) + 8 * V4_BN * 2 * 4;   // staging (Wide32x32: its padded rows) + statistics
 #ifdef USE_HIP_TRACE_BUILD
     constexpr int SMEM = 152064 + 2 * 248 * 8;               // + the stamp buffers
 #else
@@ -760,22 +942,22 @@ static void v4_launch_e(const ConvArgs& a, hipStream_t s) {
 #endif
     static_assert(MAIN <= 152064 && EPIB <= 152064 && SMEM <= 163840, "LDS budget");
     static LdsAttrOnce attr;                                 // per (instantiation, device)
-    auto kern = conv_v4_kernel<TIN, TOUT, CK, ACT, EPI>;
+    auto kern = conv_wide_kernel<SHAPE, TIN, TOUT, CK, ACT, EPI>;
     attr(kern, SMEM);
     dim3 grid(conv_v4_tiles(a.H, a.W), (a.Cout + V4_BN - 1) / V4_BN, a.B);
     hipLaunchKernelGGL(kern, grid, dim3(512), SMEM, s, a);
 }
 
-// epilogue specialisation (conv_v4_kernel's EPI): the five flag sets the network produces; a set that is not instantiated runs on the
-// next larger one (a multiply by out_scale = 1 is exact).  fp32 storage (parity mode) keeps the run-time flags.
-template <typename TIN, typename TOUT, int CK, bool ACT>
+// epilogue specialisation (conv_wide_kernel's EPI): the five flag sets the network produces; a set that is not instantiated runs on the
+// next larger one (a multiply by out_scale = 1 is exact).  fp32 storage (parity mode, Wide32x32 only) keeps the run-time flags.
+template <typename SHAPE, typename TIN, typename TOUT, int CK, bool ACT>
 static void v4_launch_t(const ConvArgs& a, hipStream_t s) {
-    if constexpr (sizeof(TIN) == 4) { v4_launch_e<TIN, TOUT, CK, ACT, -1>(a, s); return; } else {
+    if constexpr (sizeof(TIN) == 4) { v4_launch_e<SHAPE, TIN, TOUT, CK, ACT, -1>(a, s); return; } else {
     const bool res = a.res != nullptr, scale = a.out_scale != 1.f, pyr = a.pyr != nullptr;
-    if (pyr) { res ? v4_launch_e<TIN, TOUT, CK, ACT, 7>(a, s) : v4_launch_e<TIN, TOUT, CK, ACT, 6>(a, s); }
-    else if (res) v4_launch_e<TIN, TOUT, CK, ACT, 3>(a, s);
-    else if (scale) v4_launch_e<TIN, TOUT, CK, ACT, 2>(a, s);
-    else v4_launch_e<TIN, TOUT, CK, ACT, 0>(a, s);
+    if (pyr) { res ? v4_launch_e<SHAPE, TIN, TOUT, CK, ACT, 7>(a, s) : v4_launch_e<SHAPE, TIN, TOUT, CK, ACT, 6>(a, s); }
+    else if (res) v4_launch_e<SHAPE, TIN, TOUT, CK, ACT, 3>(a, s);
+    else if (scale) v4_launch_e<SHAPE, TIN, TOUT, CK, ACT, 2>(a, s);
+    else v4_launch_e<SHAPE, TIN, TOUT, CK, ACT, 0>(a, s);
     }
 }
 
@@ -798,7 +980,7 @@ const char* conv_v4_unrunnable(const ConvArgs& a) {
     if (a.H % V4_TH || a.W % V4_TW) return "H % 16 == 0 and W % 32 == 0 (whole tiles)";
     return nullptr;
 }
-// the same for conv_v5_kernel (the 16x16x32 form of this kernel, use_conv_v5.hip; forced launches: variant 5): conv_v4's conditions and 16-bit storage
+// the same for the Wide16x16 form (forced launches: variant 5): conv_v4's conditions and 16-bit storage
 const char* conv_v5_unrunnable(const ConvArgs& a) {
     return a.in_dtype == DT_F32 ? "16-bit storage" : conv_v4_unrunnable(a);
 }
@@ -812,7 +994,12 @@ bool conv_v4_eligible(const ConvArgs& a) {
     return !off && !conv_v4_unrunnable(a) && blocks >= g_v4_min_blocks;
 }
 
-void launch_conv_v4(const ConvArgs& a0, hipStream_t s) {
+static int g_conv_v5 = 1;              // use_set_option("conv_v5", 0): Wide32x32 (32x32x16 MFMAs) for the 16-bit types as well
+void conv_v5_set(int on) { g_conv_v5 = on; }
+bool conv_v5_enabled(const ConvArgs& a) { return g_conv_v5 != 0 && a.in_dtype != DT_F32; }   // (a launch conv_v4_eligible has accepted)
+
+template <typename SHAPE>
+static void launch_wide(const ConvArgs& a0, hipStream_t s) {
     ConvArgs a = a0;
 #ifdef USE_HIP_TRACE_BUILD
     if (getenv("USE_HIP_TRACE")) {           // bring-up only: print the coarse timeline of the first H=512 launch with a given Cin
@@ -828,7 +1015,7 @@ void launch_conv_v4(const ConvArgs& a0, hipStream_t s) {
             (void)hipMemsetAsync(trace_buf, 0, 512 * 8, s);
             a.trace = trace_buf;
             if (getenv("USE_HIP_TRACE_WG")) a.dbg = atoi(getenv("USE_HIP_TRACE_WG"));
-            a.act ? v4_launch_t<__bf16, __bf16, 32, true>(a, s) : v4_launch_t<__bf16, __bf16, 32, false>(a, s);
+            a.act ? v4_launch_t<SHAPE, __bf16, __bf16, 32, true>(a, s) : v4_launch_t<SHAPE, __bf16, __bf16, 32, false>(a, s);
             (void)hipStreamSynchronize(s);
             unsigned long long hbuf[512];
             (void)hipMemcpy(hbuf, trace_buf, sizeof hbuf, hipMemcpyDeviceToHost);
@@ -844,9 +1031,13 @@ void launch_conv_v4(const ConvArgs& a0, hipStream_t s) {
         }
     }
 #endif
-    if (a.in_dtype == DT_BF16)     { a.act ? v4_launch_t<__bf16, __bf16, 32, true>(a, s) : v4_launch_t<__bf16, __bf16, 32, false>(a, s); }
-    else if (a.in_dtype == DT_F16) { a.act ? v4_launch_t<_Float16, _Float16, 32, true>(a, s) : v4_launch_t<_Float16, _Float16, 32, false>(a, s); }
-    else                           { a.act ? v4_launch_t<float, float, 16, true>(a, s) : v4_launch_t<float, float, 16, false>(a, s); }
+    constexpr bool S16 = SHAPE::MN == 16;                    // 16-bit storage only (conv_v5_unrunnable)
+    if (a.in_dtype == DT_BF16)            { a.act ? v4_launch_t<SHAPE, __bf16, __bf16, 32, true>(a, s) : v4_launch_t<SHAPE, __bf16, __bf16, 32, false>(a, s); }
+    else if (S16 || a.in_dtype == DT_F16) { a.act ? v4_launch_t<SHAPE, _Float16, _Float16, 32, true>(a, s) : v4_launch_t<SHAPE, _Float16, _Float16, 32, false>(a, s); }
+    else if constexpr (!S16)              { a.act ? v4_launch_t<SHAPE, float, float, 16, true>(a, s) : v4_launch_t<SHAPE, float, float, 16, false>(a, s); }
 }
+
+void launch_conv_v4(const ConvArgs& a, hipStream_t s) { launch_wide<Wide32x32>(a, s); }
+void launch_conv_v5(const ConvArgs& a, hipStream_t s) { launch_wide<Wide16x16>(a, s); }
 
 }  // namespace use

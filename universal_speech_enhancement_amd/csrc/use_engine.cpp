@@ -73,7 +73,7 @@ static inline uint16_t f32_to_f16(float f) {    // round to nearest even, overfl
 struct ConvW { std::string wname, bname; int cin = 0, cout = 0, cout_pad = 0, ntaps = 1, w_dtype = DT_F32;
                bool nin = false; size_t w_off = 0, b_off = 0;
                int cin_src = 0, cout_src = 0;                 // extents of the host tensor when it is zero-padded to cin / cout
-               size_t wb_off = 0; bool has_wb = false;        // slab-major copy for conv_v4_kernel (see pack_conv)
+               size_t wb_off = 0; bool has_wb = false;        // slab-major copy for conv_wide_kernel (see pack_conv)
                bool split_in = false; };                      // wb = the bf16 hi / lo split copy of the input convolution (pack_conv_in_split)
 struct GNW { std::string prefix; int C = 0; size_t g_off = 0, b_off = 0; };
 struct ResW { int idx = 0, in_ch = 0, out_ch = 0; bool up = false, down = false, has_c2 = false;
@@ -538,7 +538,7 @@ struct Fwd {
         p.pyr = pyr; p.w4 = cb ? W<float>(cb->w_off) : nullptr; p.b4 = cb ? W<float>(cb->b_off) : nullptr;
         p.out = o.p; p.out_dtype = out_dtype; p.stats = o.stats;
         p.B = B; p.H = a.H; p.W = a.W; p.Cout = w.cout; p.ntaps = w.ntaps;
-        const bool main_variant = conv_v4_eligible(p);        // the dominant kernel (conv_v4_kernel, large maps)
+        const bool main_variant = conv_v4_eligible(p);        // the dominant kernel (conv_wide_kernel, large maps)
         if (const int nparts = part ? conv_stats_parts(p) : 0) {
             if (nparts <= part_rows) { p.stats_part = part; p.stats = nullptr; o.part = part; o.ntiles = nparts; }   // (else: atomics; cannot happen, both count the same grid)
         }

@@ -105,7 +105,7 @@ bool conv_v4_eligible(const ConvArgs& a);
 const char* conv_v4_unrunnable(const ConvArgs& a);         // null if conv_v4 can run `a` (forced launches), else the violated condition
 void conv_v4_set_min_blocks(long n);                     // smallest grid conv_v4 is used for (default 80 workgroups per image)
 void launch_conv_v4(const ConvArgs& a, hipStream_t s);
-// the same kernel on v_mfma_f32_16x16x32 (use_conv_v5.hip; 16-bit storage): less energy per FLOP than the 32x32x16 shape
+// the same kernel on v_mfma_f32_16x16x32 (conv_wide_kernel<Wide16x16>, use_conv_v4.hip; 16-bit storage): less energy per FLOP than the 32x32x16 shape
 const char* conv_v5_unrunnable(const ConvArgs& a);         // the same for conv_v5: conv_v4's conditions and 16-bit storage (defined beside conv_v4_unrunnable)
 void conv_v5_set(int on);                                // use_set_option("conv_v5", 0 / 1), default 1
 bool conv_v5_enabled(const ConvArgs& a);                 // for a launch conv_v4_eligible() accepted

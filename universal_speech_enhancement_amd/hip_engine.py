@@ -272,7 +272,7 @@ class HipScoreEngine:
 
     def profile_score(self, x, y, t):
         """(conv_ms, conv_flops, conv_bytes, conv_launches, total_ms) of one eager score evaluation: HIP events around every
-        launch of the dominant kernel (conv_v4_kernel), its algorithmic FLOPs / HBM bytes, and the evaluation's wall time."""
+        launch of the dominant kernel (conv_wide_kernel), its algorithmic FLOPs / HBM bytes, and the evaluation's wall time."""
         x = _require_cuda_c64("x", x); y = _require_cuda_c64("y", y, x.shape)
         self.plan(x.shape[0], x.shape[3])
         t = t.to(device=x.device, dtype=torch.float32).contiguous()
