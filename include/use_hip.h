@@ -217,6 +217,10 @@ int use_fill_noise_items(use_handle* h, const uint64_t* seeds_host /* [B] */, in
  * x, y: complex64 [B,1,F,T'] device; y must be null when input_channels == 2 (the input is x alone), t must be null when
  * the handle is unconditional and may be null when it is conditional only if no_sigma_scale... (not supported: give t). */
 int use_forward(use_handle* h, const void* x, const void* y, const float* t, void* out, use_stream_t stream);
+/* use_forward with the kernel choice of the per-item sampler loop (use_sample_items): every form that use_forward picks from the size
+ * of the whole (sub-)batch is picked from one image alone, so that item b's output has the bits use_forward gives that item in a batch
+ * of one (own-length refine stage: a group of items of equal T' in one pass).  Same arguments, same plan. */
+int use_forward_items(use_handle* h, const void* x, const void* y, const float* t, void* out, use_stream_t stream);
 
 /* Spectrogram glue either side of the sampler, handle-free (ScoreModel.spec_fwd + pad_spec, model_wrapper.py:92-96,275-278,
  * util/other.py:128-135; ScoreModel.spec_back + crop, model_wrapper.py:98-103,320).  stft: complex64 [B,F,T] (torch.stft
@@ -236,6 +240,19 @@ int use_stft_fwd(const float* wav, void* Y, int B, int L, int n_fft, int hop, co
                  float exponent, use_stream_t s);
 int use_istft_back(const void* X, float* wav, int B, int L, int n_fft, int hop, const float* window, int Tpad, float factor,
                    float exponent, use_stream_t s);
+
+/* The same two transforms with one valid length per item (own-length sampling): wav float32 DEVICE [B][stride], item b valid for
+ * len_host[b] samples (HOST ints, as in use_metrics; they travel as kernel arguments - no copy, no allocation, no synchronisation
+ * beyond the first call's twiddle table).  use_stft_fwd_items analyses item b as if it were alone: reflect padding at its own end,
+ * T_b = 1 + len[b] / hop frames written, frames T_b <= t < Tpad zero, samples of a row past len[b] never read.
+ * use_istft_back_items: all Tpad frames of item b enter, samples m < len[b] are written, len[b] <= m < stride are written as zero.
+ * Row b of either call has the bits of use_stft_fwd / use_istft_back called on that item alone with L = len[b] and the same Tpad
+ * (same kernel body, same order of additions).  USE_E_INVALID (argument named in use_last_error(), nothing launched): a null
+ * pointer, B < 1, odd n_fft, len[b] <= n_fft / 2, len[b] > stride, 1 + len[b] / hop > Tpad. */
+int use_stft_fwd_items(const float* wav, int64_t stride, const int* len_host, void* Y, int B, int n_fft, int hop, const float* window,
+                       int Tpad, float factor, float exponent, use_stream_t s);
+int use_istft_back_items(const void* X, float* wav, int64_t stride, const int* len_host, int B, int n_fft, int hop,
+                         const float* window, int Tpad, float factor, float exponent, use_stream_t s);
 
 /* Chunked sampling of long recordings (no reference counterpart), handle-free: the frame axis of Y [B,1,F,Tp] (Tp the padded frame
  * count, a multiple of 64) is cut into n windows of C frames (C a positive multiple of 64) that start hop = C - overlap frames apart,
@@ -419,12 +436,18 @@ int use_op_attention_bwd(const float* q, const float* k, const float* v, const f
  * use_resample_fft: scipy.signal.resample(x, num) == librosa.resample(res_type="fft") for real x (loadwav_dataset.py:95-98).
  * use_load_utterance: the reference's inference loader for one file (loadwav_dataset.py:90-120): first channel, FFT resampling
  *   to target_rate (0: keep), x / max|x| * 0.8 when normalize, float64 throughout, float32 out (malloc'ed; use_free).
- * use_wav_write: sf.write(path, x, rate) of SGMSE_module.py:80 (USE_WAV_PCM16 = soundfile's default WAV subtype) or 32-bit float. */
+ * use_wav_write: sf.write(path, x, rate) of SGMSE_module.py:80 (USE_WAV_PCM16 = soundfile's default WAV subtype) or 32-bit float.
+ * use_wav_info: what use_wav_read reports about a file, from its chunk headers alone (no sample is read).
+ * use_resampled_length: the length use_load_utterance gives a file of `frames` frames at sample_rate - librosa's ratio-first
+ *   rounding, ceil(frames * (double(target_rate) / sample_rate)); `frames` itself for target_rate <= 0 or == sample_rate; -1 for
+ *   frames < 0 or sample_rate < 1. */
 enum { USE_WAV_PCM16 = 0, USE_WAV_FLOAT32 = 1 };
 int use_wav_read(const char* path, double** samples, int64_t* frames, int* channels, int* sample_rate);
 int use_wav_write(const char* path, const float* samples, int64_t frames, int channels, int sample_rate, int subtype);
 int use_resample_fft(const double* x, int64_t n, int64_t num, double* y);
 int use_load_utterance(const char* path, int target_rate, int normalize, float** wav, int64_t* length, int* sample_rate);
+int use_wav_info(const char* path, int64_t* frames, int* channels, int* sample_rate);
+int64_t use_resampled_length(int64_t frames, int sample_rate, int target_rate);
 void use_free(void* p);
 
 /* timesteps of the sampler, torch.linspace(1, t_eps, N) float32 semantics (sampling/__init__.py:63); host only */

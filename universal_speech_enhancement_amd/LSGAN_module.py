@@ -21,7 +21,7 @@ class GANModule(_Base):
                  rewrite_lr=False, G_lr=None, D_lr=None, wav_subtype: str = "PCM_16", sampler_kwargs=None):
         super().__init__()
         self.G = G
-        self.sampler_kwargs = dict(sampler_kwargs or {})     # optional chunk_frames / chunk_overlap / chunk_batch for long recordings (as SGMSEModule)
+        self.sampler_kwargs = dict(sampler_kwargs or {})     # optional chunk_frames / chunk_overlap / chunk_batch for long recordings, own_length (as SGMSEModule)
         self.wav_subtype = wav_subtype
         self.compile = compile
 

@@ -36,7 +36,7 @@ class SGMSEModule(_Base):
         self.Score = Score
         self.wav_subtype = wav_subtype                       # "PCM_16" = what the reference's sf.write produces; "FLOAT" = float32
         self.optimizer, self.scheduler, self.compile = optimizer, scheduler, compile
-        self.sampler_kwargs = dict(sampler_kwargs or {})     # optional N / corrector_steps / snr overrides, sampler_type="ode" (+ rtol / atol / minibatch), chunk_frames (+ chunk_overlap / chunk_batch), per_item (+ seed)
+        self.sampler_kwargs = dict(sampler_kwargs or {})     # optional N / corrector_steps / snr overrides, sampler_type="ode" (+ rtol / atol / minibatch), chunk_frames (+ chunk_overlap / chunk_batch), per_item (+ seed), own_length
 
     def load_lightning_checkpoint(self, path: str, map_location="cpu"):
         """Loads ``ckpt['state_dict']`` with the reference's key layout (``Score.score_net.all_modules...``)."""
@@ -52,7 +52,8 @@ class SGMSEModule(_Base):
         kw = dict(self.sampler_kwargs)
         if kw.get("per_item") and kw.get("item_seeds") is None and "audio_path" in batch:
             # batch-invariant sampling: a file's noise is named by its path relative to data_folder, so that its output does not depend
-            # on the batch order, on batch_size (at equal padded length T') or on how the files are sharded over the ranks
+            # on the batch order, on batch_size or on how the files are sharded over the ranks - at equal padded length T', or for any
+            # mix of lengths with own_length (every file at its own T')
             from .seeding import item_seed, path_key
             kw["item_seeds"] = [item_seed(int(kw.get("seed", 0)), path_key(os.path.relpath(p, batch["data_folder"]).replace(os.sep, "/")))
                                 for p in batch["audio_path"]]

@@ -73,6 +73,7 @@ SYMBOLS = {
     "use_workspace_bytes": (_i, [_vp, C.POINTER(C.c_size_t)]),
     "use_score": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "use_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "use_forward_items": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "use_score2": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "use_sample_cond2": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp]),
     "use_sample_items": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_u64), _vp, _vp]),
@@ -95,6 +96,8 @@ SYMBOLS = {
     "use_spec_back": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_float, C.c_float, _vp]),
     "use_stft_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, C.c_float, C.c_float, _vp]),
     "use_istft_back": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, C.c_float, C.c_float, _vp]),
+    "use_stft_fwd_items": (_i, [_vp, _i64, C.POINTER(_i), _vp, _i, _i, _i, _vp, _i, C.c_float, C.c_float, _vp]),
+    "use_istft_back_items": (_i, [_vp, _vp, _i64, C.POINTER(_i), _i, _i, _i, _vp, _i, C.c_float, C.c_float, _vp]),
     "use_chunk_count": (_i, [_i, _i, _i]),
     "use_chunk_split": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "use_chunk_merge": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
@@ -139,6 +142,8 @@ SYMBOLS = {
     "use_wav_write": (_i, [C.c_char_p, _vp, _i64, _i, _i, _i]),
     "use_resample_fft": (_i, [_vp, _i64, _i64, _vp]),
     "use_load_utterance": (_i, [C.c_char_p, _i, _i, C.POINTER(C.POINTER(C.c_float)), C.POINTER(_i64), C.POINTER(_i)]),
+    "use_wav_info": (_i, [C.c_char_p, C.POINTER(_i64), C.POINTER(_i), C.POINTER(_i)]),
+    "use_resampled_length": (_i64, [_i64, _i, _i]),
     "use_free": (None, [_vp]),
 }
 

@@ -1351,6 +1351,11 @@ int use_score(use_handle* h, const void* x, const void* y, const float* t, void*
 int use_forward(use_handle* h, const void* x, const void* y, const float* t, void* out, use_stream_t stream) {
     return eval_net(h, x, y, t, out, stream, +1.f);
 }
+int use_forward_items(use_handle* h, const void* x, const void* y, const float* t, void* out, use_stream_t stream) {
+    // the kernel choice of the per-item sampler loop (run_sampler): conv_sk picks its tile form from the per-image workgroup count
+    struct PerImage { PerImage() { conv_sk_set_per_image(true); } ~PerImage() { conv_sk_set_per_image(false); } } per_image;
+    return eval_net(h, x, y, t, out, stream, +1.f);
+}
 
 int use_profile_score(use_handle* h, const void* x, const void* y, const float* t, void* out, use_stream_t stream,
                       double* conv_ms, double* conv_flops, double* conv_bytes, int* conv_launches, double* total_ms) {
@@ -2001,6 +2006,51 @@ int use_istft_back(const void* X, float* wav, int B, int L, int n_fft, int hop, 
     const float2* tw = nullptr;
     rc = twiddles(n_fft, (hipStream_t)s, &tw); if (rc) return rc;
     launch_istft_back((const float2*)X, window, tw, wav, B, L, n_fft, hop, Tpad, factor, exponent, (hipStream_t)s);
+    HIPCHK(hipGetLastError());
+    return USE_OK;
+}
+
+namespace {
+int check_stft_items(const char* who, const int* len_host, int64_t stride, int B, int n_fft, int hop, int Tpad) {
+    if (!len_host) return fail(USE_E_INVALID, "%s: len_host is null", who);
+    if (B < 1) return fail(USE_E_INVALID, "%s: B=%d must be positive", who, B);
+    if (n_fft < 4 || (n_fft & 1)) return fail(USE_E_INVALID, "%s: n_fft=%d must be even and at least 4", who, n_fft);
+    if (hop < 1 || hop > n_fft) return fail(USE_E_INVALID, "%s: hop=%d must lie in 1 ... n_fft = %d", who, hop, n_fft);
+    if (stride < 1 || stride > INT32_MAX) return fail(USE_E_INVALID, "%s: stride=%lld must lie in 1 ... 2^31 - 1", who, (long long)stride);
+    if (Tpad < 1) return fail(USE_E_INVALID, "%s: Tpad=%d must be positive", who, Tpad);
+    for (int b = 0; b < B; ++b) {
+        const int L = len_host[b];
+        if (L <= n_fft / 2) return fail(USE_E_INVALID, "%s: len[%d]=%d is too short for reflect padding with n_fft=%d (needs more than %d samples)", who, b, L, n_fft, n_fft / 2);
+        if (L > stride) return fail(USE_E_INVALID, "%s: len[%d]=%d exceeds stride=%lld", who, b, L, (long long)stride);
+        if (1 + L / hop > Tpad) return fail(USE_E_INVALID, "%s: len[%d]=%d has %d frames, more than Tpad=%d", who, b, L, 1 + L / hop, Tpad);
+    }
+    if ((size_t)n_fft * 8 + (size_t)((n_fft + hop - 1) / hop) * (n_fft / 2 + 1) * 8 > 64 * 1024) return fail(USE_E_INVALID, "%s: n_fft / hop combination exceeds the synthesis kernel's LDS", who);
+    return USE_OK;
+}
+}  // namespace
+
+int use_stft_fwd_items(const float* wav, int64_t stride, const int* len_host, void* Y, int B, int n_fft, int hop, const float* window,
+                       int Tpad, float factor, float exponent, use_stream_t s) {
+    if (!wav) return fail(USE_E_INVALID, "use_stft_fwd_items: wav is null");
+    if (!Y) return fail(USE_E_INVALID, "use_stft_fwd_items: Y is null");
+    if (!window) return fail(USE_E_INVALID, "use_stft_fwd_items: window is null");
+    int rc = check_stft_items("use_stft_fwd_items", len_host, stride, B, n_fft, hop, Tpad); if (rc) return rc;
+    const float2* tw = nullptr;
+    rc = twiddles(n_fft, (hipStream_t)s, &tw); if (rc) return rc;
+    launch_stft_fwd_items(wav, (long)stride, len_host, window, tw, (float2*)Y, B, n_fft, hop, Tpad, factor, exponent, (hipStream_t)s);
+    HIPCHK(hipGetLastError());
+    return USE_OK;
+}
+int use_istft_back_items(const void* X, float* wav, int64_t stride, const int* len_host, int B, int n_fft, int hop,
+                         const float* window, int Tpad, float factor, float exponent, use_stream_t s) {
+    if (!X) return fail(USE_E_INVALID, "use_istft_back_items: X is null");
+    if (!wav) return fail(USE_E_INVALID, "use_istft_back_items: wav is null");
+    if (!window) return fail(USE_E_INVALID, "use_istft_back_items: window is null");
+    if (factor == 0.f || exponent == 0.f) return fail(USE_E_INVALID, "use_istft_back_items: factor and exponent must not be zero");
+    int rc = check_stft_items("use_istft_back_items", len_host, stride, B, n_fft, hop, Tpad); if (rc) return rc;
+    const float2* tw = nullptr;
+    rc = twiddles(n_fft, (hipStream_t)s, &tw); if (rc) return rc;
+    launch_istft_back_items((const float2*)X, window, tw, wav, (long)stride, len_host, B, n_fft, hop, Tpad, factor, exponent, (hipStream_t)s);
     HIPCHK(hipGetLastError());
     return USE_OK;
 }

@@ -208,6 +208,53 @@ int use_resample_fft(const double* x, int64_t n, int64_t num, double* y) {
     return USE_OK;
 }
 
+int64_t use_resampled_length(int64_t frames, int sample_rate, int target_rate) {
+    if (frames < 0 || sample_rate < 1) return -1;
+    if (target_rate <= 0 || target_rate == sample_rate) return frames;
+    // librosa.resample: ratio = float(target_sr) / orig_sr first, then int(ceil(len * ratio)) - for 44.1 kHz-family rates and
+    // lengths that are multiples of 147 the rounded ratio gives one sample more than ceil(len * target / sr) would
+    const double ratio = (double)target_rate / (double)sample_rate;
+    return (int64_t)ceil((double)frames * ratio);
+}
+
+// What use_wav_read reports, from the chunk headers alone: the same walk over the chunks, the same clamping of a truncated data chunk.
+int use_wav_info(const char* path, int64_t* frames, int* channels, int* sample_rate) {
+    if (!path || !frames || !channels || !sample_rate) return use_set_error(USE_E_INVALID, "use_wav_info: null argument");
+    FILE* f = fopen(path, "rb");
+    if (!f) return failf(USE_E_INVALID, "cannot open '%s'", path);
+    fseek(f, 0, SEEK_END); const long sz = ftell(f); fseek(f, 0, SEEK_SET);
+    unsigned char h[48];
+    if (sz < 12 || fread(h, 1, 12, f) != 12 || memcmp(h, "RIFF", 4) || memcmp(h + 8, "WAVE", 4)) {
+        fclose(f);
+        return failf(USE_E_INVALID, "'%s' is not a RIFF/WAVE file", path);
+    }
+    int fmt = 0, ch = 0, bits = 0, align = 0; uint32_t sr = 0;
+    bool have_data = false; size_t data_len = 0;
+    for (size_t pos = 12; pos + 8 <= (size_t)sz;) {
+        if (fseek(f, (long)pos, SEEK_SET) || fread(h, 1, 8, f) != 8) break;
+        size_t len = rd32(h + 4);
+        if (pos + 8 + len > (size_t)sz) len = (size_t)sz - pos - 8;
+        if (!memcmp(h, "fmt ", 4) && len >= 16) {
+            const size_t want = len < 40 ? len : 40;
+            if (fread(h + 8, 1, want, f) != want) break;
+            fmt = rd16(h + 8); ch = rd16(h + 10); sr = rd32(h + 12); align = rd16(h + 20); bits = rd16(h + 22);
+            if (fmt == 0xFFFE && len >= 26) fmt = rd16(h + 8 + 24);
+        } else if (!memcmp(h, "data", 4)) {
+            have_data = true; data_len = len;
+            break;
+        }
+        pos += 8 + len + (len & 1);
+    }
+    fclose(f);
+    if (!have_data || ch < 1 || bits < 8) return failf(USE_E_INVALID, "'%s': no fmt/data chunk", path);
+    const int bps = bits / 8;
+    if (align < bps * ch) align = bps * ch;
+    if (!((fmt == 1 && (bps >= 1 && bps <= 4)) || (fmt == 3 && (bps == 4 || bps == 8))))
+        return failf(USE_E_INVALID, "'%s': unsupported sample format (tag %ld)", path, (long)fmt * 100 + bits);
+    *frames = (int64_t)(data_len / (size_t)align); *channels = ch; *sample_rate = (int)sr;
+    return USE_OK;
+}
+
 int use_load_utterance(const char* path, int target_rate, int normalize, float** wav, int64_t* length, int* sample_rate) {
     if (!wav || !length || !sample_rate) return use_set_error(USE_E_INVALID, "use_load_utterance: null argument");
     double* raw = nullptr; int64_t frames = 0; int ch = 0, sr = 0;
@@ -218,10 +265,7 @@ int use_load_utterance(const char* path, int target_rate, int normalize, float**
     for (int64_t i = 0; i < frames; ++i) x[(size_t)i] = raw[(size_t)i * (size_t)ch];        // first channel (loadwav_dataset.py:93-94)
     free(raw);
     if (target_rate > 0 && target_rate != sr) {                                             // loadwav_dataset.py:95-98
-        // librosa.resample: ratio = float(target_sr) / orig_sr first, then int(ceil(len * ratio)) - for 44.1 kHz-family rates and
-        // lengths that are multiples of 147 the rounded ratio gives one sample more than ceil(len * target / sr) would
-        const double ratio = (double)target_rate / (double)sr;
-        const int64_t num = (int64_t)ceil((double)frames * ratio);
+        const int64_t num = use_resampled_length(frames, sr, target_rate);
         std::vector<double> y((size_t)num);
         resample_fft(x.data(), frames, num, y.data());
         x.swap(y);

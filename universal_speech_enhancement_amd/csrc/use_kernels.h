@@ -152,6 +152,11 @@ void launch_stft_fwd(const float* wav, const float* win, const float2* tw, float
                      int Tpad, float factor, float expo, hipStream_t s);
 void launch_istft_back(const float2* X, const float* win, const float2* tw, float* wav, int B, int L, int N, int hop, int Tpad,
                        float factor, float expo, hipStream_t s);
+// One valid length per item (len_host: [B] HOST ints, passed as kernel arguments, 64 items per launch): rows of `stride` samples.
+void launch_stft_fwd_items(const float* wav, long stride, const int* len_host, const float* win, const float2* tw, float2* Y, int B,
+                           int N, int hop, int Tpad, float factor, float expo, hipStream_t s);
+void launch_istft_back_items(const float2* X, const float* win, const float2* tw, float* wav, long stride, const int* len_host, int B,
+                             int N, int hop, int Tpad, float factor, float expo, hipStream_t s);
 
 // x4[b,f,t,:] = 2*(x.re, x.im, y.re, y.im) - 1   (fp32), x/y complex64 [B,F,T]; y2 != null: 8 channels per pixel,
 // 2*(x, y, y2) - 1 and two zero channels (the 6-channel input of condition="both")

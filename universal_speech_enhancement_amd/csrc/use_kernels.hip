@@ -1577,13 +1577,14 @@ void launch_twiddle_table(float2* tw, int N, hipStream_t s) {
 
 // Y[b][0][k][t] = compress(sum_n w[n] y_b[reflect(t hop + n - N/2)] e^{-2 pi i k n / N}), zero for T <= t < Tpad.
 // One workgroup per (frame, item): the windowed frame and the twiddle table sit in LDS, every thread owns bins k, k + 256.
-__global__ __launch_bounds__(256) void stft_fwd_kernel(const float* __restrict__ wav, const float* __restrict__ win,
-                                                       const float2* __restrict__ tw, float2* __restrict__ Y, int L, int N,
-                                                       int hop, int T, int Tpad, int F, float factor, float expo) {
+// The body is shared by the two kernels below: `row` is the item's waveform (L valid samples), b its row in Y.
+__device__ __forceinline__ void stft_fwd_item(const float* __restrict__ row, const float* __restrict__ win,
+                                              const float2* __restrict__ tw, float2* __restrict__ Y, int b, int L, int N, int hop,
+                                              int T, int Tpad, int F, float factor, float expo) {
     extern __shared__ __attribute__((aligned(16))) char fsm[];
     float* xs = reinterpret_cast<float*>(fsm);                              // [N] windowed frame
     float2* tws = reinterpret_cast<float2*>(fsm + ((N * 4 + 15) & ~15));    // [N] twiddles
-    const int t = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int t = blockIdx.x, tid = threadIdx.x;
     if (t >= T) {                                             // frame padding (pad_spec)
         for (int k = tid; k < F; k += 256) Y[((size_t)b * F + k) * Tpad + t] = make_float2(0.f, 0.f);
         return;
@@ -1592,7 +1593,7 @@ __global__ __launch_bounds__(256) void stft_fwd_kernel(const float* __restrict__
         int q = t * hop + n - N / 2;                          // center=True: reflect padding of N/2 samples on both sides
         if (q < 0) q = -q;
         if (q >= L) q = 2 * (L - 1) - q;
-        xs[n] = wav[(size_t)b * L + q] * win[n];
+        xs[n] = row[q] * win[n];
         tws[n] = tw[n];
     }
     __syncthreads();
@@ -1614,23 +1615,53 @@ __global__ __launch_bounds__(256) void stft_fwd_kernel(const float* __restrict__
         Y[((size_t)b * F + k) * Tpad + t] = make_float2(re * sc, im * sc);
     }
 }
+__global__ __launch_bounds__(256) void stft_fwd_kernel(const float* __restrict__ wav, const float* __restrict__ win,
+                                                       const float2* __restrict__ tw, float2* __restrict__ Y, int L, int N,
+                                                       int hop, int T, int Tpad, int F, float factor, float expo) {
+    const int b = blockIdx.y;
+    stft_fwd_item(wav + (size_t)b * L, win, tw, Y, b, L, N, hop, T, Tpad, F, factor, expo);
+}
+// One valid length per item (own-length sampling): item b is analysed as if it were alone - its reflect padding sits at its own end,
+// T_b = 1 + len[b] / hop frames are written, the rest of the Tpad frames is zero, samples past len[b] are never read.  The lengths of
+// up to 64 items travel as a kernel argument (as metrics_lens_kernel's do): no copy, no allocation, no synchronisation.
+struct StftLens { int v[64]; };
+__global__ __launch_bounds__(256) void stft_fwd_items_kernel(const float* __restrict__ wav, long stride, StftLens lens,
+                                                             const float* __restrict__ win, const float2* __restrict__ tw,
+                                                             float2* __restrict__ Y, int N, int hop, int Tpad, int F, float factor,
+                                                             float expo) {
+    const int b = blockIdx.y, L = lens.v[b];
+    stft_fwd_item(wav + (size_t)b * stride, win, tw, Y, b, L, N, hop, 1 + L / hop, Tpad, F, factor, expo);
+}
 void launch_stft_fwd(const float* wav, const float* win, const float2* tw, float2* Y, int B, int L, int N, int hop, int T,
                      int Tpad, float factor, float expo, hipStream_t s) {
     const size_t sh = ((size_t)N * 4 + 15 & ~(size_t)15) + (size_t)N * 8;
     hipLaunchKernelGGL(stft_fwd_kernel, dim3(Tpad, B), dim3(256), sh, s, wav, win, tw, Y, L, N, hop, T, Tpad, N / 2 + 1, factor, expo);
+}
+void launch_stft_fwd_items(const float* wav, long stride, const int* len_host, const float* win, const float2* tw, float2* Y, int B,
+                           int N, int hop, int Tpad, float factor, float expo, hipStream_t s) {
+    const size_t sh = ((size_t)N * 4 + 15 & ~(size_t)15) + (size_t)N * 8;
+    const int F = N / 2 + 1;
+    for (int b0 = 0; b0 < B; b0 += 64) {                      // 64 items per launch: what one argument pack holds
+        const int nb = B - b0 < 64 ? B - b0 : 64;
+        StftLens p{};
+        for (int i = 0; i < nb; ++i) p.v[i] = len_host[b0 + i];
+        hipLaunchKernelGGL(stft_fwd_items_kernel, dim3(Tpad, nb), dim3(256), sh, s, wav + (size_t)b0 * stride, stride, p, win, tw,
+                           Y + (size_t)b0 * F * Tpad, N, hop, Tpad, F, factor, expo);
+    }
 }
 
 // y_b[m] = sum_t w[n] x_t[n] / sum_t w[n]^2, n = m + N/2 - t hop in [0, N), over the T' frames, with
 // x_t[n] = (1/N) (Re S_0 + (-1)^n Re S_{F-1} + 2 sum_{k=1}^{F-2} (Re S_k cos(2 pi k n / N) - Im S_k sin(2 pi k n / N)))   (irfft),
 // S = decompress(X).  One workgroup per (hop-sized block of output samples, item): every output sample of the block meets the
 // same <= ceil(N / hop) frames, whose decompressed spectra are staged in LDS once.
-__global__ __launch_bounds__(256) void istft_back_kernel(const float2* __restrict__ X, const float* __restrict__ win,
-                                                         const float2* __restrict__ tw, float* __restrict__ wav, int L, int N,
-                                                         int hop, int Tpad, int F, int nfr, float inv_factor, float inv_expo) {
+// The body is shared by the two kernels below: `row` is the item's output waveform (samples m < L are written), b its row in X.
+__device__ __forceinline__ void istft_back_item(const float2* __restrict__ X, const float* __restrict__ win,
+                                                const float2* __restrict__ tw, float* __restrict__ row, int b, int L, int N, int hop,
+                                                int Tpad, int F, int nfr, float inv_factor, float inv_expo) {
     extern __shared__ __attribute__((aligned(16))) char ism[];
     float2* tws = reinterpret_cast<float2*>(ism);                           // [N]
     float2* sp = reinterpret_cast<float2*>(ism + (size_t)N * 8);            // [nfr][F] decompressed spectra of the frames in reach
-    const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int h = blockIdx.x, tid = threadIdx.x;
     const int t_hi = h;                                       // frames t_hi - nfr + 1 .. t_hi can reach samples [h hop, (h + 1) hop)
     for (int n = tid; n < N; n += 256) tws[n] = tw[n];
     for (int i = tid; i < nfr * F; i += 256) {
@@ -1676,8 +1707,30 @@ __global__ __launch_bounds__(256) void istft_back_kernel(const float2* __restric
             const float w = win[n];
             acc = fmaf(w, x, acc); env = fmaf(w, w, env);
         }
-        wav[(size_t)b * L + m] = env > 1e-11f ? acc / env : 0.f;
+        row[m] = env > 1e-11f ? acc / env : 0.f;
     }
+}
+__global__ __launch_bounds__(256) void istft_back_kernel(const float2* __restrict__ X, const float* __restrict__ win,
+                                                         const float2* __restrict__ tw, float* __restrict__ wav, int L, int N,
+                                                         int hop, int Tpad, int F, int nfr, float inv_factor, float inv_expo) {
+    const int b = blockIdx.y;
+    istft_back_item(X, win, tw, wav + (size_t)b * L, b, L, N, hop, Tpad, F, nfr, inv_factor, inv_expo);
+}
+// One valid length per item: rows of `stride` samples, m < len[b] synthesised as istft_back_kernel does for L = len[b] (all Tpad frames
+// enter), len[b] <= m < stride written as zero (the collate's padding).  The grid covers the stride; a workgroup whose hop-block lies
+// wholly in the padding only writes its zeros.
+__global__ __launch_bounds__(256) void istft_back_items_kernel(const float2* __restrict__ X, const float* __restrict__ win,
+                                                               const float2* __restrict__ tw, float* __restrict__ wav, long stride,
+                                                               StftLens lens, int N, int hop, int Tpad, int F, int nfr,
+                                                               float inv_factor, float inv_expo) {
+    const int h = blockIdx.x, b = blockIdx.y, L = lens.v[b];
+    float* row = wav + (size_t)b * stride;
+    for (int r = threadIdx.x; r < hop; r += 256) {            // the padding samples of this block
+        const long m = (long)h * hop + r - N / 2;
+        if (m >= L && m < stride) row[m] = 0.f;
+    }
+    if ((long)h * hop - N / 2 >= L) return;                   // no sample of the item in this block
+    istft_back_item(X, win, tw, row, b, L, N, hop, Tpad, F, nfr, inv_factor, inv_expo);
 }
 void launch_istft_back(const float2* X, const float* win, const float2* tw, float* wav, int B, int L, int N, int hop, int Tpad,
                        float factor, float expo, hipStream_t s) {
@@ -1688,6 +1741,21 @@ void launch_istft_back(const float2* X, const float* win, const float2* tw, floa
     attr(istft_back_kernel, 64 * 1024);
     hipLaunchKernelGGL(istft_back_kernel, dim3(nblocks, B), dim3(256), sh, s, X, win, tw, wav, L, N, hop, Tpad, F, nfr, 1.f / factor,
                        1.f / expo);
+}
+void launch_istft_back_items(const float2* X, const float* win, const float2* tw, float* wav, long stride, const int* len_host, int B,
+                             int N, int hop, int Tpad, float factor, float expo, hipStream_t s) {
+    const int F = N / 2 + 1, nfr = (N + hop - 1) / hop;
+    const int nblocks = (int)((stride + N / 2 + hop - 1) / hop);            // blocks of centre-padded samples over the whole row
+    const size_t sh = (size_t)N * 8 + (size_t)nfr * F * 8;
+    static LdsAttrOnce attr;
+    attr(istft_back_items_kernel, 64 * 1024);
+    for (int b0 = 0; b0 < B; b0 += 64) {
+        const int nb = B - b0 < 64 ? B - b0 : 64;
+        StftLens p{};
+        for (int i = 0; i < nb; ++i) p.v[i] = len_host[b0 + i];
+        hipLaunchKernelGGL(istft_back_items_kernel, dim3(nblocks, nb), dim3(256), sh, s, X + (size_t)b0 * F * Tpad, win, tw,
+                           wav + (size_t)b0 * stride, stride, p, N, hop, Tpad, F, nfr, 1.f / factor, 1.f / expo);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------

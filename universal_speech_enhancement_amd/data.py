@@ -2,7 +2,11 @@
 ``pad_to_longest_monaural_inference`` produces (``src/data/components/collate.py:42-73``): first channel, resampled to
 ``sampling_rate`` (FFT method), peak-normalised to 0.8 (``src/data/components/loadwav_dataset.py:90-120``), zero-padded to
 the longest item.  Multi-process runs shard the file list over ranks like the reference's per-rank batches
-(``src/data/loadwav_datamodule.py:53-60``)."""
+(``src/data/loadwav_datamodule.py:53-60``).
+
+``bucket_by_length`` (no reference counterpart, off by default): the rank's shard - the same file set as without it - is ordered by
+(padded frame count T', relative path) and cut into batches of files of EQUAL T', so that ``sample(own_length=True)`` runs full
+batches of one plan shape; T' comes from the WAV headers (``wav_info`` + ``resampled_length``), no file is decoded for it."""
 from __future__ import annotations
 
 import os
@@ -12,14 +16,16 @@ import numpy as np
 import torch
 
 from .distributed import shard_list
-from .wavio import load_utterance
+from .wavio import load_utterance, resampled_length, wav_info
 
 
 class LoadWavData:
     def __init__(self, data_folder: str, target_folder: str, normalize: bool = True, sampling_rate: int = 24000,
-                 batch_size: int = 1, num_workers: int = 0, rank: int = 0, world_size: int = 1, **ignored):
+                 batch_size: int = 1, num_workers: int = 0, rank: int = 0, world_size: int = 1, bucket_by_length: bool = False,
+                 **ignored):
         self.data_folder, self.target_folder = data_folder, target_folder
         self.normalize, self.sampling_rate, self.batch_size = normalize, sampling_rate, batch_size
+        self.bucket_by_length = bool(bucket_by_length)
         files: List[str] = []
         for root, _, names in os.walk(data_folder):
             files += [os.path.join(root, n) for n in sorted(names) if n.endswith(".wav")]
@@ -32,9 +38,34 @@ class LoadWavData:
         x, sr = load_utterance(path, self.sampling_rate, self.normalize)       # native loader (csrc/use_io.cpp)
         return {"perturbed": x, "name": os.path.basename(path).split(".wav")[0], "audio_path": path, "sampling_rate": sr}
 
-    def predict_batches(self, device="cuda") -> Iterator[Dict]:
-        for i in range(0, len(self.filepaths), self.batch_size):
-            items = [self._item(p) for p in self.filepaths[i:i + self.batch_size]]
+    def padded_frames(self, path: str, frame_hop: int) -> int:
+        """T' = pad64(1 + L // frame_hop) of a file, L from its header: the length ``load_utterance`` will give it."""
+        frames, _, sr = wav_info(path)
+        L = resampled_length(frames, sr, self.sampling_rate)
+        return (1 + L // int(frame_hop) + 63) // 64 * 64
+
+    def batch_files(self, frame_hop=None) -> List[List[str]]:
+        """The file lists of the batches ``predict_batches`` yields, in its order.  Default: consecutive ``batch_size`` files of the
+        shard.  ``bucket_by_length``: the shard ordered by (T', path relative to ``data_folder``), cut where T' changes or a batch is
+        full - a batch never mixes two values of T'; the same on every call."""
+        if not self.bucket_by_length:
+            return [self.filepaths[i:i + self.batch_size] for i in range(0, len(self.filepaths), self.batch_size)]
+        if frame_hop is None:
+            raise ValueError("bucket_by_length needs frame_hop (the model's hop_length): predict_batches(device, frame_hop=...)")
+        keyed = sorted((self.padded_frames(p, frame_hop), os.path.relpath(p, self.data_folder).replace(os.sep, "/"), p)
+                       for p in self.filepaths)
+        batches: List[List[str]] = []
+        last = None
+        for Tp, _, p in keyed:
+            if Tp != last or len(batches[-1]) >= self.batch_size:
+                batches.append([])
+                last = Tp
+            batches[-1].append(p)
+        return batches
+
+    def predict_batches(self, device="cuda", frame_hop=None) -> Iterator[Dict]:
+        for paths in self.batch_files(frame_hop):
+            items = [self._item(p) for p in paths]
             lens = np.array([len(it["perturbed"]) for it in items], dtype=np.int32)
             wav = torch.zeros(len(items), int(lens.max()))
             for k, it in enumerate(items):

@@ -89,6 +89,44 @@ def istft_decompress(X: torch.Tensor, window: torch.Tensor, n_fft: int, hop: int
     return wav
 
 
+def _host_lengths(lengths, B: int):
+    lens = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+    if len(lens) != B:
+        raise ValueError(f"lengths has {len(lens)} entries for a batch of {B}")
+    return (C.c_int * B)(*lens)
+
+
+def stft_compress_pad_items(wav: torch.Tensor, lengths, window: torch.Tensor, n_fft: int, hop: int, factor: float, exponent: float,
+                            Tpad: int) -> torch.Tensor:
+    """``stft_compress_pad`` with one valid length per item (``use_stft_fwd_items``): float32 CUDA [B, stride], ``lengths`` B host
+    integers -> complex64 [B,1,F,Tpad].  Row b has the bits of ``stft_compress_pad(wav[b:b+1, :lengths[b]])`` at the same ``Tpad``;
+    samples past ``lengths[b]`` are never read."""
+    if not wav.is_cuda or wav.dtype != torch.float32 or wav.dim() != 2:
+        raise UseHipError("stft_compress_pad_items needs a float32 CUDA tensor [B, stride]")
+    wav, window = wav.contiguous(), window.to(device=wav.device, dtype=torch.float32).contiguous()
+    B, stride = wav.shape
+    lens = _host_lengths(lengths, B)
+    Y = torch.empty((B, 1, n_fft // 2 + 1, int(Tpad)), dtype=torch.complex64, device=wav.device)
+    check(_lib.lib().use_stft_fwd_items(wav.data_ptr(), stride, lens, Y.data_ptr(), B, int(n_fft), int(hop), window.data_ptr(), int(Tpad),
+                                        float(factor), float(exponent), _stream_ptr(wav.device)), "use_stft_fwd_items")
+    return Y
+
+
+def istft_decompress_items(X: torch.Tensor, lengths, window: torch.Tensor, n_fft: int, hop: int, stride: int, factor: float,
+                           exponent: float) -> torch.Tensor:
+    """``istft_decompress`` with one valid length per item (``use_istft_back_items``): complex64 CUDA [B,1,F,T'] -> float32 [B, stride],
+    row b = ``istft_decompress(X[b:b+1], length=lengths[b])`` bit for bit, followed by zeros."""
+    if not X.is_cuda or X.dtype != torch.complex64 or X.dim() != 4 or X.shape[1] != 1 or X.shape[2] != n_fft // 2 + 1:
+        raise UseHipError("istft_decompress_items needs a complex64 CUDA tensor [B, 1, n_fft/2+1, T']")
+    X, window = X.contiguous(), window.to(device=X.device, dtype=torch.float32).contiguous()
+    B, _, _, Tp = X.shape
+    lens = _host_lengths(lengths, B)
+    wav = torch.empty((B, int(stride)), dtype=torch.float32, device=X.device)
+    check(_lib.lib().use_istft_back_items(X.data_ptr(), wav.data_ptr(), int(stride), lens, B, int(n_fft), int(hop), window.data_ptr(), Tp,
+                                          float(factor), float(exponent), _stream_ptr(X.device)), "use_istft_back_items")
+    return wav
+
+
 def chunk_split(Y: torch.Tensor, chunk_frames: int, overlap: int) -> torch.Tensor:
     """The overlapping windows of chunked sampling in one kernel (``use_chunk_split``): complex64 CUDA [B,1,F,T'] -> [B*n,1,F,chunk_frames],
     window k of item b in row b*n + k, frames beyond T' zero; geometry: ``chunking.chunk_plan`` (``ValueError`` for what it refuses)."""
@@ -254,9 +292,11 @@ class HipScoreEngine:
             check(self.L.use_score(self.h, x.data_ptr(), y.data_ptr(), t.data_ptr(), out.data_ptr(), _stream_ptr(x.device)), "use_score")
         return out
 
-    def forward(self, x: torch.Tensor, y: Optional[torch.Tensor] = None, t: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, y: Optional[torch.Tensor] = None, t: Optional[torch.Tensor] = None,
+                per_image: bool = False) -> torch.Tensor:
         """Raw backbone output ``NCSNpp.forward(cat[x, y], t)`` (``use_forward``).  ``y`` is None for a 2-channel
-        (discriminative) network, ``t`` is None for an unconditional one."""
+        (discriminative) network, ``t`` is None for an unconditional one.  ``per_image``: ``use_forward_items`` - the kernel forms a
+        batch of one takes, so that an item's output does not depend on the size of the batch."""
         x = _require_cuda_c64("x", x)
         if y is not None:
             y = _require_cuda_c64("y", y, x.shape)
@@ -266,8 +306,9 @@ class HipScoreEngine:
             if t.shape != (x.shape[0],):
                 raise ValueError(f"t must have shape [{x.shape[0]}]")
         out = torch.empty_like(x)
-        check(self.L.use_forward(self.h, x.data_ptr(), None if y is None else y.data_ptr(), None if t is None else t.data_ptr(),
-                                 out.data_ptr(), _stream_ptr(x.device)), "use_forward")
+        fn, what = (self.L.use_forward_items, "use_forward_items") if per_image else (self.L.use_forward, "use_forward")
+        check(fn(self.h, x.data_ptr(), None if y is None else y.data_ptr(), None if t is None else t.data_ptr(),
+                 out.data_ptr(), _stream_ptr(x.device)), what)
         return out
 
     def profile_score(self, x, y, t):

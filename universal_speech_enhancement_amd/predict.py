@@ -10,6 +10,10 @@
                                                  (batch-invariant sampling: every file draws from its own noise stream, seeded from S and
                                                   its path relative to data_folder, and takes its own Langevin step - the output does not
                                                   depend on batch order, world size, or data.batch_size at equal padded length; off by default)
+        [model.sampler_kwargs.own_length=true [data.bucket_by_length=true]]
+                                                 (every file at its own padded frame count T' instead of its batch's longest: with
+                                                  per_item a file's output is that of its batch-size-1 run, for any mix of lengths;
+                                                  bucket_by_length orders a rank's files by T' so that batches are full at one T')
         [data.clean_folder=clean/]               (score every enhanced file whose clean counterpart exists under clean/ at the same
                                                   relative path: SI-SDR / SI-SIR / SI-SAR / LSD on the device -> enhanced/metrics.csv)
 
@@ -112,8 +116,8 @@ def predict(cfg: dict):
     torch.cuda.set_device(local)
     data = instantiate(cfg["data"], rank=rank, world_size=world)
     model = instantiate(cfg["model"])
+    owner = model.G if hasattr(model, "G") else model.Score                # the module that carries n_fft and hop_length
     if cfg.get("ckpt_path") and str(cfg["ckpt_path"]).endswith(".usehip"):   # packed weight file (pack_checkpoint)
-        owner = model.G if hasattr(model, "G") else model.Score            # the module that carries n_fft
         net = model.G.net if hasattr(model, "G") else model.Score.score_net
         net.load_weight_file(cfg["ckpt_path"], n_freq=int(owner.n_fft) // 2 + 1, device=torch.device("cuda", local))
     elif cfg.get("ckpt_path"):
@@ -129,7 +133,7 @@ def predict(cfg: dict):
     clean_folder = cfg["data"].get("clean_folder")           # off by default: nothing below runs, no CSV is written
     rows = []
     with torch.no_grad():
-        for i, batch in enumerate(data.predict_batches(device=torch.device("cuda", local))):
+        for i, batch in enumerate(data.predict_batches(device=torch.device("cuda", local), frame_hop=owner.hop_length)):
             model.predict_step(batch, i)
             n += len(batch["name"])
             if clean_folder:

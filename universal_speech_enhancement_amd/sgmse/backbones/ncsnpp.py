@@ -177,7 +177,9 @@ class NCSNpp(nn.Module):
         return ncsnpp_forward_train(P, x, time_cond, self.ch_mult, self.num_res_blocks, conditional=self.conditional,
                                     scale_by_sigma=self.scale_by_sigma, compute_dtype=cd)
 
-    def forward(self, x: torch.Tensor, time_cond: torch.Tensor = None) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, time_cond: torch.Tensor = None, per_image: bool = False) -> torch.Tensor:
+        """``per_image`` (inference only): the kernel forms of a batch of one (``use_forward_items``) - an item's output then has the
+        same bits in any batch of its T'."""
         nin = self.input_channels // 2
         if x.dim() != 4 or x.shape[1] != nin:
             raise ValueError("expected complex input [B, 2, F, T'] = cat([x_t, Y], dim=1)" if nin == 2 else
@@ -192,10 +194,12 @@ class NCSNpp(nn.Module):
             return self.forward_train(x, time_cond)
         eng = self.engine(x.shape[2], x.device)
         if nin == 1:
-            return eng.forward(x, None, time_cond if (self.conditional or self.scale_by_sigma) else None)
+            return eng.forward(x, None, time_cond if (self.conditional or self.scale_by_sigma) else None, per_image=per_image)
         if nin == 3:                                         # condition="both": forward = -score (use_score2)
+            if per_image:
+                raise NotImplementedError("per_image is not available for the 6-channel network's forward pass")
             return -eng.score(x[:, 0:1], x[:, 1:2], time_cond, y2=x[:, 2:3])
-        return eng.forward(x[:, 0:1], x[:, 1:2], time_cond)
+        return eng.forward(x[:, 0:1], x[:, 1:2], time_cond, per_image=per_image)
 
 
 @BackboneRegistry.register("ncsnpplarge")

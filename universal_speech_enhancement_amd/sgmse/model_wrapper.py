@@ -257,7 +257,7 @@ class ScoreModel(SpectralGlue, nn.Module):
         return chunk_plan(int(Tp), chunk_frames, chunk_overlap).n > 1
 
     def sample(self, batch, sampler_type="pc", N=50, corrector_steps=1, snr=0.5, noise=None, seed=0, chunk_frames=None,
-               chunk_overlap=64, chunk_batch=8, per_item=False, item_seeds=None, **ode_kwargs):
+               chunk_overlap=64, chunk_batch=8, per_item=False, item_seeds=None, own_length=False, **ode_kwargs):
         """Reference :262-329: adds ``batch['enhanced']`` (float32 [B, L]) for condition / sde_input 'noisy'.
         ``sampler_type="ode"``: the probability-flow ODE sampler (``get_ode_sampler``; ``ode_kwargs``: ``rtol``, ``atol``,
         ``minibatch`` (default 1), ``first_step``, ``max_step``, ``max_nfe``); its NFE is left in ``self.last_nfe``.
@@ -267,14 +267,82 @@ class ScoreModel(SpectralGlue, nn.Module):
         ``per_item`` (default off) / ``item_seeds``: batch-invariant sampling (``sampling.get_pc_sampler``) - every item has its own noise
         stream and its own Langevin step, so that at equal padded frame count T' its result does not depend on the batch it rides in.
         Zero padding to the batch's longest item changes T' and with it what the network sees: un-chunked batches of unequal lengths
-        stay composition-dependent through T'."""
+        are composition-dependent through T' unless ``own_length`` is set.
+
+        ``own_length`` (default off) runs every item at its own padded frame count: the items are grouped by
+        ``T' = pad64(1 + batch["sample_length"][b] // hop)`` (``length_groups``; a missing key raises ``ValueError``), item b is analysed
+        over its own ``sample_length[b]`` samples with the reflect padding at its own end (``use_stft_fwd_items``), and each group runs
+        through the code path above at its own T', the groups one after the other in ascending T'; the results are scattered into
+        ``enhanced`` [B, Lmax], zero past each item's length.  Under ``per_item`` an item keeps the seed it has in the whole batch
+        (``item_seeds[b]``, or the one derived from ``seed`` and b), so its samples are those of ``sample`` called on that item alone,
+        whatever its companions, their order and the batch size.  Without ``per_item``, group g samples with ``seed + g`` (the rule chunk
+        groups follow) and the items of a group are coupled as the items of a batch are: the Langevin step is a mean over the group.
+        An injected ``noise`` has the layout of one plan shape, so it raises ``ValueError`` when the batch forms more than one group.
+        ``self.last_groups``: ``[(T', items), ...]``; ``self.last_nfe``: a list with one entry per group."""
         item_kw = {"per_item": True, "item_seeds": item_seeds} if per_item else {}
         if item_seeds is not None and not per_item:
             raise ValueError("item_seeds needs per_item=True")
+        run_kw = dict(sampler_type=sampler_type, N=N, corrector_steps=corrector_steps, snr=snr, chunk_frames=chunk_frames,
+                      chunk_overlap=chunk_overlap, chunk_batch=chunk_batch, ode_kwargs=ode_kwargs)
+        if own_length:
+            return self._sample_own_length(batch, noise, seed, per_item, item_seeds, run_kw)
         y = batch["perturbed"]
         T_orig = y.size(1)
         Y = self._spectrogram(y)
         Y_denoised = self._spectrogram(batch["fake"]) if "fake" in batch else None
+        sample, key = self._sample_spectrograms(Y, Y_denoised, noise=noise, seed=seed, item_kw=item_kw, **run_kw)
+        batch[key] = self._waveform(sample, T_orig)
+        return batch
+
+    def _sample_own_length(self, batch, noise, seed, per_item, item_seeds, run_kw):
+        """``sample(own_length=True)``: one pass of ``_sample_spectrograms`` per group of equal T'."""
+        if "sample_length" not in batch:
+            raise ValueError("own_length=True needs batch['sample_length'] (the valid samples of every item)")
+        y = batch["perturbed"]
+        B, stride = y.shape
+        lens = [int(v) for v in (batch["sample_length"].tolist() if hasattr(batch["sample_length"], "tolist") else batch["sample_length"])]
+        if len(lens) != B:
+            raise ValueError(f"sample_length has {len(lens)} entries for a batch of {B}")
+        for b, L in enumerate(lens):
+            if L > stride:
+                raise ValueError(f"item {b}: sample_length {L} exceeds the {stride} samples of a row")
+        groups = self.length_groups(lens)
+        if noise is not None and len(groups) > 1:
+            raise ValueError(f"an injected noise tensor has the layout of one plan shape; this batch forms {len(groups)} groups "
+                             f"(T' = {[Tp for Tp, _ in groups]})")
+        if per_item:
+            if item_seeds is None:
+                from ..seeding import item_seeds as derive_item_seeds
+                item_seeds = derive_item_seeds(seed, B)                      # named by the item's index in the whole batch
+            if len(item_seeds) != B:
+                raise ValueError(f"item_seeds has {len(item_seeds)} entries for a batch of {B}")
+        out, key, nfes = None, None, []
+        for g, (Tp, idx) in enumerate(groups):
+            whole = len(idx) == B
+            sel = None if whole else torch.as_tensor(idx, device=y.device)
+            take = lambda a: a if whole else a.index_select(0, sel)         # noqa: E731
+            glens = [lens[i] for i in idx]
+            Y = self._spectrogram_items(take(y), glens, Tp)
+            Y_denoised = self._spectrogram_items(take(batch["fake"]), glens, Tp) if "fake" in batch else None
+            item_kw = {"per_item": True, "item_seeds": [item_seeds[i] for i in idx]} if per_item else {}
+            sample, key = self._sample_spectrograms(Y, Y_denoised, noise=noise, seed=seed if per_item else seed + g, item_kw=item_kw,
+                                                    **run_kw)
+            nfes.append(self.last_nfe)
+            wav = self._waveform_items(sample, glens, stride)
+            if whole:
+                out = wav
+            else:
+                out = torch.zeros((B, stride), dtype=wav.dtype, device=wav.device) if out is None else out
+                out.index_copy_(0, sel, wav)
+        self.last_groups = [(Tp, len(idx)) for Tp, idx in groups]
+        self.last_nfe = nfes
+        batch[key] = out
+        return batch
+
+    def _sample_spectrograms(self, Y, Y_denoised, sampler_type, N, corrector_steps, snr, noise, seed, chunk_frames, chunk_overlap,
+                             chunk_batch, item_kw, ode_kwargs):
+        """The sampler between the analysis and the synthesis of ``sample``: -> (spectrogram [B,1,F,T'], the batch key of the result);
+        the NFE is left in ``self.last_nfe``."""
         # conditioning (reference :283-291): the spectrogram(s) the network sees beside x
         if self.condition == "noisy":
             score_conditioning = [Y]
@@ -291,12 +359,13 @@ class ScoreModel(SpectralGlue, nn.Module):
             sde_input = Y
         else:
             raise NotImplementedError(f"Don't know the sde input you have wished for: {self.sde_input}")
+        # reference :320-328: the key depends on what the SDE started from
+        key = "fake_sde_enhanced" if (self.sde_input == "denoised" and Y_denoised is not None) else "enhanced"
         if self._chunked(sde_input.shape[3], chunk_frames, chunk_overlap, chunk_batch):
             sample = self.sample_spec_chunked(sde_input, score_conditioning, sampler_type=sampler_type, N=N, corrector_steps=corrector_steps,
                                               snr=snr, noise=noise, seed=seed, chunk_frames=chunk_frames, chunk_overlap=chunk_overlap,
                                               chunk_batch=chunk_batch, **item_kw, **ode_kwargs)
-            batch["fake_sde_enhanced" if (self.sde_input == "denoised" and Y_denoised is not None) else "enhanced"] = self._waveform(sample, T_orig)
-            return batch
+            return sample, key
         if sampler_type == "pc":
             if ode_kwargs:
                 raise TypeError(f"sample(sampler_type='pc') got ODE sampler options {sorted(ode_kwargs)}")
@@ -308,9 +377,7 @@ class ScoreModel(SpectralGlue, nn.Module):
             raise NotImplementedError(f"{sampler_type} is not a valid sampler type!")
         sample, nfe = sampler()
         self.last_nfe = nfe
-        # reference :320-328: the key depends on what the SDE started from
-        batch["fake_sde_enhanced" if (self.sde_input == "denoised" and Y_denoised is not None) else "enhanced"] = self._waveform(sample, T_orig)
-        return batch
+        return sample, key
 
     @torch.no_grad()
     def enhance(self, y, sampler_type="pc", predictor="reverse_diffusion", corrector="ald", N=50, corrector_steps=1,

@@ -80,3 +80,44 @@ class SpectralGlue:
             from ...hip_engine import spec_decompress_crop
             return self.istft(spec_decompress_crop(X, X.shape[3], self.spec_factor, self.spec_abs_exponent), length)
         return self.istft(self.spec_back(X.squeeze(1)), length)
+
+    # ---- own-length forms: every item at its own padded frame count ---------------------------------------------------------
+    def length_groups(self, lengths):
+        """``[(Tpad, [indices])]`` of a batch's valid lengths: items of equal ``Tpad = pad64(1 + L // hop)`` form a group, groups in
+        ascending ``Tpad``, indices ascending within a group.  Pure host function.  A length <= n_fft // 2 raises ``ValueError`` and
+        names the item (reflect padding needs more; the reference's ``torch.stft`` refuses such an input too)."""
+        lens = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+        groups = {}
+        for b, L in enumerate(lens):
+            if L <= self.n_fft // 2:
+                raise ValueError(f"item {b} has {L} samples: own-length sampling needs more than n_fft // 2 = {self.n_fft // 2} "
+                                 "(reflect padding of the STFT)")
+            T = 1 + L // self.hop_length
+            groups.setdefault((T + 63) // 64 * 64, []).append(b)
+        return [(Tp, groups[Tp]) for Tp in sorted(groups)]
+
+    def _spectrogram_items(self, y, lengths, Tpad):
+        """waveform rows [B, stride], item b valid for ``lengths[b]`` samples -> [B, 1, F, Tpad]: row b is ``_spectrogram`` of the item
+        alone (reflect padding at its own end), one kernel on the device (``use_stft_fwd_items``)."""
+        lens = [int(v) for v in lengths]
+        if y.is_cuda and y.dtype == torch.float32 and all(self._device_stft_ok(L) for L in lens):
+            from ...hip_engine import stft_compress_pad_items
+            return stft_compress_pad_items(y, lens, self._get_window(y), self.n_fft, self.hop_length, self.spec_factor,
+                                           self.spec_abs_exponent, Tpad)
+        rows = [self._spectrogram(y[b:b + 1, :L].contiguous()) for b, L in enumerate(lens)]
+        if any(r.shape[3] != Tpad for r in rows):
+            raise ValueError(f"items of padded frame counts {[r.shape[3] for r in rows]} do not form one group of T' = {Tpad}")
+        return torch.cat(rows, dim=0)
+
+    def _waveform_items(self, X, lengths, stride):
+        """[B, 1, F, T'] -> waveform rows [B, stride]: row b is ``_waveform(X[b:b+1], lengths[b])`` followed by zeros, one kernel on
+        the device (``use_istft_back_items``)."""
+        lens = [int(v) for v in lengths]
+        if X.is_cuda and all(self._device_stft_ok(L) and X.shape[3] >= 1 + L // self.hop_length for L in lens):
+            from ...hip_engine import istft_decompress_items
+            return istft_decompress_items(X, lens, self._get_window(X), self.n_fft, self.hop_length, stride, self.spec_factor,
+                                          self.spec_abs_exponent)
+        out = torch.zeros((X.shape[0], int(stride)), dtype=torch.float32, device=X.device)
+        for b, L in enumerate(lens):
+            out[b, :L] = self._waveform(X[b:b + 1], L)[0]
+        return out

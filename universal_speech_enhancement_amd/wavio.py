@@ -32,6 +32,22 @@ def write_wav(path: str, wav: np.ndarray, sample_rate: int, subtype: int = PCM16
     check(lib().use_wav_write(os.fsencode(path), a.ctypes.data_as(C.c_void_p), frames, ch, int(sample_rate), subtype), "use_wav_write")
 
 
+def wav_info(path: str):
+    """-> (frames, channels, sample rate) from the file's chunk headers alone (``use_wav_info``): what ``read_wav`` would report."""
+    n, ch, sr = C.c_int64(), C.c_int(), C.c_int()
+    check(lib().use_wav_info(os.fsencode(path), C.byref(n), C.byref(ch), C.byref(sr)), "use_wav_info")
+    return n.value, ch.value, sr.value
+
+
+def resampled_length(frames: int, sr: int, target: int) -> int:
+    """The length ``load_utterance`` gives a file of ``frames`` frames at ``sr`` (``use_resampled_length``: librosa's ratio-first
+    rounding; ``target`` 0 / None or equal to ``sr``: ``frames``)."""
+    n = lib().use_resampled_length(int(frames), int(sr), int(target or 0))
+    if n < 0:
+        raise ValueError(f"resampled_length: bad arguments frames={frames}, sr={sr}")
+    return n
+
+
 def resample_fft(x: np.ndarray, num: int) -> np.ndarray:
     """``scipy.signal.resample(x, num)`` for a real 1-D signal (float64)."""
     a = np.ascontiguousarray(x, dtype=np.float64)
