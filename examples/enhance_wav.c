@@ -2,11 +2,16 @@
  * file through the C ABI of libuse_hip.so alone: no Python, no torch.  What a non-Python host of the library looks like.
  *
  *   enhance_wav <weights.usehip> <noisy.wav> <enhanced.wav> [N=30] [seed=0] [precision: bf16|fp16|fp32 = what the file was packed for]
- *               [--chunk-frames C [--chunk-overlap M=64]]
+ *               [--chunk-frames C [--chunk-overlap M=64]] [--refine refine.usehip]
  *
  * --chunk-frames C (a multiple of 64; anywhere on the line): a recording of more than C padded frames is sampled in overlapping windows of C
  * frames, groups of at most 8 windows per sampler call with seed + group index, and cross-faded back (use_chunk_count / _split / _merge):
  * one plan per group size whatever the file length.  Without the flag, or for a shorter file, the whole file is one sampler call.
+ * --refine refine.usehip (anywhere on the line): the second stage of the reference's pipeline in the same run, on a second handle - the
+ * sampler's waveform passes use_wav_handoff (the 16-bit samples a stage-1 file would hold, the loader's peak normalisation to 0.8: what
+ * lies between the two predict runs of the reference's README, on the device) and then the LSGAN generator, use_stft_fwd -> use_forward ->
+ * use_istft_back, one pass over the whole file; enhanced.wav then holds the refined signal.  refine.usehip: pack_checkpoint model=LSGAN
+ * at the precision of weights.usehip.
  * weights.usehip: `python -m universal_speech_enhancement_amd.pack_checkpoint ckpt=last.ckpt out=weights.usehip precision=bf16`
  * Steps (reference file:line): loader (loadwav_dataset.py:90-120) -> STFT + compression + padding (model_wrapper.py:275-278) ->
  * 30-step PC sampler, reverse diffusion + Langevin x1, snr 0.5 (SGMSE_Large.yaml, sampling/__init__.py:59-71) -> decompression +
@@ -63,9 +68,15 @@ done:
 
 int main(int argc, char** argv) {
     int chunk_frames = -1, chunk_overlap = 64;                              /* -1: no --chunk-frames */
-    {   /* take the two optional flags out of argv; the positional arguments keep their places */
+    const char* refine_path = NULL;                                         /* NULL: no --refine */
+    {   /* take the optional flags out of argv; the positional arguments keep their places */
         int k = 1;
         for (int i = 1; i < argc; ++i) {
+            if (!strcmp(argv[i], "--refine")) {
+                if (++i >= argc) { fprintf(stderr, "%s needs a value\n", argv[i - 1]); return 2; }
+                refine_path = argv[i];
+                continue;
+            }
             int* dst = !strcmp(argv[i], "--chunk-frames") ? &chunk_frames : !strcmp(argv[i], "--chunk-overlap") ? &chunk_overlap : NULL;
             if (!dst) { argv[k++] = argv[i]; continue; }
             if (++i >= argc) { fprintf(stderr, "%s needs a value\n", argv[i - 1]); return 2; }
@@ -77,7 +88,7 @@ int main(int argc, char** argv) {
         argc = k;
     }
     if (argc < 4) {
-        fprintf(stderr, "usage: %s weights.usehip noisy.wav enhanced.wav [N=30] [seed=0] [bf16|fp16|fp32] [--chunk-frames C [--chunk-overlap M]]\n", argv[0]);
+        fprintf(stderr, "usage: %s weights.usehip noisy.wav enhanced.wav [N=30] [seed=0] [bf16|fp16|fp32] [--chunk-frames C [--chunk-overlap M]] [--refine refine.usehip]\n", argv[0]);
         return 2;
     }
     const int N = argc > 4 ? atoi(argv[4]) : 30;
@@ -101,6 +112,18 @@ int main(int argc, char** argv) {
     use_handle* h = NULL;
     CHECK(use_create(&cfg, 0, &h));
     CHECK(use_load_weight_blob(h, argv[1]));
+    use_handle* hg = NULL;                                                  /* NCSNpp(discriminative=True): GAN/generator/ncsnpp/model_wrapper.py:54 */
+    if (refine_path) {
+        use_config gcfg;
+        memset(&gcfg, 0, sizeof gcfg);
+        gcfg.nf = 128; gcfg.n_levels = 4; gcfg.num_res_blocks = 1; gcfg.n_freq = F;
+        { const int cm[4] = {1, 2, 2, 2}; memcpy(gcfg.ch_mult, cm, sizeof cm); }
+        gcfg.precision = cfg.precision;
+        gcfg.theta = 1.5f; gcfg.sigma_min = 0.05f; gcfg.sigma_max = 0.5f;
+        gcfg.input_channels = 2; gcfg.unconditional = 1; gcfg.no_sigma_scale = 1;
+        CHECK(use_create(&gcfg, 0, &hg));
+        CHECK(use_load_weight_blob(hg, refine_path));
+    }
 
     float* win = (float*)malloc(sizeof(float) * n_fft);                     /* periodic Hann (model_wrapper.py:14-20) */
     for (int n = 0; n < n_fft; ++n) win[n] = (float)(0.5 - 0.5 * cos(2.0 * M_PI * (double)n / (double)n_fft));
@@ -124,11 +147,25 @@ int main(int argc, char** argv) {
         return 1;
     }
     CHECK(use_istft_back(d_X, d_out, 1, (int)L, n_fft, hop, d_win, Tpad, factor, expo, NULL));
+    if (hg) {   /* the stage-1 file and the second run's loader, on the device and in place; then the generator over the same buffers */
+        const int len = (int)L;
+        const size_t work_bytes = use_wav_handoff_workspace(1, L);
+        void* d_work = NULL; double* d_peak = NULL;
+        HIPCHECK(hipMalloc(&d_work, work_bytes)); HIPCHECK(hipMalloc((void**)&d_peak, sizeof(double)));
+        CHECK(use_wav_handoff(d_out, d_out, L, &len, 1, USE_WAV_PCM16, 1, d_work, work_bytes, d_peak, NULL));
+        CHECK(use_stft_fwd(d_out, d_Y, 1, (int)L, n_fft, hop, d_win, Tpad, factor, expo, NULL));
+        CHECK(use_plan(hg, 1, Tpad));
+        CHECK(use_forward(hg, d_Y, NULL, NULL, d_X, NULL));
+        CHECK(use_istft_back(d_X, d_out, 1, (int)L, n_fft, hop, d_win, Tpad, factor, expo, NULL));
+        HIPCHECK(hipDeviceSynchronize());
+        hipFree(d_work); hipFree(d_peak);
+    }
     HIPCHECK(hipDeviceSynchronize());
     HIPCHECK(hipMemcpy(wav, d_out, L * 4, hipMemcpyDeviceToHost));
     CHECK(use_wav_write(argv[3], wav, L, 1, sr, USE_WAV_PCM16));
     printf("%s: %lld samples at %d Hz, %d frames (T' = %d), %d-step PC sampler -> %s\n", argv[2], (long long)L, sr, T, Tpad, N, argv[3]);
     if (n_chunks > 1) printf("sampled in %d windows of %d frames, %d frames of overlap\n", n_chunks, chunk_frames, chunk_overlap);
+    if (hg) { printf("refined by %s\n", refine_path); use_destroy(hg); }
     use_destroy(h); use_free(wav); free(win);
     hipFree(d_wav); hipFree(d_out); hipFree(d_win); hipFree(d_Y); hipFree(d_X);
     return 0;

@@ -285,6 +285,25 @@ size_t use_metrics_workspace(int B, int stride);
 int use_metrics(const float* est, const float* clean, const float* noise, const int* len_host, int B, int stride, void* work,
                 size_t work_bytes, double* out_dev, use_stream_t s);
 
+/* The hand-off between the two stages of the pipeline (SGMSE sampler, then the LSGAN refine generator), handle-free: what the two-run flow
+ * does to a stage-1 waveform between the writer of SGMSEModule.predict_step and the batch the stage-2 loader builds, on the device.  in / out:
+ * float32 DEVICE [B][stride] (out == in is allowed; any other overlap is not), item b valid for len_host[b] samples (HOST ints, as in
+ * use_metrics and use_stft_fwd_items; they travel as kernel arguments).  For m < len[b], v is formed from in[b][m] in fp64:
+ *   subtype USE_WAV_PCM16: q = nearbyint(x * 32767) clamped to [-32768, 32767] (what use_wav_write stores; a NaN is stored as 0), v = q / 32768
+ *   (what use_load_utterance reads back); USE_WAV_FLOAT32: v = x;
+ *   normalize != 0: mx = max |v| over the item by `fabs(v) > mx` (a NaN never becomes the peak), v = v / mx * 0.8 with two roundings (the
+ *   loader's peak normalisation; a silent item gives NaN, as the loader and the reference do);
+ * out[b][m] = (float)v, and out[b][m] = 0 for len[b] <= m < stride (the loader's zero padding).  Samples of `in` past len[b] are never read:
+ * after stage 1 they hold whatever the iSTFT left in the padding.  peak_dev: fp64 DEVICE [B], receives mx in either mode.  Every output
+ * sample has the bits the file round trip gives it, in every run, in any batch and at any stride (a maximum has no order; no atomics).
+ * Row offsets b * stride are 64-bit.  work: use_wav_handoff_workspace(B, stride) bytes of device scratch, 8-byte aligned (0: bad arguments).
+ * Two launches on `s` (+ one per 64 items for the lengths), no synchronisation, no allocation, nothing to zero between calls.
+ * USE_E_INVALID (argument named in use_last_error(), nothing launched): B < 1 or > 65535, stride < 1, a null in / out / len_host / work /
+ * peak_dev, len[b] < 1 or > stride, an unknown subtype, work_bytes too small. */
+size_t use_wav_handoff_workspace(int B, int64_t stride);
+int use_wav_handoff(const float* in, float* out, int64_t stride, const int* len_host, int B, int subtype /* USE_WAV_PCM16 | USE_WAV_FLOAT32 */,
+                    int normalize, void* work, size_t work_bytes, double* peak_dev, use_stream_t s);
+
 /* Counters of a handle: "graph_captures" (segments of the sampling loop captured so far), "plans_built", "plan_cache_hits", "ode_steps",
  * "ode_rejected", "ode_nfev_max" (of the last use_sample_ode),
  * "plans_parked", "plan_stale" (1: use_set_option was called since use_plan - the evaluation entry points will refuse the plan).  A handle keeps the plans - workspace, state, time-embedding tables, captured graphs - of the most recently used

@@ -7,12 +7,9 @@ training is out of scope).
 """
 from __future__ import annotations
 
-import os
-
-import numpy as np
 import torch
 
-from .SGMSE_module import _Base, _write_wav
+from .SGMSE_module import _Base, _write_items
 
 
 class GANModule(_Base):
@@ -37,15 +34,7 @@ class GANModule(_Base):
     @torch.no_grad()
     def predict_step(self, batch: dict, batch_idx: int = 0) -> dict:
         batch = self.G(batch, **self.sampler_kwargs)
-        for i, fake in enumerate(batch["fake"]):
-            if "audio_path" not in batch:
-                continue
-            noisy_path = batch["audio_path"][i]
-            sample_length = int(batch["sample_length"][i])
-            sample_rate = batch["sampling_rate"][i]
-            enhanced_path = noisy_path.replace(batch["data_folder"], batch["target_folder"])
-            os.makedirs(os.path.dirname(enhanced_path) or ".", exist_ok=True)
-            _write_wav(enhanced_path, fake.detach().cpu().numpy().astype(np.float32)[:sample_length], sample_rate, self.wav_subtype)
+        _write_items(batch, batch["fake"], batch.get("target_folder"), self.wav_subtype)
         return batch
 
     def training_step(self, *a, **k):

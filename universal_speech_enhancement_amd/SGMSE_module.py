@@ -22,6 +22,34 @@ def _write_wav(path: str, wav: np.ndarray, sr: int, subtype: str = "PCM_16"):
     write_wav(path, wav, int(sr), PCM16 if subtype == "PCM_16" else FLOAT32)
 
 
+def _with_path_seeds(sampler_kwargs: dict, batch: dict) -> dict:
+    """The keywords of ``Score.sample`` for one batch of ``predict_step``: under ``per_item`` (and without ``item_seeds`` of the
+    caller's) every file gets the seed named by its path."""
+    kw = dict(sampler_kwargs)
+    if kw.get("per_item") and kw.get("item_seeds") is None and "audio_path" in batch:
+        # batch-invariant sampling: a file's noise is named by its path relative to data_folder, so that its output does not depend
+        # on the batch order, on batch_size or on how the files are sharded over the ranks - at equal padded length T', or for any
+        # mix of lengths with own_length (every file at its own T')
+        from .seeding import item_seed, path_key
+        kw["item_seeds"] = [item_seed(int(kw.get("seed", 0)), path_key(os.path.relpath(p, batch["data_folder"]).replace(os.sep, "/")))
+                            for p in batch["audio_path"]]
+    return kw
+
+
+def _write_items(batch: dict, wavs, folder, subtype: str):
+    """Item i of ``wavs``, trimmed to ``sample_length[i]``, to ``audio_path[i].replace(data_folder, folder)`` (reference
+    SGMSE_module.py:72-80); a batch without ``audio_path`` writes nothing."""
+    if "audio_path" not in batch:
+        return
+    for i, wav in enumerate(wavs):
+        noisy_path = batch["audio_path"][i]
+        sample_length = int(batch["sample_length"][i])
+        sample_rate = batch["sampling_rate"][i]
+        path = noisy_path.replace(batch["data_folder"], folder)
+        os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+        _write_wav(path, wav.detach().cpu().numpy().astype(np.float32)[:sample_length], sample_rate, subtype)
+
+
 try:                                                     # reference: class SGMSEModule(LightningModule), SGMSE_module.py:10
     from lightning import LightningModule as _Base
     HAS_LIGHTNING = True
@@ -49,25 +77,8 @@ class SGMSEModule(_Base):
 
     @torch.no_grad()
     def predict_step(self, batch: dict, batch_idx: int = 0) -> dict:
-        kw = dict(self.sampler_kwargs)
-        if kw.get("per_item") and kw.get("item_seeds") is None and "audio_path" in batch:
-            # batch-invariant sampling: a file's noise is named by its path relative to data_folder, so that its output does not depend
-            # on the batch order, on batch_size or on how the files are sharded over the ranks - at equal padded length T', or for any
-            # mix of lengths with own_length (every file at its own T')
-            from .seeding import item_seed, path_key
-            kw["item_seeds"] = [item_seed(int(kw.get("seed", 0)), path_key(os.path.relpath(p, batch["data_folder"]).replace(os.sep, "/")))
-                                for p in batch["audio_path"]]
-        batch = self.Score.sample(batch, **kw)
-        for i, enhanced in enumerate(batch["enhanced"]):
-            if "audio_path" not in batch:
-                continue
-            noisy_path = batch["audio_path"][i]
-            sample_length = int(batch["sample_length"][i])
-            sample_rate = batch["sampling_rate"][i]
-            enhanced_path = noisy_path.replace(batch["data_folder"], batch["target_folder"])
-            os.makedirs(os.path.dirname(enhanced_path) or ".", exist_ok=True)
-            wav = enhanced.detach().cpu().numpy().astype(np.float32)[:sample_length]
-            _write_wav(enhanced_path, wav, sample_rate, self.wav_subtype)
+        batch = self.Score.sample(batch, **_with_path_seeds(self.sampler_kwargs, batch))
+        _write_items(batch, batch["enhanced"], batch.get("target_folder"), self.wav_subtype)
         return batch
 
     def get_score_loss(self, batch: dict) -> torch.Tensor:

@@ -139,6 +139,9 @@ void launch_chunk_merge(const float2* chunks, float2* X, int B, int F, int n, in
 // (float32 device, noise nullable: ratios NaN) with HOST lengths 256 <= len[b] <= stride; out [B][4] fp64 (device).  `work`:
 // metrics_layout(B, stride).bytes of 8-byte aligned scratch.  Six launches on `s` (+ one per 64 items for the lengths), no
 // synchronisation, no atomics.  The caller has checked the arguments (B <= 65535).
+// lens[b] = len_host[b], b < B: HOST ints to a device array as kernel arguments, one launch per 64 items on `s` (use_metrics.hip; also
+// the hand-off's, use_handoff.hip)
+void launch_item_lengths(int* lens, const int* len_host, int B, hipStream_t s);
 constexpr int METRICS_SLICE = 2048;                        // samples per workgroup of the two streaming passes
 struct MetricsWork { size_t part1, part2, alpha, lsd, bytes; int nblk, Tmax; };    // byte offsets behind the int lens[B]
 MetricsWork metrics_layout(int B, int stride);

@@ -43,7 +43,7 @@ __device__ __forceinline__ double sum_partials(const double* p, int n, int step,
 }
 
 struct LenPack { int v[64]; };
-__global__ void metrics_lens_kernel(int* lens, LenPack p, int base, int B) {
+__global__ void item_lengths_kernel(int* lens, LenPack p, int base, int B) {
     const int i = threadIdx.x;
     if (base + i < B) lens[base + i] = p.v[i];
 }
@@ -151,6 +151,14 @@ __global__ __launch_bounds__(256) void metrics_final_kernel(const double* __rest
 }
 }  // namespace
 
+void launch_item_lengths(int* lens, const int* len_host, int B, hipStream_t s) {
+    for (int b0 = 0; b0 < B; b0 += 64) {                      // the lengths travel as kernel arguments: no copy, no synchronisation
+        LenPack p{};
+        for (int i = 0; i < 64 && b0 + i < B; ++i) p.v[i] = len_host[b0 + i];
+        hipLaunchKernelGGL(item_lengths_kernel, dim3(1), dim3(64), 0, s, lens, p, b0, B);
+    }
+}
+
 MetricsWork metrics_layout(int B, int stride) {
     MetricsWork w;
     w.nblk = (stride + METRICS_SLICE - 1) / METRICS_SLICE;
@@ -173,11 +181,7 @@ void launch_metrics(const float* est, const float* clean, const float* noise, co
     double* part2 = reinterpret_cast<double*>(base + w.part2);
     double* alpha = reinterpret_cast<double*>(base + w.alpha);
     double* lsd = reinterpret_cast<double*>(base + w.lsd);
-    for (int b0 = 0; b0 < B; b0 += 64) {                      // the lengths travel as kernel arguments: no copy, no synchronisation
-        LenPack p{};
-        for (int i = 0; i < 64 && b0 + i < B; ++i) p.v[i] = len_host[b0 + i];
-        hipLaunchKernelGGL(metrics_lens_kernel, dim3(1), dim3(64), 0, s, lens, p, b0, B);
-    }
+    launch_item_lengths(lens, len_host, B, s);
     const dim3 pass_grid(w.nblk, B), lsd_grid(w.Tmax, B);     // the caller has checked B <= 65535 (gridDim.y)
     hipLaunchKernelGGL(metrics_lsd_kernel, lsd_grid, dim3(256), 0, s, est, clean, lens, lsd, stride, w.Tmax);
     if (noise) {

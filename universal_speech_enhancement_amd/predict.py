@@ -14,6 +14,15 @@
                                                  (every file at its own padded frame count T' instead of its batch's longest: with
                                                   per_item a file's output is that of its batch-size-1 run, for any mix of lengths;
                                                   bucket_by_length orders a rank's files by T' so that batches are full at one T')
+    python -m universal_speech_enhancement_amd.predict model=USE ckpt_path=score.ckpt refine_ckpt_path=lsgan.ckpt \
+        data.data_folder=noisy/ data.target_folder=refined/
+                                                 (both stages in one run: the sampler, the hand-off on the device - what the stage-1 file,
+                                                  its 16-bit samples and the second run's loader do to the audio - and the refine generator;
+                                                  the refined files are byte for byte those of model=SGMSE_Large followed by model=LSGAN.
+                                                  model.sampler_kwargs as above, passed on to the generator where it takes them;
+                                                  [model.handoff_subtype=FLOAT] hands over unquantised samples; [model.stage1_folder=enhanced/]
+                                                  keeps the stage-1 files as well; each checkpoint a Lightning .ckpt or a packed .usehip file)
+    Options of every model:
         [data.clean_folder=clean/]               (score every enhanced file whose clean counterpart exists under clean/ at the same
                                                   relative path: SI-SDR / SI-SIR / SI-SAR / LSD on the device -> enhanced/metrics.csv)
 
@@ -111,15 +120,42 @@ def _score_batch(batch: dict, clean_folder: str, data_cfg: dict, device):
     return rows
 
 
+def _load_pipeline_weights(model, cfg: dict, device):
+    """``model=USE``: ``ckpt_path`` serves the score network and ``refine_ckpt_path`` the generator, each a Lightning ``.ckpt`` or a
+    packed ``.usehip`` file; without either, ``random_init_seed=S`` gives both networks the weights the two single-stage dry runs get
+    from the same seed."""
+    stages = (("score", "ckpt_path", model.Score.score_net, model.Score), ("refine", "refine_ckpt_path", model.G.net, model.G))
+    paths = [cfg.get(key) for _, key, _, _ in stages]
+    if not any(paths):
+        if cfg.get("random_init_seed") is None:
+            raise SystemExit("ckpt_path and refine_ckpt_path are required (or random_init_seed=<int> for a dry run)")
+        from .testing.weights import LARGE, REFINE, make_state_dict
+        for (_, _, net, _), arch in zip(stages, (LARGE, REFINE)):
+            net.load_state_dict({k: torch.from_numpy(v) for k, v in make_state_dict(int(cfg["random_init_seed"]), **arch).items()})
+        return
+    for (_, key, _, _), path in zip(stages, paths):
+        if not path:
+            raise SystemExit(f"model=USE needs both ckpt_path (the score network) and refine_ckpt_path (the generator): {key} is missing")
+    for (stage, key, net, owner), path in zip(stages, paths):
+        if str(path).endswith(".usehip"):
+            net.load_weight_file(path, n_freq=int(owner.n_fft) // 2 + 1, device=device)
+        else:
+            model.load_lightning_checkpoint(path, stage)
+
+
 def predict(cfg: dict):
     rank, world, local = D.init_from_env()
     torch.cuda.set_device(local)
     data = instantiate(cfg["data"], rank=rank, world_size=world)
     model = instantiate(cfg["model"])
-    owner = model.G if hasattr(model, "G") else model.Score                # the module that carries n_fft and hop_length
-    if cfg.get("ckpt_path") and str(cfg["ckpt_path"]).endswith(".usehip"):   # packed weight file (pack_checkpoint)
+    device = torch.device("cuda", local)
+    both = hasattr(model, "G") and hasattr(model, "Score")   # model=USE: the two stages in one run
+    owner = model.Score if both else model.G if hasattr(model, "G") else model.Score   # the module that carries n_fft and hop_length
+    if both:
+        _load_pipeline_weights(model, cfg, device)
+    elif cfg.get("ckpt_path") and str(cfg["ckpt_path"]).endswith(".usehip"):   # packed weight file (pack_checkpoint)
         net = model.G.net if hasattr(model, "G") else model.Score.score_net
-        net.load_weight_file(cfg["ckpt_path"], n_freq=int(owner.n_fft) // 2 + 1, device=torch.device("cuda", local))
+        net.load_weight_file(cfg["ckpt_path"], n_freq=int(owner.n_fft) // 2 + 1, device=device)
     elif cfg.get("ckpt_path"):
         model.load_lightning_checkpoint(cfg["ckpt_path"])
     elif cfg.get("random_init_seed") is not None:
@@ -133,11 +169,11 @@ def predict(cfg: dict):
     clean_folder = cfg["data"].get("clean_folder")           # off by default: nothing below runs, no CSV is written
     rows = []
     with torch.no_grad():
-        for i, batch in enumerate(data.predict_batches(device=torch.device("cuda", local), frame_hop=owner.hop_length)):
+        for i, batch in enumerate(data.predict_batches(device=device, frame_hop=owner.hop_length)):
             model.predict_step(batch, i)
             n += len(batch["name"])
             if clean_folder:
-                rows += _score_batch(batch, clean_folder, cfg["data"], torch.device("cuda", local))
+                rows += _score_batch(batch, clean_folder, cfg["data"], device)
     if clean_folder:
         from .metrics import write_csv
         write_csv(os.path.join(cfg["data"]["target_folder"], "metrics.csv" if world == 1 else f"metrics_rank{rank}.csv"), rows)
