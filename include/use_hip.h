@@ -304,6 +304,37 @@ size_t use_wav_handoff_workspace(int B, int64_t stride);
 int use_wav_handoff(const float* in, float* out, int64_t stride, const int* len_host, int B, int subtype /* USE_WAV_PCM16 | USE_WAV_FLOAT32 */,
                     int normalize, void* work, size_t work_bytes, double* peak_dev, use_stream_t s);
 
+/* The convergence part of the refine stage's generator criterion, forward only and handle-free (reference
+ * loss_function/monaural_loss.py:59-178, WavSpecConvergence_Loss; the same arithmetic inside WavSpecConvergence_HIFIGAN_Vocoder_G_Loss, which
+ * LSGAN.yaml selects).  est, clean: float32 DEVICE [B][stride], item b valid for len_host[b] samples (HOST ints, as in use_metrics; the rest of a
+ * row is never read).  out_dev: fp64 DEVICE [B][USE_SPECLOSS_COUNT], per item and unweighted - the reference's values at batch size 1 on exactly
+ * those samples:
+ *   [USE_SPECLOSS_WAV_L1]        mean |e - c|
+ *   [USE_SPECLOSS_MAG_L2 + r]    l2_r   = mean (Me - Mc)^2
+ *   [USE_SPECLOSS_MAG_LOG + r]   log_r  = mean |log(32768 Me + 1e-6) - log(32768 Mc + 1e-6)|
+ *   [USE_SPECLOSS_MAG_NORM + r]  norm_r = sqrt(sum (Mc - Me)^2) / (sqrt(sum Mc^2) + 1e-6)
+ *   [USE_SPECLOSS_MEL_LOG], [USE_SPECLOSS_MEL_L2]   the log and l2 formulas on the mel maps
+ * r = 0..3 in ascending n_fft: Me, Mc the magnitude Spectrograms with n_fft = int(512 q), int(1024 q), int(2048 q), int(4096 q), q =
+ * sampling_rate / 48000 (256 ... 2048 at 24 kHz, 512 ... 4096 at 48 kHz), win_length n_fft, hop n_fft / 4, periodic Hann, power 1, centred,
+ * reflect padding, one-sided, not normalised: n_fft / 2 + 1 bins x (1 + len / hop) frames.  Mel maps: the MelSpectrogram with n_fft 2048,
+ * win_length int(0.025 sr) (periodic Hann, centred in the frame with zeros either side), hop int(0.010 sr), power 1, 128 HTK bands from 0 to
+ * sr / 2, norm None (torchaudio's melscale_fbanks: triangles between 130 points equally spaced in mel, over linspace(0, sr / 2, 1025)).
+ * The reference's six terms are wav_l1, mag_l2 = sum_r l2_r (a sum, not a mean), mag_log = mean_r log_r, mag_norm_l2 = mean_r norm_r, mel_log,
+ * mel_l2; their weighting (alpha_*) and the mean over a batch are the caller's (universal_speech_enhancement_amd/losses.py).
+ * Precision: float32 samples in; window, transform (a real FFT per frame), magnitude, log, filter bank, products and sums in fp64 - the
+ * float64 evaluation of the reference's formulas.  est == clean gives exactly 0 in all 15.  Every sum has a fixed order that depends on len[b]
+ * alone: an item's 15 values are the same bits in any batch, at any stride, in every run (no atomics).  Row offsets b * stride are 64-bit.
+ * work: use_spec_losses_workspace(B, stride, sampling_rate) bytes of device scratch, 8-byte aligned (0: bad arguments).  Eight launches on `s`
+ * (+ one per 64 items for the lengths), no synchronisation, no allocation, nothing to zero between calls.  USE_E_INVALID (argument named in
+ * use_last_error(), nothing launched): a sampling_rate other than 24000 / 48000 (the rates at which all four frame lengths are powers of two),
+ * B < 1 or > 65535, stride < 1, a null est / clean / len_host / work / out_dev, len[b] <= n_max / 2 (reflect padding; the minimum is 1025 at
+ * 24 kHz, 2049 at 48 kHz) or > stride, work_bytes too small. */
+enum { USE_SPECLOSS_WAV_L1 = 0, USE_SPECLOSS_MAG_L2 = 1, USE_SPECLOSS_MAG_LOG = 5, USE_SPECLOSS_MAG_NORM = 9,
+       USE_SPECLOSS_MEL_LOG = 13, USE_SPECLOSS_MEL_L2 = 14, USE_SPECLOSS_COUNT = 15 };
+size_t use_spec_losses_workspace(int B, int64_t stride, int sampling_rate);
+int use_spec_losses(const float* est, const float* clean, const int* len_host, int B, int64_t stride, int sampling_rate,
+                    void* work, size_t work_bytes, double* out_dev, use_stream_t s);
+
 /* Counters of a handle: "graph_captures" (segments of the sampling loop captured so far), "plans_built", "plan_cache_hits", "ode_steps",
  * "ode_rejected", "ode_nfev_max" (of the last use_sample_ode),
  * "plans_parked", "plan_stale" (1: use_set_option was called since use_plan - the evaluation entry points will refuse the plan).  A handle keeps the plans - workspace, state, time-embedding tables, captured graphs - of the most recently used

@@ -25,6 +25,9 @@
     Options of every model:
         [data.clean_folder=clean/]               (score every enhanced file whose clean counterpart exists under clean/ at the same
                                                   relative path: SI-SDR / SI-SIR / SI-SAR / LSD on the device -> enhanced/metrics.csv)
+        [data.clean_folder=clean/ data.convergence_losses=true]
+                                                 (the same files against the refine stage's training objective, forward only: waveform
+                                                  L1, multi-resolution STFT and log-mel distances on the device -> enhanced/losses.csv)
 
 Hydra and Lightning are not available on the target image, so this is a small stand-in: the same YAML groups
 (``configs/predict.yaml`` -> ``data/``, ``model/``), ``key=value`` / ``group=name`` overrides, ``_target_`` instantiation,
@@ -120,6 +123,20 @@ def _score_batch(batch: dict, clean_folder: str, data_cfg: dict, device):
     return rows
 
 
+def _loss_batch(batch: dict, clean_folder: str, data_cfg: dict, device):
+    """``data.convergence_losses``: (relative path, convergence losses) of the files ``_score_batch`` scores (``losses.score_files``)."""
+    from .losses import score_files
+    rows = []
+    for noisy_path in batch["audio_path"]:
+        rel = os.path.relpath(noisy_path, batch["data_folder"])
+        clean_path = os.path.join(clean_folder, rel)
+        if os.path.isfile(clean_path):
+            enhanced_path = noisy_path.replace(batch["data_folder"], batch["target_folder"])
+            rows.append((rel, score_files(enhanced_path, clean_path, int(data_cfg.get("sampling_rate", 24000) or 0),
+                                          bool(data_cfg.get("normalize", True)), device)))
+    return rows
+
+
 def _load_pipeline_weights(model, cfg: dict, device):
     """``model=USE``: ``ckpt_path`` serves the score network and ``refine_ckpt_path`` the generator, each a Lightning ``.ckpt`` or a
     packed ``.usehip`` file; without either, ``random_init_seed=S`` gives both networks the weights the two single-stage dry runs get
@@ -144,6 +161,9 @@ def _load_pipeline_weights(model, cfg: dict, device):
 
 
 def predict(cfg: dict):
+    with_losses = bool(cfg["data"].get("convergence_losses"))   # off by default: nothing of it runs, no losses.csv is written
+    if with_losses and not cfg["data"].get("clean_folder"):
+        raise SystemExit("data.convergence_losses=true needs data.clean_folder=<the folder of the clean files>")
     rank, world, local = D.init_from_env()
     torch.cuda.set_device(local)
     data = instantiate(cfg["data"], rank=rank, world_size=world)
@@ -167,16 +187,21 @@ def predict(cfg: dict):
         raise SystemExit("ckpt_path is required (or random_init_seed=<int> for a dry run)")
     n = 0
     clean_folder = cfg["data"].get("clean_folder")           # off by default: nothing below runs, no CSV is written
-    rows = []
+    rows, loss_rows = [], []
     with torch.no_grad():
         for i, batch in enumerate(data.predict_batches(device=device, frame_hop=owner.hop_length)):
             model.predict_step(batch, i)
             n += len(batch["name"])
             if clean_folder:
                 rows += _score_batch(batch, clean_folder, cfg["data"], device)
+            if with_losses:
+                loss_rows += _loss_batch(batch, clean_folder, cfg["data"], device)
     if clean_folder:
         from .metrics import write_csv
         write_csv(os.path.join(cfg["data"]["target_folder"], "metrics.csv" if world == 1 else f"metrics_rank{rank}.csv"), rows)
+    if with_losses:
+        from .losses import write_csv as write_losses_csv
+        write_losses_csv(os.path.join(cfg["data"]["target_folder"], "losses.csv" if world == 1 else f"losses_rank{rank}.csv"), loss_rows)
     print(f"[rank {rank}] enhanced {n} file(s) -> {cfg['data']['target_folder']}")
     return n
 
