@@ -194,7 +194,11 @@ int use_ode_num_groups(use_ode* o);
 int use_ode_destroy(use_ode* o);
 
 /* Element-wise SDE pieces for callers that drive the loop themselves through the reference's
- * Predictor / Corrector registries (uniform t over the batch). n = number of complex elements. */
+ * Predictor / Corrector registries (uniform t over the batch). n = number of complex elements.
+ * USE_E_INVALID (argument named in use_last_error(), nothing launched): a null handle; a null y / x or n < 1 in use_sde_prior; an unknown
+ * predictor id, a null x / y / score / x_out or n < 1 in use_sde_predictor; a null x / score / x_out, n < 1, B < 1, n no multiple of B,
+ * an unknown corrector id or (Langevin) B > 1024 in use_sde_corrector.  noise (NULL: drawn on the device from `seed`) and x_mean may be
+ * null. */
 int use_sde_prior(use_handle* h, const void* y, const void* noise, uint64_t seed, void* x, int64_t n, use_stream_t s);
 int use_sde_predictor(use_handle* h, int predictor, float t, int N, const void* x, const void* y, const void* score,
                       const void* noise, uint64_t seed, void* x_out, void* x_mean, int64_t n, use_stream_t s);
@@ -205,7 +209,10 @@ int use_sde_corrector(use_handle* h, int corrector, float t, float snr, int B, c
  * [B,1,F,T']) = the z that draw `draw` uses at element i -- draw 0 is the prior's randn_like (sdes.py:254), then per reverse step the
  * corrector draws (sampling/correctors.py:54) followed by the predictor draw (sampling/predictors.py:63), the reference's order of
  * consumption.  use_sample(noise = [use_fill_noise(seed, d) for d in 0..use_num_noise_draws-1]) is bit-identical to
- * use_sample(noise = NULL, seed): this is how the timed (device-noise) branch is pinned to the oracle in tests/. */
+ * use_sample(noise = NULL, seed): this is how the timed (device-noise) branch is pinned to the oracle in tests/.
+ * The generator: (c0, c1, c2, c3) = Philox4x32-10(counter = (i low, i high, draw low, draw high), key = (seed low, seed high));
+ * u1, u2 = ((float)(c0 >> 8) + 0.5f) 2^-24, ((float)(c1 >> 8) + 0.5f) 2^-24, both in (0, 1] (the + 0.5f rounds to even above 2^23, so 1.0
+ * occurs); z = sqrt(-ln u1) (cos, sin)(2 pi u2) in float32 (Box-Muller at variance 1/2 per component). */
 int use_fill_noise(use_handle* h, uint64_t seed, int draw, void* out, int64_t n, use_stream_t s);
 
 /* The noise of use_sample_items, draw by draw: out (complex64, n elements = B items of n / B) = item b's z from seeds_host[b]

@@ -2057,6 +2057,9 @@ int use_istft_back_items(const void* X, float* wav, int64_t stride, const int* l
 
 int use_sde_prior(use_handle* h, const void* y, const void* noise, uint64_t seed, void* x, int64_t n, use_stream_t s) {
     int rc = ensure_sde_scratch(h); if (rc) return rc;
+    if (!y) return fail(USE_E_INVALID, "use_sde_prior: y is null");
+    if (!x) return fail(USE_E_INVALID, "use_sde_prior: x is null");
+    if (n < 1) return fail(USE_E_INVALID, "use_sde_prior: n=%lld must be positive", (long long)n);
     hipLaunchKernelGGL(set_rng_kernel, dim3(1), dim3(1), 0, (hipStream_t)s, h->sde_rng, (unsigned long long)seed, 0ull);
     launch_prior((const float2*)y, (const float2*)noise, RngRef{h->sde_rng, 0}, ouve_std(h->cfg, 1.0f), (float2*)x, n, (hipStream_t)s);
     HIPCHK(hipGetLastError());
@@ -2075,7 +2078,8 @@ int use_fill_noise_items(use_handle* h, const uint64_t* seeds_host, int B, int d
 }
 
 int use_fill_noise(use_handle* h, uint64_t seed, int draw, void* out, int64_t n, use_stream_t s) {
-    // draw `draw` of the device noise stream of use_sample(noise = NULL, seed): element i = Philox4x32-10(key = seed, counter = (i, draw))
+    // draw `draw` of the device noise stream of use_sample(noise = NULL, seed): element i = Philox4x32-10(key = seed, counter = (i, draw)),
+    // Box-Muller on two uniforms u in (0, 1] (24 high bits + 0.5, rounded to float32: 1.0 occurs)
     int rc = ensure_sde_scratch(h); if (rc) return rc;
     if (!out || n < 1 || draw < 0) return fail(USE_E_INVALID, "bad arguments");
     hipLaunchKernelGGL(set_rng_kernel, dim3(1), dim3(1), 0, (hipStream_t)s, h->sde_rng, (unsigned long long)seed, 0ull);
@@ -2088,6 +2092,11 @@ int use_sde_predictor(use_handle* h, int predictor, float t, int N, const void* 
                       const void* noise, uint64_t seed, void* x_out, void* x_mean, int64_t n, use_stream_t s) {
     int rc = ensure_sde_scratch(h); if (rc) return rc;
     if (predictor != USE_PRED_REVERSE_DIFFUSION && predictor != USE_PRED_EULER_MARUYAMA) return fail(USE_E_INVALID, "predictor id %d has no update kernel", predictor);
+    if (!x) return fail(USE_E_INVALID, "use_sde_predictor: x is null");
+    if (!y) return fail(USE_E_INVALID, "use_sde_predictor: y is null");
+    if (!score) return fail(USE_E_INVALID, "use_sde_predictor: score is null");
+    if (!x_out) return fail(USE_E_INVALID, "use_sde_predictor: x_out is null");
+    if (n < 1) return fail(USE_E_INVALID, "use_sde_predictor: n=%lld must be positive", (long long)n);
     float cd, cs, cn; predictor_coeffs(h->cfg, predictor, t, N, cd, cs, cn);
     hipLaunchKernelGGL(set_rng_kernel, dim3(1), dim3(1), 0, (hipStream_t)s, h->sde_rng, (unsigned long long)seed, 0ull);
     launch_predictor((const float2*)x, (const float2*)y, (const float2*)score, (const float2*)noise, RngRef{h->sde_rng, 0},
@@ -2100,18 +2109,24 @@ int use_sde_corrector(use_handle* h, int corrector, float t, float snr, int B, c
                       const void* noise, uint64_t seed, void* x_out, void* x_mean, int64_t n, use_stream_t st) {
     int rc = ensure_sde_scratch(h); if (rc) return rc;
     hipStream_t s = (hipStream_t)st;
+    if (!x) return fail(USE_E_INVALID, "use_sde_corrector: x is null");
+    if (!score) return fail(USE_E_INVALID, "use_sde_corrector: score is null");
+    if (!x_out) return fail(USE_E_INVALID, "use_sde_corrector: x_out is null");
+    if (n < 1) return fail(USE_E_INVALID, "use_sde_corrector: n=%lld must be positive", (long long)n);
     if (B < 1 || n % B != 0) return fail(USE_E_INVALID, "n must be a multiple of B");
+    // every refusal comes before the first launch (the seed word is written by a kernel)
+    if (corrector != USE_CORR_LANGEVIN && corrector != USE_CORR_ALD) return fail(USE_E_INVALID, "corrector id %d has no update kernel", corrector);
+    if (corrector == USE_CORR_LANGEVIN && B > use_handle::SDE_MAX_B) return fail(USE_E_INVALID, "B=%d exceeds %d", B, use_handle::SDE_MAX_B);
     hipLaunchKernelGGL(set_rng_kernel, dim3(1), dim3(1), 0, s, h->sde_rng, (unsigned long long)seed, 0ull);
     RngRef rr{h->sde_rng, 0};
     if (corrector == USE_CORR_LANGEVIN) {
-        if (B > use_handle::SDE_MAX_B) return fail(USE_E_INVALID, "B=%d exceeds %d", B, use_handle::SDE_MAX_B);
         launch_langevin_norms((const float2*)score, (const float2*)noise, rr, h->sde_partial, B, n / B, use_handle::SDE_BLOCKS, s);
         launch_langevin_step(h->sde_partial, B, use_handle::SDE_BLOCKS, snr, h->sde_step, s);
         launch_corrector((const float2*)x, (const float2*)score, (const float2*)noise, rr, h->sde_step, 0.f, (float2*)x_out, (float2*)x_mean, n, s);
-    } else if (corrector == USE_CORR_ALD) {
+    } else {
         const float sd = snr * ouve_std(h->cfg, t);
         launch_corrector((const float2*)x, (const float2*)score, (const float2*)noise, rr, nullptr, sd * sd * 2.f, (float2*)x_out, (float2*)x_mean, n, s);
-    } else return fail(USE_E_INVALID, "corrector id %d has no update kernel", corrector);
+    }
     HIPCHK(hipGetLastError());
     return USE_OK;
 }

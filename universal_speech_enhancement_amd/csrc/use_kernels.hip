@@ -2039,7 +2039,7 @@ DEVI float2 philox_cnormal(unsigned long long seed, unsigned long long draw, uns
     unsigned k[2] = {(unsigned)seed, (unsigned)(seed >> 32)};
 #pragma unroll
     for (int r = 0; r < 10; ++r) philox_round(c, k);
-    const float u1 = ((float)(c[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);   // (0,1)
+    const float u1 = ((float)(c[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);   // (0,1]: + 0.5f rounds above 2^23
     const float u2 = ((float)(c[1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
     const float r = sqrtf(-logf(u1));           // sqrt(-2 ln u) * sqrt(1/2)
     float sn, cs;
