@@ -140,8 +140,9 @@ int use_sample_cond2(use_handle* h, const void* y, const void* cond, const void*
  * changes what the network sees, so batches padded to different lengths are outside the guarantee.  At B > 1 this reproduces the
  * reference run per file (batch size 1), not the reference at batch size B.  (For this the per-item loop also makes the one
  * batch-size-dependent kernel choice of the network, conv_sk's tile form, from the per-image shape - DESIGN.md section 1.)
+ * The update kernels are those of use_sample*, addressed as B items of F*T' elements instead of one item of all B*F*T'.
  * noise != NULL: injected draws in use_sample's layout (per item already).  Otherwise seeds_host: HOST array of B seeds, copied to
- * a device array of the plan before the call returns and read there by the kernels, so captured graphs replay with new seeds.
+ * the seed array of the plan before the call returns and read there by the kernels, so captured graphs replay with new seeds.
  * Both NULL: USE_E_INVALID.  The per-item loop has its own captured graphs beside those of use_sample*; neither form drops the
  * other's, and "graph_captures" counts both. */
 int use_sample_items(use_handle* h, const void* y, const void* cond, const void* cond2, const void* noise,

@@ -1,5 +1,5 @@
 """The device noise generator and the element-wise SDE updates, one launch at a time through the C ABI, against an integer restatement of
-Philox4x32-10 and float64 restatements of the OUVE updates (tests/philox_ref.py): fill_noise_kernel, fill_noise_items_kernel,
+Philox4x32-10 and float64 restatements of the OUVE updates (tests/philox_ref.py): fill_noise_kernel (as one item and per item),
 prior_kernel, predictor_kernel, langevin_norms_kernel + langevin_step_kernel, corrector_kernel.  Same construction as
 tests/test_hip_forward_kernels.py: every reference sees the operands the kernel sees and rounds where the kernel rounds; every bound is
 per element and per real component, was fixed before the first GPU run and is not fitted.  2^-24 is the float32 unit roundoff; every
@@ -36,7 +36,7 @@ global element (item 0 is exempt: its offset is 0); norm of the batch mean for m
 sqrt(eps) for sqrt(2 eps), x_mean carrying the noise term.
 
 Measured on the MI355X (2026-10-19, this file's first commit, on f35ed92), worst |err| / bound: fill_noise_kernel 0.665 (0.817 past the
-grid-stride wrap), fill_noise_items_kernel 0.881, prior_kernel 0.981 (0.838 with device noise), predictor_kernel 0.977, corrector_kernel
+grid-stride wrap), per item 0.881, prior_kernel 0.981 (0.838 with device noise), predictor_kernel 0.977, corrector_kernel
 Langevin 0.995 (0.999 on the device's own noise), ALD 0.996, the Langevin step size alone (x = 0) 0.099.  The updates' worst elements are output roundings at the bottom
 of a binade, where half a spacing is 2^-24 |ref| itself.  No constant changed after a measurement.  There is no float32 emulation here:
 these bounds count worst-case roundings and need none.  The GPU tests' output buffers start as NaN with a guard element behind them,
@@ -57,7 +57,7 @@ DRAWS = (0, 1, 60, 2 ** 31 - 1)
 SIZES = (1, 255, 257)
 N_WRAP = 8192 * 256 + 300                                   # past fill_noise_kernel's grid-stride wrap
 ITEM_SEEDS = (0x0123456789ABCDEF, 7, 2 ** 64 - 1)
-N_ITEM_WRAP = 2730 * 256 + 5                                # past fill_noise_items_kernel's wrap at B = 3 (8192 / 3 = 2730 blocks)
+N_ITEM_WRAP = 2730 * 256 + 5                                # past fill_noise_kernel's wrap per item at B = 3 (8192 / 3 = 2730 blocks)
 SHAPES = ((3, 1, 33, 7), (2, 1, 512, 64))
 GAINS = {3: (1e-2, 1.0, 10.0), 2: (1e-2, 10.0)}             # three decades between the items
 TS, NS, SNR = (1.0, 0.4, 0.03), (30, 1), 0.5
@@ -311,7 +311,7 @@ def test_fill_noise_items_values_and_one_item_bits(eng):
     got = got[:B * n].reshape(B, n)
     re, im, b = pr.fill_noise_items(ITEM_SEEDS, 1, n)
     worst = pr.ratio(got, re + 1j * im, b, b)
-    print(f"[measured] fill_noise_items_kernel worst |err| / bound {worst:.3f}")
+    print(f"[measured] fill_noise_kernel per item worst |err| / bound {worst:.3f}")
     assert worst <= 1.0
     for i, s in enumerate(ITEM_SEEDS):
         assert np.array_equal(got[i].view(np.uint32), _fill(eng, s, 1, n).view(np.uint32)), f"item {i} != use_fill_noise(seeds[{i}])"

@@ -138,10 +138,10 @@ struct use_handle {
     float2 *cond_buf = nullptr, *cond2_buf = nullptr;   // cond2: the second conditioning spectrogram of condition="both" (6 input channels)
     int pcp = 4;                                 // input / pyramid channels as stored: the reference's 2, 4 or 6 zero-padded to 4 or 8
     float2 *Cond = nullptr;                      // score conditioning of the sampler: == Y unless use_sample_cond gave another
-    float *lang_partial = nullptr, *lang_step = nullptr;
-    unsigned long long* rng_state = nullptr;
-    unsigned long long* item_seeds = nullptr;    // [B] per-item Philox seeds of use_sample_items (read by the kernels: graphs replay with new seeds)
-    float* item_step = nullptr;                  // [B] per-item Langevin steps
+    float *lang_partial = nullptr;
+    float* lang_step = nullptr;                  // [B] Langevin steps: one per item (use_sample_items), or [0] for the batch
+    unsigned long long* seeds = nullptr;         // [B] Philox seeds: one per item, or [0] for the shared stream.  Every call uploads its own
+                                                 // before its launches; the kernels read them, so graphs replay with new seeds
     int lang_blocks = 0;
     // sampler
     use_sampler_config sc{};
@@ -177,7 +177,7 @@ struct use_handle {
     long long opt_gen_at_plan = -1;              // g_opt_gen when the current plan was built
     long long n_graph_captures = 0, n_plans_built = 0, n_plan_cache_hits = 0;
     // scratch for the stand-alone use_sde_* entry points (independent of weights / plan)
-    char* sde_buf = nullptr; unsigned long long* sde_rng = nullptr; float* sde_step = nullptr; float* sde_partial = nullptr; unsigned long long* sde_seeds = nullptr;
+    char* sde_buf = nullptr; unsigned long long* sde_seeds = nullptr; float* sde_step = nullptr; float* sde_partial = nullptr;
     static constexpr int SDE_MAX_B = 1024, SDE_BLOCKS = 128;
     // per-launch HIP-event profiling of the dominant conv kernel (use_profile_score)
     bool profile = false, profile_all = false; std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events; std::vector<double> prof_flops, prof_bytes; std::vector<char> prof_main; std::vector<std::pair<int, int>> prof_hw;
@@ -827,45 +827,36 @@ static void predictor_coeffs(const use_config& c, int predictor, float t, int N,
 // ---------------------------------------------------------------------------------------------------------
 // the PC loop (reference sampling/__init__.py:59-71)
 // ---------------------------------------------------------------------------------------------------------
-__global__ void set_rng_kernel(unsigned long long* st, unsigned long long seed, unsigned long long base) { st[0] = seed; st[1] = base; }
+__global__ void set_rng_kernel(unsigned long long* seeds, unsigned long long seed) { seeds[0] = seed; }
 __global__ void fill_f32_kernel(float* p, float v, int n) { for (int i = threadIdx.x; i < n; i += blockDim.x) p[i] = v; }
 
 // steps [i0, i1) of the loop (i0 == 0: preceded by the prior sampling); the whole loop is run_sampler(h, noise, s, 0, N).
-// per_item: the SDE updates in their per-item forms (use_sample_items) - item b's noise from h->item_seeds[b], its own
-// Langevin step; the score evaluations and the stream schedule are the same.
+// per_item (use_sample_items): the SDE updates address the batch as B items - item b's noise from h->seeds[b], its own
+// Langevin step - instead of one item of all n elements; the score evaluations and the stream schedule are the same.
 static void run_sampler(use_handle* h, const float2* noise, hipStream_t s, int i0, int i1, bool per_item = false) {
     const use_sampler_config& sc = h->sc;
     const long n = (long)h->B * h->cfg.n_freq * h->T, n_per_b = (long)h->cfg.n_freq * h->T;
+    const int items = per_item ? h->B : 1;
+    const long n_per_item = n / items;
     const int ncorr = sc.corrector == USE_CORR_NONE ? 0 : sc.corrector_steps;
     // the network's kernel choice must not see the (sub-)batch size either: an item of a sub-batch of 3 has to get the bits it gets alone
     struct PerImage { bool on; PerImage(bool o) : on(o) { if (on) conv_sk_set_per_image(true); } ~PerImage() { if (on) conv_sk_set_per_image(false); } } per_image(per_item);
     auto nz = [&](unsigned d) { return noise ? noise + (size_t)d * n : nullptr; };
     unsigned d = 1 + (unsigned)i0 * (unsigned)(ncorr + (sc.predictor == USE_PRED_NONE ? 0 : 1));   // noise draws consumed so far
-    if (i0 == 0) {
-        if (per_item) launch_prior_items(h->Y, nz(0), ItemRng{h->item_seeds, 0}, ouve_std(h->cfg, 1.0f), h->X, h->B, n_per_b, s);
-        else launch_prior(h->Y, nz(0), RngRef{h->rng_state, 0}, ouve_std(h->cfg, 1.0f), h->X, n, s);
-    }
+    if (i0 == 0) launch_prior(h->Y, nz(0), SdeRng{h->seeds, 0}, ouve_std(h->cfg, 1.0f), h->X, items, n_per_item, s);
     for (int i = i0; i < i1; ++i) {
         const float t = h->timesteps[i];
         const float* temb = h->temb_table + (size_t)i * h->dense_rows;
         for (int k = 0; k < ncorr; ++k) {
             run_score(h, h->X, h->Cond, temb, 0, h->ts_dev + i, 0, h->score, s, -1.f, h->pcp == 8 ? h->cond2_buf : nullptr);
-            RngRef rr{h->rng_state, d};
-            ItemRng ir{h->item_seeds, d};
-            if (per_item && sc.corrector == USE_CORR_LANGEVIN) {
-                launch_langevin_norms_items(h->score, nz(d), ir, h->lang_partial, h->B, n_per_b, h->lang_blocks, s);
-                launch_langevin_step_items(h->lang_partial, h->B, h->lang_blocks, sc.snr, h->item_step, s);
-                launch_corrector_items(h->X, h->score, nz(d), ir, h->item_step, 0.f, h->X, nullptr, h->B, n_per_b, s);
-            } else if (per_item) {
-                const float sd = sc.snr * ouve_std(h->cfg, t);
-                launch_corrector_items(h->X, h->score, nz(d), ir, nullptr, sd * sd * 2.f, h->X, nullptr, h->B, n_per_b, s);
-            } else if (sc.corrector == USE_CORR_LANGEVIN) {
-                launch_langevin_norms(h->score, nz(d), rr, h->lang_partial, h->B, n_per_b, h->lang_blocks, s);
-                launch_langevin_step(h->lang_partial, h->B, h->lang_blocks, sc.snr, h->lang_step, s);
-                launch_corrector(h->X, h->score, nz(d), rr, h->lang_step, 0.f, h->X, nullptr, n, s);
+            const SdeRng rng{h->seeds, d};
+            if (sc.corrector == USE_CORR_LANGEVIN) {
+                launch_langevin_norms(h->score, nz(d), rng, per_item, h->lang_partial, h->B, n_per_b, h->lang_blocks, s);
+                launch_langevin_step(h->lang_partial, h->B, per_item, h->lang_blocks, sc.snr, h->lang_step, s);
+                launch_corrector(h->X, h->score, nz(d), rng, h->lang_step, 0.f, h->X, nullptr, items, n_per_item, s);
             } else {                                               // ALD: correctors.py:79-98
                 const float sd = sc.snr * ouve_std(h->cfg, t);
-                launch_corrector(h->X, h->score, nz(d), rr, nullptr, sd * sd * 2.f, h->X, nullptr, n, s);
+                launch_corrector(h->X, h->score, nz(d), rng, nullptr, sd * sd * 2.f, h->X, nullptr, items, n_per_item, s);
             }
             d++;
         }
@@ -874,12 +865,8 @@ static void run_sampler(use_handle* h, const float2* noise, hipStream_t s, int i
         } else {
             run_score(h, h->X, h->Cond, temb, 0, h->ts_dev + i, 0, h->score, s, -1.f, h->pcp == 8 ? h->cond2_buf : nullptr);
             float cd, cs, cn; predictor_coeffs(h->cfg, sc.predictor, t, sc.N, cd, cs, cn);
-            if (per_item)
-                launch_predictor_items(h->X, h->Y, h->score, nz(d), ItemRng{h->item_seeds, d}, cd, cs, cn, h->X,
-                                       i == sc.N - 1 ? h->Xmean : nullptr, h->B, n_per_b, s);
-            else
-            launch_predictor(h->X, h->Y, h->score, nz(d), RngRef{h->rng_state, d}, cd, cs, cn, h->X,
-                             i == sc.N - 1 ? h->Xmean : nullptr, n, s);
+            launch_predictor(h->X, h->Y, h->score, nz(d), SdeRng{h->seeds, d}, cd, cs, cn, h->X,
+                             i == sc.N - 1 ? h->Xmean : nullptr, items, n_per_item, s);
             d++;
         }
     }
@@ -894,7 +881,7 @@ static void drop_graphs(use_handle* h) {
 // everything of the handle that belongs to ONE plan (the current plan lives in the handle's own fields)
 #define USE_PLAN_FIELDS(X)                                                                                            \
     X(B) X(T) X(nsub) X(arena) X(arena_alloc) X(arena_plan_bytes) X(persist) X(persist_bytes) X(persist_alloc) X(x4) X(silu_temb) X(tembias) X(t_dev) \
-    X(Y) X(X) X(Xmean) X(score) X(xin) X(cond_buf) X(cond2_buf) X(Cond) X(lang_partial) X(lang_step) X(rng_state) X(item_seeds) X(item_step) X(lang_blocks)   \
+    X(Y) X(X) X(Xmean) X(score) X(xin) X(cond_buf) X(cond2_buf) X(Cond) X(lang_partial) X(lang_step) X(seeds) X(lang_blocks)   \
     X(sc) X(sampler_set) X(timesteps) X(ts_dev) X(temb_table) X(silu_table) X(noise_copy) X(noise_copy_bytes) X(score_graph)      \
     X(debug) X(debug_B) X(opt_gen_at_plan) X(oc) X(ode_set)
 struct use_handle::PlanState {
@@ -944,11 +931,12 @@ static int ensure_sde_scratch(use_handle* h) {
     HIPCHK(hipSetDevice(h->device));
     if (!h->sde_buf) {
         const size_t part = (size_t)use_handle::SDE_MAX_B * use_handle::SDE_BLOCKS * 2 * 4;
-        const size_t bytes = 512 + part + (size_t)use_handle::SDE_MAX_B * 8;       // + the seeds of use_fill_noise_items
+        const size_t seeds = (size_t)use_handle::SDE_MAX_B * 8;                    // [0] alone but for use_fill_noise_items
+        const size_t bytes = seeds + 256 + part;
         HIPCHK(hipMalloc((void**)&h->sde_buf, bytes));
         HIPCHK(hipMemset(h->sde_buf, 0, bytes));
-        h->sde_rng = (unsigned long long*)h->sde_buf; h->sde_step = (float*)(h->sde_buf + 256);
-        h->sde_partial = (float*)(h->sde_buf + 512); h->sde_seeds = (unsigned long long*)(h->sde_buf + 512 + part);
+        h->sde_seeds = (unsigned long long*)h->sde_buf; h->sde_step = (float*)(h->sde_buf + seeds);
+        h->sde_partial = (float*)(h->sde_buf + seeds + 256);
     }
     return USE_OK;
 }
@@ -1270,8 +1258,8 @@ int use_plan(use_handle* h, int B, int Tpad) {
     auto take = [&](size_t bytes) { off = (off + 255) & ~(size_t)255; size_t o = off; off += bytes; return o; };
     const size_t o_x4 = take(n * 4 * h->pcp), o_c2 = take(h->pcp == 8 ? n * 8 : 0), o_Y = take(n * 8), o_X = take(n * 8), o_Xm = take(n * 8), o_sc = take(n * 8),
                  o_xin = take(n * 8), o_cond = take(n * 8), o_st = take((size_t)B * 4 * h->cfg.nf * 4), o_tb = take((size_t)B * h->dense_rows * 4),
-                 o_t = take((size_t)B * 4), o_lp = take((size_t)B * h->lang_blocks * 2 * 4), o_ls = take(256), o_rng = take(256),
-                 o_is = take((size_t)B * 8), o_ist = take((size_t)B * 4);
+                 o_t = take((size_t)B * 4), o_lp = take((size_t)B * h->lang_blocks * 2 * 4), o_ls = take((size_t)B * 4),
+                 o_sd = take((size_t)std::max(B, 1) * 8);
     h->persist_bytes = off;
     if (!h->persist || off > h->persist_alloc) {
         if (h->persist) { HIPCHK(hipFree(h->persist)); h->persist = nullptr; h->persist_alloc = 0; }
@@ -1288,8 +1276,7 @@ int use_plan(use_handle* h, int B, int Tpad) {
     h->cond2_buf = h->pcp == 8 ? (float2*)(h->persist + o_c2) : nullptr;
     h->silu_temb = (float*)(h->persist + o_st); h->tembias = (float*)(h->persist + o_tb); h->t_dev = (float*)(h->persist + o_t);
     h->lang_partial = (float*)(h->persist + o_lp); h->lang_step = (float*)(h->persist + o_ls);
-    h->rng_state = (unsigned long long*)(h->persist + o_rng);
-    h->item_seeds = (unsigned long long*)(h->persist + o_is); h->item_step = (float*)(h->persist + o_ist);
+    h->seeds = (unsigned long long*)(h->persist + o_sd);
     HIPCHK(hipMemset(h->persist, 0, off));
     return USE_OK;
 }
@@ -1497,20 +1484,54 @@ static void upload_item_seeds(unsigned long long* dst, const uint64_t* seeds_hos
     }
 }
 
+// what every sampler checks first; `set` is the plan's flag that the sampler at hand has been configured
+static int check_sample_args(use_handle* h, bool use_handle::*set, const char* unset, const void* y, const void* cond2, const void* out,
+                             const char* six_hint) {
+    int rc = check_ready(h); if (rc) return rc;
+    if (!(h->*set)) return fail(USE_E_STATE, "%s", unset);
+    if (!y || !out) return fail(USE_E_INVALID, "null tensor");
+    if ((h->cfg.input_channels == 6) != (cond2 != nullptr))
+        return h->cfg.input_channels == 6 ? fail(USE_E_INVALID, "a 6-channel network samples with two conditioning tensors%s", six_hint)
+                                          : fail(USE_E_INVALID, "this network takes one conditioning tensor");
+    return USE_OK;
+}
+
+// record(cap_stream), captured into an executable graph; what: "the sampling loop", for the error text.  *ge is null on failure, and what
+// else has to go then is the caller's business.
+template <class F>
+static int capture_graph(use_handle* h, const char* what, F&& record, hipGraphExec_t* ge) {
+    *ge = nullptr;
+    hipGraph_t g = nullptr;
+    HIPCHK(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
+    record(h->cap_stream);
+    // (nothing returns between begin and end: a failed launch invalidates the capture and surfaces here, with the
+    // stream out of capture mode either way)
+    hipError_t e = hipStreamEndCapture(h->cap_stream, &g);
+    if (eval_status(h)) { if (g) (void)hipGraphDestroy(g); (void)hipGetLastError(); return USE_E_STATE; }
+    if (e != hipSuccess || !g) {
+        if (g) (void)hipGraphDestroy(g);
+        (void)hipGetLastError();
+        return fail(USE_E_HIP, "capturing %s failed: %s", what, hipGetErrorString(e));
+    }
+    e = hipGraphInstantiate(ge, g, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(g);
+    if (e != hipSuccess) { *ge = nullptr; return fail(USE_E_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e)); }
+    ++h->n_graph_captures;
+    return USE_OK;
+}
+
 // use_sample_cond2 (seeds_host == null, per_item false) and use_sample_items (per_item)
 static int sample_impl(use_handle* h, const void* y, const void* cond, const void* cond2, const void* noise, uint64_t seed,
                        const uint64_t* seeds_host, bool per_item, void* out, use_stream_t stream) {
-    int rc = check_ready(h); if (rc) return rc;
-    if (!h->sampler_set) return fail(USE_E_STATE, "use_set_sampler has not been called");
-    if (!y || !out) return fail(USE_E_INVALID, "null tensor");
-    if ((h->cfg.input_channels == 6) != (cond2 != nullptr))
-        return fail(USE_E_INVALID, h->cfg.input_channels == 6 ? "a 6-channel network samples with two conditioning tensors (use_sample_cond2)"
-                                                              : "this network takes one conditioning tensor");
+    int rc = check_sample_args(h, &use_handle::sampler_set, "use_set_sampler has not been called", y, cond2, out, " (use_sample_cond2)");
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     const size_t n = (size_t)h->B * h->cfg.n_freq * h->T;
     rc = load_sampler_inputs(h, y, cond, cond2, s); if (rc) return rc;
-    if (per_item) { if (seeds_host) upload_item_seeds(h->item_seeds, seeds_host, h->B, s); }
-    else hipLaunchKernelGGL(set_rng_kernel, dim3(1), dim3(1), 0, s, h->rng_state, (unsigned long long)seed, 0ull);
+    // both forms keep their seeds in h->seeds, and so do both forms' graphs: each call uploads its own (per item without seeds: all its noise
+    // is injected, and its kernels read none)
+    if (per_item) { if (seeds_host) upload_item_seeds(h->seeds, seeds_host, h->B, s); }
+    else hipLaunchKernelGGL(set_rng_kernel, dim3(1), dim3(1), 0, s, h->seeds, (unsigned long long)seed);
     if (!h->sc.use_graph) {
         run_sampler(h, (const float2*)noise, s, 0, h->sc.N, per_item);
         rc = eval_status(h); if (rc) return rc;
@@ -1541,25 +1562,11 @@ static int sample_impl(use_handle* h, const void* y, const void* cond, const voi
             const int ncorr = h->sc.corrector == USE_CORR_NONE ? 0 : h->sc.corrector_steps;
             const int per_seg = std::max(1, 64 / (ncorr + 1));
             for (int i0 = 0; i0 < h->sc.N; i0 += per_seg) {
-                hipGraph_t g = nullptr;
                 hipGraphExec_t ge = nullptr;
-                HIPCHK(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
-                run_sampler(h, nz, h->cap_stream, i0, std::min(h->sc.N, i0 + per_seg), per_item);
-                // (nothing returns between begin and end: a failed launch invalidates the capture and surfaces here, with the
-                // stream out of capture mode either way)
-                hipError_t e = hipStreamEndCapture(h->cap_stream, &g);
-                if (eval_status(h)) { if (g) (void)hipGraphDestroy(g); (void)hipGetLastError(); drop_graphs(h); return USE_E_STATE; }
-                if (e != hipSuccess || !g) {
-                    if (g) (void)hipGraphDestroy(g);
-                    (void)hipGetLastError();
-                    drop_graphs(h);
-                    return fail(USE_E_HIP, "capturing the sampling loop failed: %s", hipGetErrorString(e));
-                }
-                e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
-                (void)hipGraphDestroy(g);
-                if (e != hipSuccess) { drop_graphs(h); return fail(USE_E_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e)); }
+                rc = capture_graph(h, "the sampling loop",
+                                   [&](hipStream_t cs) { run_sampler(h, nz, cs, i0, std::min(h->sc.N, i0 + per_seg), per_item); }, &ge);
+                if (rc) { drop_graphs(h); return rc; }
                 h->graph_exec[gi].push_back(ge);
-                ++h->n_graph_captures;
             }
         }
         for (auto ge : h->graph_exec[gi]) HIPCHK(hipGraphLaunch(ge, s));
@@ -1788,12 +1795,8 @@ int use_set_ode(use_handle* h, const use_ode_config* oc) {
 
 int use_sample_ode(use_handle* h, const void* y, const void* cond, const void* cond2, const void* noise, uint64_t seed, void* out,
                    int* nfev, int* status, use_stream_t stream) {
-    int rc = check_ready(h); if (rc) return rc;
-    if (!h->ode_set) return fail(USE_E_STATE, "use_set_ode has not been called");
-    if (!y || !out) return fail(USE_E_INVALID, "null tensor");
-    if ((h->cfg.input_channels == 6) != (cond2 != nullptr))
-        return fail(USE_E_INVALID, h->cfg.input_channels == 6 ? "a 6-channel network samples with two conditioning tensors"
-                                                              : "this network takes one conditioning tensor");
+    int rc = check_sample_args(h, &use_handle::ode_set, "use_set_ode has not been called", y, cond2, out, "");
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     const long n_per_b = (long)h->cfg.n_freq * h->T, n = (long)h->B * n_per_b;
     use_ode* o = h->ode_run;
@@ -1822,8 +1825,8 @@ int use_sample_ode(use_handle* h, const void* y, const void* cond, const void* c
         }
     };
     // 1. prior: draw 0 of the Philox stream (use_sample's), or the given draw
-    hipLaunchKernelGGL(set_rng_kernel, dim3(1), dim3(1), 0, s, h->rng_state, (unsigned long long)seed, 0ull);
-    launch_prior(h->Y, (const float2*)noise, RngRef{h->rng_state, 0}, ouve_std(h->cfg, 1.0f), o->d.xin, n, s);
+    hipLaunchKernelGGL(set_rng_kernel, dim3(1), dim3(1), 0, s, h->seeds, (unsigned long long)seed);
+    launch_prior(h->Y, (const float2*)noise, SdeRng{h->seeds, 0}, ouve_std(h->cfg, 1.0f), o->d.xin, 1, n, s);
     // 2. f0 and select_initial_step
     ode_start_impl(o, s);
     eval(0); ode_supply_impl(o, h->score, 1, s);
@@ -1836,22 +1839,10 @@ int use_sample_ode(use_handle* h, const void* y, const void* cond, const void* c
         if (h->ode_graph && key != h->ode_graph_key) { (void)hipGraphExecDestroy(h->ode_graph); h->ode_graph = nullptr; }
         if (!h->ode_graph) {
             rc = ensure_cap_stream(h); if (rc) return rc;
-            hipGraph_t g = nullptr;
-            HIPCHK(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
-            step(h->cap_stream);
-            hipError_t e = hipStreamEndCapture(h->cap_stream, &g);
-            o->phase = 1;
-            if (eval_status(h)) { if (g) (void)hipGraphDestroy(g); (void)hipGetLastError(); return USE_E_STATE; }
-            if (e != hipSuccess || !g) {
-                if (g) (void)hipGraphDestroy(g);
-                (void)hipGetLastError();
-                return fail(USE_E_HIP, "capturing the RK45 step failed: %s", hipGetErrorString(e));
-            }
-            e = hipGraphInstantiate(&h->ode_graph, g, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(g);
-            if (e != hipSuccess) { h->ode_graph = nullptr; return fail(USE_E_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e)); }
+            rc = capture_graph(h, "the RK45 step", step, &h->ode_graph);
+            o->phase = 1;                                         // (the recording walked the stepper's host-side phase through a step)
+            if (rc) return rc;
             h->ode_graph_key = key;
-            ++h->n_graph_captures;
         }
     }
     for (;;) {
@@ -1868,7 +1859,7 @@ int use_sample_ode(use_handle* h, const void* y, const void* cond, const void* c
         run_temb(h, h->t_dev, h->B, h->silu_temb, h->tembias, s);
         run_score(h, h->X, h->Cond, h->tembias, h->dense_rows, h->t_dev, 1, h->score, s, -1.f, c2);
         float cd, cs, cn; predictor_coeffs(h->cfg, USE_PRED_REVERSE_DIFFUSION, h->oc.t_eps, h->oc.N, cd, cs, cn);
-        launch_predictor(h->X, h->Y, h->score, nullptr, RngRef{h->rng_state, 1}, cd, cs, cn, h->Xmean, (float2*)out, n, s);
+        launch_predictor(h->X, h->Y, h->score, nullptr, SdeRng{h->seeds, 1}, cd, cs, cn, h->Xmean, (float2*)out, 1, n, s);
     } else {
         HIPCHK(hipMemcpyAsync(out, h->X, (size_t)n * 8, hipMemcpyDeviceToDevice, s));
     }
@@ -2060,8 +2051,8 @@ int use_sde_prior(use_handle* h, const void* y, const void* noise, uint64_t seed
     if (!y) return fail(USE_E_INVALID, "use_sde_prior: y is null");
     if (!x) return fail(USE_E_INVALID, "use_sde_prior: x is null");
     if (n < 1) return fail(USE_E_INVALID, "use_sde_prior: n=%lld must be positive", (long long)n);
-    hipLaunchKernelGGL(set_rng_kernel, dim3(1), dim3(1), 0, (hipStream_t)s, h->sde_rng, (unsigned long long)seed, 0ull);
-    launch_prior((const float2*)y, (const float2*)noise, RngRef{h->sde_rng, 0}, ouve_std(h->cfg, 1.0f), (float2*)x, n, (hipStream_t)s);
+    hipLaunchKernelGGL(set_rng_kernel, dim3(1), dim3(1), 0, (hipStream_t)s, h->sde_seeds, (unsigned long long)seed);
+    launch_prior((const float2*)y, (const float2*)noise, SdeRng{h->sde_seeds, 0}, ouve_std(h->cfg, 1.0f), (float2*)x, 1, n, (hipStream_t)s);
     HIPCHK(hipGetLastError());
     return USE_OK;
 }
@@ -2072,7 +2063,7 @@ int use_fill_noise_items(use_handle* h, const uint64_t* seeds_host, int B, int d
     int rc = ensure_sde_scratch(h); if (rc) return rc;
     if (n == 0) return USE_OK;
     upload_item_seeds(h->sde_seeds, seeds_host, B, (hipStream_t)s);
-    launch_fill_noise_items((float2*)out, ItemRng{h->sde_seeds, (unsigned)draw}, B, (long)(n / B), (hipStream_t)s);
+    launch_fill_noise((float2*)out, SdeRng{h->sde_seeds, (unsigned)draw}, B, (long)(n / B), (hipStream_t)s);
     HIPCHK(hipGetLastError());
     return USE_OK;
 }
@@ -2082,8 +2073,8 @@ int use_fill_noise(use_handle* h, uint64_t seed, int draw, void* out, int64_t n,
     // Box-Muller on two uniforms u in (0, 1] (24 high bits + 0.5, rounded to float32: 1.0 occurs)
     int rc = ensure_sde_scratch(h); if (rc) return rc;
     if (!out || n < 1 || draw < 0) return fail(USE_E_INVALID, "bad arguments");
-    hipLaunchKernelGGL(set_rng_kernel, dim3(1), dim3(1), 0, (hipStream_t)s, h->sde_rng, (unsigned long long)seed, 0ull);
-    launch_fill_noise((float2*)out, RngRef{h->sde_rng, (unsigned)draw}, (long)n, (hipStream_t)s);
+    hipLaunchKernelGGL(set_rng_kernel, dim3(1), dim3(1), 0, (hipStream_t)s, h->sde_seeds, (unsigned long long)seed);
+    launch_fill_noise((float2*)out, SdeRng{h->sde_seeds, (unsigned)draw}, 1, (long)n, (hipStream_t)s);
     HIPCHK(hipGetLastError());
     return USE_OK;
 }
@@ -2098,9 +2089,9 @@ int use_sde_predictor(use_handle* h, int predictor, float t, int N, const void* 
     if (!x_out) return fail(USE_E_INVALID, "use_sde_predictor: x_out is null");
     if (n < 1) return fail(USE_E_INVALID, "use_sde_predictor: n=%lld must be positive", (long long)n);
     float cd, cs, cn; predictor_coeffs(h->cfg, predictor, t, N, cd, cs, cn);
-    hipLaunchKernelGGL(set_rng_kernel, dim3(1), dim3(1), 0, (hipStream_t)s, h->sde_rng, (unsigned long long)seed, 0ull);
-    launch_predictor((const float2*)x, (const float2*)y, (const float2*)score, (const float2*)noise, RngRef{h->sde_rng, 0},
-                     cd, cs, cn, (float2*)x_out, (float2*)x_mean, n, (hipStream_t)s);
+    hipLaunchKernelGGL(set_rng_kernel, dim3(1), dim3(1), 0, (hipStream_t)s, h->sde_seeds, (unsigned long long)seed);
+    launch_predictor((const float2*)x, (const float2*)y, (const float2*)score, (const float2*)noise, SdeRng{h->sde_seeds, 0},
+                     cd, cs, cn, (float2*)x_out, (float2*)x_mean, 1, n, (hipStream_t)s);
     HIPCHK(hipGetLastError());
     return USE_OK;
 }
@@ -2117,15 +2108,15 @@ int use_sde_corrector(use_handle* h, int corrector, float t, float snr, int B, c
     // every refusal comes before the first launch (the seed word is written by a kernel)
     if (corrector != USE_CORR_LANGEVIN && corrector != USE_CORR_ALD) return fail(USE_E_INVALID, "corrector id %d has no update kernel", corrector);
     if (corrector == USE_CORR_LANGEVIN && B > use_handle::SDE_MAX_B) return fail(USE_E_INVALID, "B=%d exceeds %d", B, use_handle::SDE_MAX_B);
-    hipLaunchKernelGGL(set_rng_kernel, dim3(1), dim3(1), 0, s, h->sde_rng, (unsigned long long)seed, 0ull);
-    RngRef rr{h->sde_rng, 0};
+    hipLaunchKernelGGL(set_rng_kernel, dim3(1), dim3(1), 0, s, h->sde_seeds, (unsigned long long)seed);
+    const SdeRng rng{h->sde_seeds, 0};
     if (corrector == USE_CORR_LANGEVIN) {
-        launch_langevin_norms((const float2*)score, (const float2*)noise, rr, h->sde_partial, B, n / B, use_handle::SDE_BLOCKS, s);
-        launch_langevin_step(h->sde_partial, B, use_handle::SDE_BLOCKS, snr, h->sde_step, s);
-        launch_corrector((const float2*)x, (const float2*)score, (const float2*)noise, rr, h->sde_step, 0.f, (float2*)x_out, (float2*)x_mean, n, s);
+        launch_langevin_norms((const float2*)score, (const float2*)noise, rng, false, h->sde_partial, B, n / B, use_handle::SDE_BLOCKS, s);
+        launch_langevin_step(h->sde_partial, B, false, use_handle::SDE_BLOCKS, snr, h->sde_step, s);
+        launch_corrector((const float2*)x, (const float2*)score, (const float2*)noise, rng, h->sde_step, 0.f, (float2*)x_out, (float2*)x_mean, 1, n, s);
     } else {
         const float sd = snr * ouve_std(h->cfg, t);
-        launch_corrector((const float2*)x, (const float2*)score, (const float2*)noise, rr, nullptr, sd * sd * 2.f, (float2*)x_out, (float2*)x_mean, n, s);
+        launch_corrector((const float2*)x, (const float2*)score, (const float2*)noise, rng, nullptr, sd * sd * 2.f, (float2*)x_out, (float2*)x_mean, 1, n, s);
     }
     HIPCHK(hipGetLastError());
     return USE_OK;

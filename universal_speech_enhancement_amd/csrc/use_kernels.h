@@ -228,39 +228,28 @@ void launch_pack_conv_dev(const float* src, int mode, int cout, int cin, int nta
                           const float* bias, float* bias_out, hipStream_t s);
 
 // ---- SDE updates (complex64 as float2, fp32 arithmetic) ----
-struct RngRef { const unsigned long long* state; unsigned draw; };  // state[0]=seed, state[1]=draw base
-// z source: noise != null -> read noise[i]; else Philox(seed, draw)
-void launch_prior(const float2* y, const float2* noise, RngRef rng, float std1, float2* x, long n, hipStream_t s);
+// One family, two addressings.  The element-wise updates run on (blocks, items) grids over items * n_per_item elements; item b's
+// z at its element j is noise[b*n_per_item + j] when noise != null, else Philox(seeds[b], draw, j).  The shared stream
+// (use_sample, use_sample_ode, use_sde_*) is items = 1 with all n elements and a one-entry seeds; use_sample_items is items = B,
+// n_per_item = F*T' - each item the stream of a one-item batch with its seed.
+struct SdeRng { const unsigned long long* seeds; unsigned draw; };  // seeds: device [items]
+void launch_fill_noise(float2* out, SdeRng rng, int items, long n_per_item, hipStream_t s);
+void launch_prior(const float2* y, const float2* noise, SdeRng rng, float std1, float2* x, int items, long n_per_item,
+                  hipStream_t s);
 // reverse-diffusion / Euler-Maruyama predictor: x_mean = x + c_drift*(y-x) + c_score*score ; x' = x_mean + c_noise*z
-void launch_predictor(const float2* x, const float2* y, const float2* score, const float2* noise, RngRef rng,
-                      float c_drift, float c_score, float c_noise, float2* x_out, float2* x_mean, long n,
-                      hipStream_t s);
-// Langevin norms: partial[b][blk] = (sum|g|^2, sum|z|^2)
-void launch_langevin_norms(const float2* score, const float2* noise, RngRef rng, float* partial, int B,
+void launch_predictor(const float2* x, const float2* y, const float2* score, const float2* noise, SdeRng rng,
+                      float c_drift, float c_score, float c_noise, float2* x_out, float2* x_mean, int items,
+                      long n_per_item, hipStream_t s);
+// Langevin norms: partial[b][blk] = (sum|g|^2, sum|z|^2) of batch item b; per_item: its z from (seeds[b], counter j), else
+// from the shared stream (seeds[0], counter b*n_per_b + j)
+void launch_langevin_norms(const float2* score, const float2* noise, SdeRng rng, bool per_item, float* partial, int B,
                            long n_per_b, int blocks_per_b, hipStream_t s);
-// step[0] = 2*(snr * mean_b||z_b|| / mean_b||g_b||)^2
-void launch_langevin_step(const float* partial, int B, int blocks_per_b, float snr, float* step, hipStream_t s);
-// x_mean = x + eps*g ; x' = x_mean + sqrt(2 eps) z ; eps = step_dev[0] if step_dev else step_host
-void launch_corrector(const float2* x, const float2* score, const float2* noise, RngRef rng, const float* step_dev,
-                      float step_host, float2* x_out, float2* x_mean, long n, hipStream_t s);
-void launch_fill_noise(float2* out, RngRef rng, long n, hipStream_t s);
-// The per-item forms (use_sample_items): grid (blocks, B); item b's z at element j of its n_per_b elements is
-// noise[b*n_per_b + j] when noise != null, else Philox(seeds[b], draw, j) - the stream of a one-item batch with that seed.
-struct ItemRng { const unsigned long long* seeds; unsigned draw; };  // seeds: device [B]
-void launch_prior_items(const float2* y, const float2* noise, ItemRng rng, float std1, float2* x, int B, long n_per_b,
-                        hipStream_t s);
-void launch_predictor_items(const float2* x, const float2* y, const float2* score, const float2* noise, ItemRng rng,
-                            float c_drift, float c_score, float c_noise, float2* x_out, float2* x_mean, int B,
-                            long n_per_b, hipStream_t s);
-void launch_langevin_norms_items(const float2* score, const float2* noise, ItemRng rng, float* partial, int B,
-                                 long n_per_b, int blocks_per_b, hipStream_t s);
-// step[b] = 2*(snr * ||z_b|| / ||g_b||)^2, one wave per item
-void launch_langevin_step_items(const float* partial, int B, int blocks_per_b, float snr, float* step, hipStream_t s);
-// eps = step_dev[b] if step_dev else step_host
-void launch_corrector_items(const float2* x, const float2* score, const float2* noise, ItemRng rng,
-                            const float* step_dev, float step_host, float2* x_out, float2* x_mean, int B, long n_per_b,
-                            hipStream_t s);
-void launch_fill_noise_items(float2* out, ItemRng rng, int B, long n_per_b, hipStream_t s);
+// step[0] = 2*(snr * mean_b||z_b|| / mean_b||g_b||)^2, or per_item: step[b] = 2*(snr * ||z_b|| / ||g_b||)^2; one wave per step
+void launch_langevin_step(const float* partial, int B, bool per_item, int blocks_per_b, float snr, float* step,
+                          hipStream_t s);
+// x_mean = x + eps*g ; x' = x_mean + sqrt(2 eps) z ; eps = step_dev[item] if step_dev else step_host
+void launch_corrector(const float2* x, const float2* score, const float2* noise, SdeRng rng, const float* step_dev,
+                      float step_host, float2* x_out, float2* x_mean, int items, long n_per_item, hipStream_t s);
 
 // ---- probability-flow ODE sampler (use_ode.hip): scipy's RK45 on the device, one step-size controller per group of items ----
 struct OdeGroup {                          // controller state of one group (scipy's RungeKutta solver object)

@@ -1525,7 +1525,14 @@ void launch_fir_down2(const void* src, int dtype, const float* coef, int act, vo
 #endif
     fir_launch<false>(src, dtype, coef, act, out_act, out_raw, B, H, W, C, s); }
 
-static int ew_blocks(long n) { long b = (n + 255) / 256; if (b > 8192) b = 8192; if (b < 1) b = 1; return (int)b; }
+// blocks of 256 over n elements, for grid-stride loops (the results do not depend on it); on an (ew_blocks, items) grid: per item
+static int ew_blocks(long n, int items = 1) {
+    long b = (n + 255) / 256, cap = 8192 / (items > 0 ? items : 1);
+    if (cap < 1) cap = 1;
+    if (b > cap) b = cap;
+    if (b < 1) b = 1;
+    return (int)b;
+}
 // ---------------------------------------------------------------------------------------------------------
 // Spectrogram glue either side of the sampler: magnitude compression + scaling + frame padding, and back
 //   fwd:  Y[b,0,f,t] = |S|^e e^{j arg S} * factor for t < T, 0 for T <= t < Tpad   (model_wrapper.py:92-96, other.py:128-135)
@@ -2046,37 +2053,48 @@ DEVI float2 philox_cnormal(unsigned long long seed, unsigned long long draw, uns
     sincosf(6.283185307179586f * u2, &sn, &cs);
     return make_float2(r * cs, r * sn);
 }
-DEVI float2 get_noise(const float2* noise, RngRef rng, long i) {
+// The z of the SDE updates at element j of item b (i = b * n_per_item + j): noise[i] when noise != null, else the Philox draw
+// rng.draw of stream rng.seeds[b] at counter j.  Two addressings of the one family: the shared stream (use_sample) is ONE item of
+// all n elements - seeds[0], the counter the global index - and use_sample_items is B items of n_per_b elements, each the
+// stream of a one-item batch with its seed.  The element-wise kernels run on a (blocks, items) grid and need no mode flag.
+DEVI float2 get_noise(const float2* noise, long i, SdeRng rng, int b, long j) {
     if (noise) return noise[i];
-    return philox_cnormal(rng.state[0], rng.state[1] + rng.draw, (unsigned long long)i);
+    return philox_cnormal(rng.seeds[b], rng.draw, (unsigned long long)j);
 }
 
-__global__ __launch_bounds__(256) void fill_noise_kernel(float2* out, RngRef rng, long n) {
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256)
-        out[i] = get_noise(nullptr, rng, i);
+__global__ __launch_bounds__(256) void fill_noise_kernel(float2* out, SdeRng rng, long n_per_item) {
+    const int b = blockIdx.y;
+    for (long j = (long)blockIdx.x * 256 + threadIdx.x; j < n_per_item; j += (long)gridDim.x * 256)
+        out[(long)b * n_per_item + j] = get_noise(nullptr, 0, rng, b, j);
 }
-void launch_fill_noise(float2* out, RngRef rng, long n, hipStream_t s) {
-    hipLaunchKernelGGL(fill_noise_kernel, dim3(ew_blocks(n)), dim3(256), 0, s, out, rng, n);
+void launch_fill_noise(float2* out, SdeRng rng, int items, long n_per_item, hipStream_t s) {
+    hipLaunchKernelGGL(fill_noise_kernel, dim3(ew_blocks(n_per_item, items), items), dim3(256), 0, s, out, rng, n_per_item);
 }
 
 __global__ __launch_bounds__(256) void prior_kernel(const float2* __restrict__ y, const float2* __restrict__ noise,
-                                                    RngRef rng, float std1, float2* __restrict__ x, long n) {
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const float2 z = get_noise(noise, rng, i), yy = y[i];
+                                                    SdeRng rng, float std1, float2* __restrict__ x, long n_per_item) {
+    const int b = blockIdx.y;
+    for (long j = (long)blockIdx.x * 256 + threadIdx.x; j < n_per_item; j += (long)gridDim.x * 256) {
+        const long i = (long)b * n_per_item + j;
+        const float2 z = get_noise(noise, i, rng, b, j), yy = y[i];
         x[i] = make_float2(yy.x + z.x * std1, yy.y + z.y * std1);     // sdes.py:254
     }
 }
-void launch_prior(const float2* y, const float2* noise, RngRef rng, float std1, float2* x, long n, hipStream_t s) {
-    hipLaunchKernelGGL(prior_kernel, dim3(ew_blocks(n)), dim3(256), 0, s, y, noise, rng, std1, x, n);
+void launch_prior(const float2* y, const float2* noise, SdeRng rng, float std1, float2* x, int items, long n_per_item,
+                  hipStream_t s) {
+    hipLaunchKernelGGL(prior_kernel, dim3(ew_blocks(n_per_item, items), items), dim3(256), 0, s, y, noise, rng, std1, x,
+                       n_per_item);
 }
 
 __global__ __launch_bounds__(256) void predictor_kernel(const float2* __restrict__ x, const float2* __restrict__ y,
                                                         const float2* __restrict__ score,
-                                                        const float2* __restrict__ noise, RngRef rng, float c_drift,
+                                                        const float2* __restrict__ noise, SdeRng rng, float c_drift,
                                                         float c_score, float c_noise, float2* __restrict__ x_out,
-                                                        float2* __restrict__ x_mean, long n) {
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const float2 xv = x[i], yv = y[i], sv = score[i], z = get_noise(noise, rng, i);
+                                                        float2* __restrict__ x_mean, long n_per_item) {
+    const int b = blockIdx.y;
+    for (long j = (long)blockIdx.x * 256 + threadIdx.x; j < n_per_item; j += (long)gridDim.x * 256) {
+        const long i = (long)b * n_per_item + j;
+        const float2 xv = x[i], yv = y[i], sv = score[i], z = get_noise(noise, i, rng, b, j);
         // x_mean = x - [theta (y-x) dt - G^2 s]   (predictors.py:62-65, sdes.py:88-92,164-167)
         const float fx = c_drift * (yv.x - xv.x) - c_score * sv.x;
         const float fy = c_drift * (yv.y - xv.y) - c_score * sv.y;
@@ -2085,21 +2103,23 @@ __global__ __launch_bounds__(256) void predictor_kernel(const float2* __restrict
         x_out[i] = make_float2(mx + c_noise * z.x, my + c_noise * z.y);
     }
 }
-void launch_predictor(const float2* x, const float2* y, const float2* score, const float2* noise, RngRef rng,
-                      float c_drift, float c_score, float c_noise, float2* x_out, float2* x_mean, long n,
-                      hipStream_t s) {
-    hipLaunchKernelGGL(predictor_kernel, dim3(ew_blocks(n)), dim3(256), 0, s, x, y, score, noise, rng, c_drift,
-                       c_score, c_noise, x_out, x_mean, n);
+void launch_predictor(const float2* x, const float2* y, const float2* score, const float2* noise, SdeRng rng,
+                      float c_drift, float c_score, float c_noise, float2* x_out, float2* x_mean, int items,
+                      long n_per_item, hipStream_t s) {
+    hipLaunchKernelGGL(predictor_kernel, dim3(ew_blocks(n_per_item, items), items), dim3(256), 0, s, x, y, score, noise,
+                       rng, c_drift, c_score, c_noise, x_out, x_mean, n_per_item);
 }
 
+// The norms are per batch item b in both addressings; per_item only says which stream item b's z comes from: its own
+// (seeds[b], counter j) or the shared one (seeds[0], counter the global index).
 __global__ __launch_bounds__(256) void langevin_norms_kernel(const float2* __restrict__ score,
-                                                             const float2* __restrict__ noise, RngRef rng,
+                                                             const float2* __restrict__ noise, SdeRng rng, int per_item,
                                                              float* __restrict__ partial, long n_per_b) {
     const int b = blockIdx.y;
     float g2 = 0.f, z2 = 0.f;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n_per_b; i += (long)gridDim.x * 256) {
         const long gi = (long)b * n_per_b + i;
-        const float2 g = score[gi], z = get_noise(noise, rng, gi);
+        const float2 g = score[gi], z = get_noise(noise, gi, rng, per_item ? b : 0, per_item ? i : gi);
         g2 += g.x * g.x + g.y * g.y; z2 += z.x * z.x + z.y * z.y;
     }
     __shared__ float rg[4], rz[4];
@@ -2111,17 +2131,20 @@ __global__ __launch_bounds__(256) void langevin_norms_kernel(const float2* __res
         dst[0] = rg[0] + rg[1] + rg[2] + rg[3]; dst[1] = rz[0] + rz[1] + rz[2] + rz[3];
     }
 }
-void launch_langevin_norms(const float2* score, const float2* noise, RngRef rng, float* partial, int B,
+void launch_langevin_norms(const float2* score, const float2* noise, SdeRng rng, bool per_item, float* partial, int B,
                            long n_per_b, int blocks_per_b, hipStream_t s) {
-    hipLaunchKernelGGL(langevin_norms_kernel, dim3(blocks_per_b, B), dim3(256), 0, s, score, noise, rng, partial,
-                       n_per_b);
+    hipLaunchKernelGGL(langevin_norms_kernel, dim3(blocks_per_b, B), dim3(256), 0, s, score, noise, rng, per_item ? 1 : 0,
+                       partial, n_per_b);
 }
 
-__global__ __launch_bounds__(64) void langevin_step_kernel(const float* __restrict__ partial, int B, int blocks_per_b,
+// One wave per step: workgroup w writes step[w] from the mean over its `per` items of the per-item L2 norms
+// (correctors.py:55-57).  Shared: one workgroup over the batch.  Per item: B workgroups of one item, the mean of one norm
+// being that norm, bit for bit - an item's step has the same bits in any batch.
+__global__ __launch_bounds__(64) void langevin_step_kernel(const float* __restrict__ partial, int per, int blocks_per_b,
                                                            float snr, float* __restrict__ step) {
-    // mean over the batch of per-item L2 norms (correctors.py:55-56), one wave
+    const int b0 = blockIdx.x * per;
     double gn = 0.0, zn = 0.0;
-    for (int b = 0; b < B; ++b) {
+    for (int b = b0; b < b0 + per; ++b) {
         double g2 = 0.0, z2 = 0.0;
         for (int k = threadIdx.x; k < blocks_per_b; k += 64) {
             g2 += (double)partial[((size_t)b * blocks_per_b + k) * 2];
@@ -2131,170 +2154,37 @@ __global__ __launch_bounds__(64) void langevin_step_kernel(const float* __restri
         gn += sqrt(g2); zn += sqrt(z2);
     }
     if (threadIdx.x == 0) {
-        const float gm = (float)(gn / B), zm = (float)(zn / B);
+        const float gm = (float)(gn / per), zm = (float)(zn / per);
         const float r = snr * zm / gm;
-        step[0] = r * r * 2.f;                                   // correctors.py:57
+        step[blockIdx.x] = r * r * 2.f;                          // correctors.py:57
     }
 }
-void launch_langevin_step(const float* partial, int B, int blocks_per_b, float snr, float* step, hipStream_t s) {
-    hipLaunchKernelGGL(langevin_step_kernel, dim3(1), dim3(64), 0, s, partial, B, blocks_per_b, snr, step);
+void launch_langevin_step(const float* partial, int B, bool per_item, int blocks_per_b, float snr, float* step,
+                          hipStream_t s) {
+    hipLaunchKernelGGL(langevin_step_kernel, dim3(per_item ? B : 1), dim3(64), 0, s, partial, per_item ? 1 : B,
+                       blocks_per_b, snr, step);
 }
 
 __global__ __launch_bounds__(256) void corrector_kernel(const float2* __restrict__ x, const float2* __restrict__ score,
-                                                        const float2* __restrict__ noise, RngRef rng,
+                                                        const float2* __restrict__ noise, SdeRng rng,
                                                         const float* __restrict__ step_dev, float step_host,
                                                         float2* __restrict__ x_out, float2* __restrict__ x_mean,
-                                                        long n) {
-    const float eps = step_dev ? step_dev[0] : step_host;
-    const float sq = sqrtf(eps * 2.f);
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const float2 xv = x[i], g = score[i], z = get_noise(noise, rng, i);
-        const float mx = xv.x + eps * g.x, my = xv.y + eps * g.y;   // correctors.py:60-61
-        if (x_mean) x_mean[i] = make_float2(mx, my);
-        x_out[i] = make_float2(mx + z.x * sq, my + z.y * sq);
-    }
-}
-void launch_corrector(const float2* x, const float2* score, const float2* noise, RngRef rng, const float* step_dev,
-                      float step_host, float2* x_out, float2* x_mean, long n, hipStream_t s) {
-    hipLaunchKernelGGL(corrector_kernel, dim3(ew_blocks(n)), dim3(256), 0, s, x, score, noise, rng, step_dev,
-                       step_host, x_out, x_mean, n);
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// Per-item forms of the SDE updates (use_sample_items): item b = blockIdx.y draws from its own Philox stream, keyed by
-// seeds[b] with the counter = the element index INSIDE the item - by construction the stream of a one-item batch with
-// seed = seeds[b] - and the Langevin step size is the item's own.  Same traffic as the batch forms: one pass, float2.
-// ---------------------------------------------------------------------------------------------------------
-DEVI float2 get_noise_item(const float2* noise, ItemRng rng, int b, long n_per_b, long j) {
-    if (noise) return noise[(long)b * n_per_b + j];
-    return philox_cnormal(rng.seeds[b], rng.draw, (unsigned long long)j);
-}
-// blocks per item of the element-wise per-item kernels (grid-stride loops: the results do not depend on it)
-static int item_blocks(long n_per_b, int B) {
-    long b = (n_per_b + 255) / 256, cap = 8192 / (B > 0 ? B : 1);
-    if (cap < 1) cap = 1;
-    if (b > cap) b = cap;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
-__global__ __launch_bounds__(256) void fill_noise_items_kernel(float2* out, ItemRng rng, long n_per_b) {
-    const int b = blockIdx.y;
-    for (long j = (long)blockIdx.x * 256 + threadIdx.x; j < n_per_b; j += (long)gridDim.x * 256)
-        out[(long)b * n_per_b + j] = get_noise_item(nullptr, rng, b, n_per_b, j);
-}
-void launch_fill_noise_items(float2* out, ItemRng rng, int B, long n_per_b, hipStream_t s) {
-    hipLaunchKernelGGL(fill_noise_items_kernel, dim3(item_blocks(n_per_b, B), B), dim3(256), 0, s, out, rng, n_per_b);
-}
-
-__global__ __launch_bounds__(256) void prior_items_kernel(const float2* __restrict__ y, const float2* __restrict__ noise,
-                                                          ItemRng rng, float std1, float2* __restrict__ x, long n_per_b) {
-    const int b = blockIdx.y;
-    for (long j = (long)blockIdx.x * 256 + threadIdx.x; j < n_per_b; j += (long)gridDim.x * 256) {
-        const long i = (long)b * n_per_b + j;
-        const float2 z = get_noise_item(noise, rng, b, n_per_b, j), yy = y[i];
-        x[i] = make_float2(yy.x + z.x * std1, yy.y + z.y * std1);     // sdes.py:254
-    }
-}
-void launch_prior_items(const float2* y, const float2* noise, ItemRng rng, float std1, float2* x, int B, long n_per_b,
-                        hipStream_t s) {
-    hipLaunchKernelGGL(prior_items_kernel, dim3(item_blocks(n_per_b, B), B), dim3(256), 0, s, y, noise, rng, std1, x,
-                       n_per_b);
-}
-
-__global__ __launch_bounds__(256) void predictor_items_kernel(const float2* __restrict__ x, const float2* __restrict__ y,
-                                                              const float2* __restrict__ score,
-                                                              const float2* __restrict__ noise, ItemRng rng,
-                                                              float c_drift, float c_score, float c_noise,
-                                                              float2* __restrict__ x_out, float2* __restrict__ x_mean,
-                                                              long n_per_b) {
-    const int b = blockIdx.y;
-    for (long j = (long)blockIdx.x * 256 + threadIdx.x; j < n_per_b; j += (long)gridDim.x * 256) {
-        const long i = (long)b * n_per_b + j;
-        const float2 xv = x[i], yv = y[i], sv = score[i], z = get_noise_item(noise, rng, b, n_per_b, j);
-        const float fx = c_drift * (yv.x - xv.x) - c_score * sv.x;      // as predictor_kernel
-        const float fy = c_drift * (yv.y - xv.y) - c_score * sv.y;
-        const float mx = xv.x - fx, my = xv.y - fy;
-        if (x_mean) x_mean[i] = make_float2(mx, my);
-        x_out[i] = make_float2(mx + c_noise * z.x, my + c_noise * z.y);
-    }
-}
-void launch_predictor_items(const float2* x, const float2* y, const float2* score, const float2* noise, ItemRng rng,
-                            float c_drift, float c_score, float c_noise, float2* x_out, float2* x_mean, int B,
-                            long n_per_b, hipStream_t s) {
-    hipLaunchKernelGGL(predictor_items_kernel, dim3(item_blocks(n_per_b, B), B), dim3(256), 0, s, x, y, score, noise,
-                       rng, c_drift, c_score, c_noise, x_out, x_mean, n_per_b);
-}
-
-// the partials of langevin_norms_kernel, with the item's own noise: same grid, same order of additions
-__global__ __launch_bounds__(256) void langevin_norms_items_kernel(const float2* __restrict__ score,
-                                                                   const float2* __restrict__ noise, ItemRng rng,
-                                                                   float* __restrict__ partial, long n_per_b) {
-    const int b = blockIdx.y;
-    float g2 = 0.f, z2 = 0.f;
-    for (long j = (long)blockIdx.x * 256 + threadIdx.x; j < n_per_b; j += (long)gridDim.x * 256) {
-        const float2 g = score[(long)b * n_per_b + j], z = get_noise_item(noise, rng, b, n_per_b, j);
-        g2 += g.x * g.x + g.y * g.y; z2 += z.x * z.x + z.y * z.y;
-    }
-    __shared__ float rg[4], rz[4];
-    for (int o = 32; o > 0; o >>= 1) { g2 += __shfl_xor(g2, o); z2 += __shfl_xor(z2, o); }
-    if ((threadIdx.x & 63) == 0) { rg[threadIdx.x >> 6] = g2; rz[threadIdx.x >> 6] = z2; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float* dst = partial + ((size_t)b * gridDim.x + blockIdx.x) * 2;
-        dst[0] = rg[0] + rg[1] + rg[2] + rg[3]; dst[1] = rz[0] + rz[1] + rz[2] + rz[3];
-    }
-}
-void launch_langevin_norms_items(const float2* score, const float2* noise, ItemRng rng, float* partial, int B,
-                                 long n_per_b, int blocks_per_b, hipStream_t s) {
-    hipLaunchKernelGGL(langevin_norms_items_kernel, dim3(blocks_per_b, B), dim3(256), 0, s, score, noise, rng, partial,
-                       n_per_b);
-}
-
-// step[b] = 2 (snr ||z_b|| / ||g_b||)^2: correctors.py:55-57 at batch size 1.  One wave per item; the partials are added
-// in the order langevin_step_kernel adds them at B = 1, so an item's step has the same bits in any batch.
-__global__ __launch_bounds__(64) void langevin_step_items_kernel(const float* __restrict__ partial, int blocks_per_b,
-                                                                 float snr, float* __restrict__ step) {
-    const int b = blockIdx.x;
-    double g2 = 0.0, z2 = 0.0;
-    for (int k = threadIdx.x; k < blocks_per_b; k += 64) {
-        g2 += (double)partial[((size_t)b * blocks_per_b + k) * 2];
-        z2 += (double)partial[((size_t)b * blocks_per_b + k) * 2 + 1];
-    }
-    for (int o = 32; o > 0; o >>= 1) { g2 += __shfl_xor(g2, o); z2 += __shfl_xor(z2, o); }
-    if (threadIdx.x == 0) {
-        const float gm = (float)sqrt(g2), zm = (float)sqrt(z2);
-        const float r = snr * zm / gm;
-        step[b] = r * r * 2.f;
-    }
-}
-void launch_langevin_step_items(const float* partial, int B, int blocks_per_b, float snr, float* step, hipStream_t s) {
-    hipLaunchKernelGGL(langevin_step_items_kernel, dim3(B), dim3(64), 0, s, partial, blocks_per_b, snr, step);
-}
-
-// step_dev: one step per item (Langevin); null: step_host for all (ALD)
-__global__ __launch_bounds__(256) void corrector_items_kernel(const float2* __restrict__ x,
-                                                              const float2* __restrict__ score,
-                                                              const float2* __restrict__ noise, ItemRng rng,
-                                                              const float* __restrict__ step_dev, float step_host,
-                                                              float2* __restrict__ x_out, float2* __restrict__ x_mean,
-                                                              long n_per_b) {
+                                                        long n_per_item) {
     const int b = blockIdx.y;
     const float eps = step_dev ? step_dev[b] : step_host;
     const float sq = sqrtf(eps * 2.f);
-    for (long j = (long)blockIdx.x * 256 + threadIdx.x; j < n_per_b; j += (long)gridDim.x * 256) {
-        const long i = (long)b * n_per_b + j;
-        const float2 xv = x[i], g = score[i], z = get_noise_item(noise, rng, b, n_per_b, j);
+    for (long j = (long)blockIdx.x * 256 + threadIdx.x; j < n_per_item; j += (long)gridDim.x * 256) {
+        const long i = (long)b * n_per_item + j;
+        const float2 xv = x[i], g = score[i], z = get_noise(noise, i, rng, b, j);
         const float mx = xv.x + eps * g.x, my = xv.y + eps * g.y;   // correctors.py:60-61
         if (x_mean) x_mean[i] = make_float2(mx, my);
         x_out[i] = make_float2(mx + z.x * sq, my + z.y * sq);
     }
 }
-void launch_corrector_items(const float2* x, const float2* score, const float2* noise, ItemRng rng,
-                            const float* step_dev, float step_host, float2* x_out, float2* x_mean, int B, long n_per_b,
-                            hipStream_t s) {
-    hipLaunchKernelGGL(corrector_items_kernel, dim3(item_blocks(n_per_b, B), B), dim3(256), 0, s, x, score, noise, rng,
-                       step_dev, step_host, x_out, x_mean, n_per_b);
+void launch_corrector(const float2* x, const float2* score, const float2* noise, SdeRng rng, const float* step_dev,
+                      float step_host, float2* x_out, float2* x_mean, int items, long n_per_item, hipStream_t s) {
+    hipLaunchKernelGGL(corrector_kernel, dim3(ew_blocks(n_per_item, items), items), dim3(256), 0, s, x, score, noise, rng,
+                       step_dev, step_host, x_out, x_mean, n_per_item);
 }
 
 }  // namespace use
