@@ -432,6 +432,14 @@ typedef struct use_conv_op {
     int temb_bstride;                     /* elements between temb's batch rows: 0 = Cout, -1 = one row shared by the batch */
 } use_conv_op;
 int use_op_conv(const use_conv_op* c, use_stream_t stream);
+/* use_conv_choice: which kernel the library's dispatcher (variant 0) would run this op on under the current options, without running
+ *   it (host only: no HIP call; the op is validated as use_op_conv validates it, its variant field is ignored).  It also answers for
+ *   the network's input convolution as the engine issues it, which use_op_conv does not run: dtype fp32, ntaps 9, C0 = 4 (or 8: the
+ *   6-channel input), no second source and no shortcut; with 16-bit output it then has the engine's split-bf16 weight copy.  name receives one of
+ *   "conv_sk", "conv_v4", "conv_v5", "conv_v2", "pyr_conv", "pyr_conv_ws", "conv_in", "conv_in_split", "conv_generic"; stats_parts the
+ *   per-workgroup partial GroupNorm totals per (item, channel) that kernel can write in place of atomics (0: it only knows atomics).
+ *   Either may be null. */
+int use_conv_choice(const use_conv_op* c, char* name, int name_cap, int* stats_parts);
 /* use_op_conv_dev: the same operator for the training path (reference SGMSE_module.py:46-54 -> model_wrapper.py:147-208, where the
  *   parameters are nn.Parameters on the device and change every optimiser step): c->w / c->bias are DEVICE fp32 tensors, laid out for
  *   the kernels by a kernel on `stream` into the caller's workspace (use_op_conv_dev_workspace(c) bytes); no allocation, no

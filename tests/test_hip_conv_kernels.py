@@ -255,18 +255,10 @@ def _border_heavy(g, B, H, W, Cc, dt, scale=1.0):
     return q(x, dt)
 
 
-def _run_conv(f, variant):
-    """One use_op_conv of case data `f` (dict) with the given variant: (rc, out, stats) on the CPU, the sentinels checked."""
-    L = _lib()
-    B, H, W, Cout, odt = f["B"], f["H"], f["W"], f["Cout"], f["odt"]
-    obuf, out = _guarded((B, H, W, Cout), TD[odt], SENTINEL)
-    sbuf = stats = None
-    if f["stats"]:
-        sbuf = torch.full((B * Cout * 2 + TAIL,), 0x5A5A5A5A5A5A, dtype=torch.int64, device="cuda")
-        sbuf[:B * Cout * 2] = 0
-        stats = sbuf[:B * Cout * 2].view(B, Cout, 2)
-    op = L.UseConvOp()
-    op.B, op.H, op.W, op.Cout, op.ntaps, op.act, op.dtype, op.out_dtype, op.variant = B, H, W, Cout, f["ntaps"], f["act"], f["dt"], odt, variant
+def _conv_op(f, variant, out_ptr, stats_ptr):
+    """The use_conv_op of case data `f` (dict)."""
+    op = _lib().UseConvOp()
+    op.B, op.H, op.W, op.Cout, op.ntaps, op.act, op.dtype, op.out_dtype, op.variant = f["B"], f["H"], f["W"], f["Cout"], f["ntaps"], f["act"], f["dt"], f["odt"], variant
     op.C0, op.src0 = f["C0"], f["d_src0"].data_ptr()
     op.C1, op.src1 = f["C1"], (f["d_src1"].data_ptr() if f["C1"] else None)
     op.XC0, op.x0 = f["XC0"], (f["d_x0"].data_ptr() if f["XC0"] else None)
@@ -279,13 +271,36 @@ def _run_conv(f, variant):
     op.temb_bstride = f["temb_bstride"]
     op.res = f["d_res"].data_ptr() if f["d_res"] is not None else None
     op.out_scale = f["scale"]
-    op.out = out.data_ptr()
-    op.stats = stats.data_ptr() if stats is not None else None
+    op.out = out_ptr
+    op.stats = stats_ptr
     if f["d_pyr"] is not None:
         op.pyr, op.w4, op.b4 = f["d_pyr"].data_ptr(), f["h_w4"].ctypes.data, f["h_b4"].ctypes.data
     if f["gn"] == "st":
         op.gn_st0, op.gn_st1 = f["d_st0"].data_ptr(), (f["d_st1"].data_ptr() if f["C1"] else None)
         op.gn_gamma, op.gn_beta, op.gn_groups, op.gn_eps = f["d_gamma"].data_ptr(), f["d_beta"].data_ptr(), f["groups"], GN_EPS
+    return op
+
+
+def _conv_choice(f):
+    """The kernel the library's dispatcher would run case data `f` on under the current options (use_conv_choice: nothing is launched)."""
+    L = _lib()
+    op = _conv_op(f, 0, f["d_src0"].data_ptr(), f["d_src0"].data_ptr() if f["stats"] else None)      # (present / absent is all that counts)
+    name = C.create_string_buffer(32)
+    L.check(L.lib().use_conv_choice(C.byref(op), name, 32, None), "use_conv_choice")
+    return name.value.decode()
+
+
+def _run_conv(f, variant):
+    """One use_op_conv of case data `f` (dict) with the given variant: (rc, out, stats) on the CPU, the sentinels checked."""
+    L = _lib()
+    B, H, W, Cout, odt = f["B"], f["H"], f["W"], f["Cout"], f["odt"]
+    obuf, out = _guarded((B, H, W, Cout), TD[odt], SENTINEL)
+    sbuf = stats = None
+    if f["stats"]:
+        sbuf = torch.full((B * Cout * 2 + TAIL,), 0x5A5A5A5A5A5A, dtype=torch.int64, device="cuda")
+        sbuf[:B * Cout * 2] = 0
+        stats = sbuf[:B * Cout * 2].view(B, Cout, 2)
+    op = _conv_op(f, variant, out.data_ptr(), stats.data_ptr() if stats is not None else None)
     rc = L.lib().use_op_conv(C.byref(op), _stream())
     torch.cuda.synchronize()
     if rc != 0:
@@ -485,24 +500,17 @@ for dt in (1, 2):
     _add(1, dt, 1, 40, 16, 128, 4, odt=0, gn="coef", act=1, res=1)
 
 
-def _v2_eligible(c):
-    """conv_v2_eligible (use_conv_v2.hip) of a case."""
-    ck = 32 if c["dt"] == 0 else 64
-    Cin, XC = c["C0"] + c.get("C1", 0), c.get("XC0", 0) + c.get("XC1", 0)
-    return (c.get("ntaps", 9) == 9 and c["Cout"] > 32 and c.get("odt", c["dt"]) == c["dt"] and Cin % ck == 0 and Cin <= 1024 and
-            XC % ck == 0 and (not c.get("C1") or c["C0"] % ck == 0) and (not c.get("XC1") or c["XC0"] % ck == 0) and
-            c["H"] >= 16 and c["W"] >= 16)
+# what use_conv_choice may name when the dispatcher runs a case on the kernel its forced variant runs (variant 1: the pyramid head is one of its kernels)
+CHOICE = {7: ("conv_sk",), 2: ("conv_v2",), 4: ("conv_v4",), 5: ("conv_v5",), 1: ("conv_generic", "pyr_conv", "pyr_conv_ws")}
 
 
 def _dispatch_options(c):
-    """Options under which variant 0 (the library's dispatcher) must pick the case's kernel, or None when it picks another one.
-    conv_sk is switched off for the other kernels (fp32 sends every map up to 64 x 64 to it), conv_v4_min_blocks lowered for conv_v4 /
-    conv_v5 on these small maps, conv_v5 switched off for 16-bit conv_v4."""
+    """Options under which variant 0 (the library's dispatcher) picks the case's kernel: conv_sk is switched off for the other kernels
+    (fp32 sends every map up to 64 x 64 to it), conv_v4_min_blocks lowered for conv_v4 / conv_v5 on these small maps, conv_v5 switched
+    off for 16-bit conv_v4."""
     k = c["kern"]
     if k == 7:
         return {}
-    if k == 1 and _v2_eligible(c):
-        return None
     opts = {"conv_sk_max_px": 0}
     if k in (4, 5):
         opts["conv_v4_min_blocks"] = 1
@@ -517,16 +525,18 @@ def test_conv_kernel_matches_float64_reference(c):
     f, ref, S, creal = _make_case(c, seed=len(_case_id(c)) * 7919 + CASES.index(c))
     rc, out, stats = _run_conv(f, kern)
     assert rc == 0, _lib().lib().use_last_error()
-    opts = _dispatch_options(c)
     out0 = stats0 = None
-    if opts is not None:
-        try:
-            for k, v in opts.items():
-                _set_option(k, v)
+    try:
+        for k, v in _dispatch_options(c).items():
+            _set_option(k, v)
+        chosen = _conv_choice(f)
+        # the dispatcher picks the case's kernel - except that conv_v2 takes what it can run of the generic kernel's cases
+        assert chosen in CHOICE[kern] or (kern == 1 and chosen == "conv_v2"), f"the dispatcher picks {chosen}, not {KERNEL[kern]}"
+        if chosen in CHOICE[kern]:
             rc0, out0, stats0 = _run_conv(f, 0)
-        finally:
-            _set_option("conv_sk_max_px", 16 * 20); _set_option("conv_v4_min_blocks", 80); _set_option("conv_v5", 1)
-        assert rc0 == 0
+            assert rc0 == 0
+    finally:
+        _set_option("conv_sk_max_px", 16 * 20); _set_option("conv_v4_min_blocks", 80); _set_option("conv_v5", 1)
     got = out.double()
     assert bool(torch.isfinite(got).all()), "NaN / Inf in the output"
     if creal < f["Cout"]:

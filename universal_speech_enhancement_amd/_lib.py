@@ -121,6 +121,7 @@ SYMBOLS = {
     "use_timesteps": (_i, [_i, _f, C.POINTER(_f)]),
     "use_conv_bench": (_i, [C.POINTER(UseConvCase), _vp, _vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "use_op_conv": (_i, [C.POINTER(UseConvOp), _vp]),
+    "use_conv_choice": (_i, [C.POINTER(UseConvOp), C.c_char_p, _i, C.POINTER(_i)]),
     "use_op_conv_dev_workspace": (C.c_size_t, [C.POINTER(UseConvOp)]),
     "use_op_conv_dev": (_i, [C.POINTER(UseConvOp), _i, _vp, C.c_size_t, _vp]),
     "use_op_fir": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),

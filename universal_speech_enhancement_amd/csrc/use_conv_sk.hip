@@ -377,7 +377,7 @@ void conv_sk_set_max_px(long n) { g_sk_max_px = n; }
 static thread_local bool t_sk_per_image = false;
 void conv_sk_set_per_image(bool on) { t_sk_per_image = on; }
 
-bool conv_sk_eligible(const ConvArgs& a) {
+bool conv_sk_eligible(const ConvDesc& a) {
     const int Ctot = a.C0 + a.C1, XC = a.XC0 + a.XC1;
     // outputs: full 32-channel tiles in the input's type, or the 4- / 8-channel fp32 pyramid heads (weight rows padded to 32)
     const bool full = a.in_dtype == a.out_dtype && a.Cout % 32 == 0 && a.Cout >= 32;

@@ -501,7 +501,7 @@ static void v2_launch_t(const ConvArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(kern, grid, dim3(512), SMEM, s, a);
 }
 
-bool conv_v2_eligible(const ConvArgs& a) {
+bool conv_v2_eligible(const ConvDesc& a) {
     const int Ctot = a.C0 + a.C1, XC = a.XC0 + a.XC1;
     const int ck = a.in_dtype == DT_F32 ? 32 : 64;
     return a.ntaps == 9 && a.Cout > 32 && a.in_dtype == a.out_dtype && Ctot % ck == 0 && Ctot <= 1024 && XC % ck == 0 &&

@@ -966,7 +966,7 @@ void conv_v4_set_min_blocks(long n) { g_v4_min_blocks = n; }
 
 // What the kernel itself can run (launches forced past the dispatcher: use_op_conv / use_conv_bench variants 4 and 5): every condition of
 // conv_v4_eligible except the grid-size threshold and the A/B switch.  Null, or the first violated condition.
-const char* conv_v4_unrunnable(const ConvArgs& a) {
+const char* conv_v4_unrunnable(const ConvDesc& a) {
     const int Ctot = a.C0 + a.C1, XC = a.XC0 + a.XC1;
     const int ck = conv_v4_chunk(a.in_dtype);
     if (a.ntaps != 9) return "ntaps == 9";
@@ -981,11 +981,11 @@ const char* conv_v4_unrunnable(const ConvArgs& a) {
     return nullptr;
 }
 // the same for the Wide16x16 form (forced launches: variant 5): conv_v4's conditions and 16-bit storage
-const char* conv_v5_unrunnable(const ConvArgs& a) {
+const char* conv_v5_unrunnable(const ConvDesc& a) {
     return a.in_dtype == DT_F32 ? "16-bit storage" : conv_v4_unrunnable(a);
 }
 
-bool conv_v4_eligible(const ConvArgs& a) {
+bool conv_v4_eligible(const ConvDesc& a) {
     static const bool off = getenv("USE_HIP_NO_V4") != nullptr && atoi(getenv("USE_HIP_NO_V4")) != 0;   // A/B switch
     // 512-pixel tiles need enough workgroups per image to fill the chip evenly at batch 8; smaller maps stay on conv_v2
     // (use_set_option("conv_v4_min_blocks", n) moves the threshold: the parity tests force the kernel onto small maps)
@@ -996,7 +996,7 @@ bool conv_v4_eligible(const ConvArgs& a) {
 
 static int g_conv_v5 = 1;              // use_set_option("conv_v5", 0): Wide32x32 (32x32x16 MFMAs) for the 16-bit types as well
 void conv_v5_set(int on) { g_conv_v5 = on; }
-bool conv_v5_enabled(const ConvArgs& a) { return g_conv_v5 != 0 && a.in_dtype != DT_F32; }   // (a launch conv_v4_eligible has accepted)
+bool conv_v5_enabled(const ConvDesc& a) { return g_conv_v5 != 0 && a.in_dtype != DT_F32; }   // (a launch conv_v4_eligible has accepted)
 
 template <typename SHAPE>
 static void launch_wide(const ConvArgs& a0, hipStream_t s) {

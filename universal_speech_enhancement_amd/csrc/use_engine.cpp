@@ -179,12 +179,12 @@ struct use_handle {
     // scratch for the stand-alone use_sde_* entry points (independent of weights / plan)
     char* sde_buf = nullptr; unsigned long long* sde_seeds = nullptr; float* sde_step = nullptr; float* sde_partial = nullptr;
     static constexpr int SDE_MAX_B = 1024, SDE_BLOCKS = 128;
-    // per-launch HIP-event profiling of the dominant conv kernel (use_profile_score)
-    bool profile = false, profile_all = false; std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events; std::vector<double> prof_flops, prof_bytes; std::vector<char> prof_main; std::vector<std::pair<int, int>> prof_hw;
-    // ... and of the HBM-bound kernels around it (FIR resampling, pyramid heads, input convolution): name, map, algorithmic bytes
-    struct AuxProf { std::string name; int H = 0, W = 0; double bytes = 0.0; hipEvent_t e0 = nullptr, e1 = nullptr; double ms = 0.0; double flops = 0.0; };
-    std::vector<AuxProf> prof_aux;
-    std::vector<std::string> prof_desc;
+    // per-launch HIP-event profiling (use_profile_score): one record per timed launch, in launch order - the dominant conv kernel (main),
+    // the other convolutions and the HBM-bound kernels around them (FIR resampling, pyramid heads, input convolution).  desc: the line of
+    // USE_HIP_PROFILE_VERBOSE, set for the launches it lists (those are reported there, not as records of use_profile_aux)
+    bool profile = false, profile_all = false;
+    struct ProfRec { std::string label; int H = 0, W = 0; double flops = 0.0, bytes = 0.0; hipEvent_t e0 = nullptr, e1 = nullptr; double ms = 0.0; bool main = false; std::string desc; };
+    std::vector<ProfRec> prof;
     // introspection
     bool dry = false;
     std::map<std::string, Act> debug;
@@ -478,15 +478,16 @@ struct Fwd {
         return a;
     }
 
-    // use_profile_score: HIP events around one launch of an HBM-bound kernel, with its algorithmic bytes (every operand once)
-    template <typename F> void timed_aux(const char* name, int Hm, int Wm, double bytes, F&& launch) {
-        if (!h->profile) { launch(); return; }
-        use_handle::AuxProf a{name, Hm, Wm, bytes, nullptr, nullptr, 0.0};
-        (void)hipEventCreate(&a.e0); (void)hipEventCreate(&a.e1);
-        (void)hipEventRecord(a.e0, s);
+    // use_profile_score: HIP events around one launch, recorded with its class, map and algorithmic bytes (every operand once); the record, or null
+    template <typename F> use_handle::ProfRec* timed_aux(const char* name, int Hm, int Wm, double bytes, F&& launch) {
+        if (!h->profile) { launch(); return nullptr; }
+        use_handle::ProfRec r; r.label = name; r.H = Hm; r.W = Wm; r.bytes = bytes;
+        (void)hipEventCreate(&r.e0); (void)hipEventCreate(&r.e1);
+        (void)hipEventRecord(r.e0, s);
         launch();
-        (void)hipEventRecord(a.e1, s);
-        h->prof_aux.push_back(a);
+        (void)hipEventRecord(r.e1, s);
+        h->prof.push_back(std::move(r));
+        return &h->prof.back();
     }
 
     // coefficient array for the consumers that cannot finalise the GroupNorm themselves (the FIR resampling kernels)
@@ -500,7 +501,8 @@ struct Fwd {
     }
 
     // gn != null: the input concat(a, a2) goes through this GroupNorm, finalised inside the conv kernel from the producers' totals
-    Act conv(const Act& a, const Act* a2, const GNW* gn, int act, const ConvW& w, const float* temb,
+    // temb_row >= 0: + the Dense_0(temb) row of this sub-batch's tembias that starts there
+    Act conv(const Act& a, const Act* a2, const GNW* gn, int act, const ConvW& w, int temb_row,
              const Act* res, float scale, const float* pyr, const CombineW* cb, int out_dtype, bool stats,
              const Act* sx0 = nullptr, const Act* sx1 = nullptr, const ConvW* w2 = nullptr, size_t bias_off = 0) {
         Act o = new_act(w.cout, a.H, a.W, out_dtype, stats);
@@ -508,17 +510,20 @@ struct Fwd {
         if (w2) fl += 2.0 * B * a.H * a.W * (double)w2->cout * w2->cin;
         h->flops += fl;
         // large maps: separate finalize launch into a coefficient array (allocated in the dry run as well: the arena is sized by it)
-        const float* coef_arr = (gn && (long)a.H * a.W > g_gn_inline) ? gn_coef(a, a2, *gn) : nullptr;
-        // Large maps: the producer writes per-workgroup partial totals instead of queueing 640 atomics per item on each total; every consumer
-        // of such a map goes through gn_coef (same threshold), which sums them.  (allocated in the dry run as well: the arena is sized by it)
-        // Only for the two launch shapes that can write them (pointer-free test, so that the dry run sizes the arena like the real one):
-        // the input convolution's walk (conv_in_split_wgs workgroups per item) and conv_v4's tile grid (the buffer used to be
-        // max(tiles, 256, conv_in_wgs) rows for every stats-producing convolution of a large map, whatever kernel ran it).
-        const bool in_shape = a.dtype == DT_F32 && w.cin <= 8 && w.ntaps == 9 && out_dtype != DT_F32;
-        const bool v4_shape = w.ntaps == 9 && w.cout > 32 && a.dtype == out_dtype && a.H % 16 == 0 && a.W % 32 == 0;
-        const int part_rows = in_shape ? conv_in_split_wgs(a.H, a.W) : v4_shape ? conv_v4_tiles(a.H, a.W) : 0;
-        long long* part = (stats && g_stats_part && part_rows > 0 && (long)a.H * a.W > g_gn_inline)
-                              ? (long long*)arena->alloc((size_t)B * part_rows * w.cout * 2 * sizeof(long long)) : nullptr;
+        const bool large = (long)a.H * a.W > g_gn_inline;
+        const float* coef_arr = (gn && large) ? gn_coef(a, a2, *gn) : nullptr;
+        // The launch as the dispatcher sees it, from shapes and flags alone (the dry run has no pointers): the dry run and the real one ask
+        // conv_choose with the same value, once, and its answer sizes the partial-totals buffer, picks stats_part or stats and labels the profile
+        ConvDesc d{};
+        d.H = a.H; d.W = a.W; d.C0 = a.C; d.C1 = a2 ? a2->C : 0; d.XC0 = w2 ? sx0->C : 0; d.XC1 = (w2 && sx1) ? sx1->C : 0;
+        d.Cout = w.cout; d.cout_pad = w.cout_pad; d.ntaps = w.ntaps; d.in_dtype = a.dtype; d.out_dtype = out_dtype; d.act = act;
+        d.coef = gn && large; d.w = true; d.wb = w.has_wb; d.w2 = w2 != nullptr; d.w2b = w2 && w2->has_wb;
+        d.res = res != nullptr; d.pyr = cb != nullptr; d.temb = temb_row >= 0; d.stats = stats;
+        const ConvChoice ch = conv_choose(d);
+        // Large maps: the producer writes per-workgroup partial totals instead of queueing 640 atomics per item on each total (where its kernel
+        // knows that form: ch.stats_parts workgroups per item); every consumer of such a map goes through gn_coef (same threshold), which sums them
+        long long* part = (stats && g_stats_part && ch.stats_parts > 0 && large)
+                              ? (long long*)arena->alloc((size_t)B * ch.stats_parts * w.cout * 2 * sizeof(long long)) : nullptr;
         if (h->dry) return o;
         ConvArgs p{};
         p.src0 = a.p; p.C0 = a.C; p.src1 = a2 ? a2->p : nullptr; p.C1 = a2 ? a2->C : 0; p.in_dtype = a.dtype;
@@ -533,47 +538,28 @@ struct Fwd {
         p.bias = W<float>(w2 ? bias_off : w.b_off);
         if (w2) { p.x0 = sx0->p; p.XC0 = sx0->C; p.x1 = sx1 ? sx1->p : nullptr; p.XC1 = sx1 ? sx1->C : 0; p.w2 = h->blob + w2->w_off;
                   p.w2b = w2->has_wb ? h->blob + w2->wb_off : nullptr; }
-        p.temb = temb; p.temb_bstride = temb_bstride;
+        p.temb = temb_row >= 0 ? tembias + temb_row : nullptr; p.temb_bstride = temb_bstride;
         p.res = res ? res->p : nullptr; p.out_scale = scale;
         p.pyr = pyr; p.w4 = cb ? W<float>(cb->w_off) : nullptr; p.b4 = cb ? W<float>(cb->b_off) : nullptr;
-        p.out = o.p; p.out_dtype = out_dtype; p.stats = o.stats;
+        p.out = o.p; p.out_dtype = out_dtype;
+        if (part) { p.stats_part = part; o.part = part; o.ntiles = ch.stats_parts; } else p.stats = o.stats;
         p.B = B; p.H = a.H; p.W = a.W; p.Cout = w.cout; p.ntaps = w.ntaps;
-        const bool main_variant = conv_v4_eligible(p);        // the dominant kernel (conv_wide_kernel, large maps)
-        if (const int nparts = part ? conv_stats_parts(p) : 0) {
-            if (nparts <= part_rows) { p.stats_part = part; p.stats = nullptr; o.part = part; o.ntiles = nparts; }   // (else: atomics; cannot happen, both count the same grid)
-        }
         // consumers that read the totals directly (inline GroupNorm below gn_inline pixels, the fused attention) must never meet a producer
         // that wrote partial totals instead: both sides test the same H * W > gn_inline - checked here, where the input is consumed
         if (gn && !coef_arr && (a.part || (a2 && a2->part))) { arena->overflow = true; h->dry = true; return o; }   // reported by eval_status as a stale plan
-        if (h->profile && (main_variant || (h->profile_all && conv_v2_eligible(p)))) {
-            hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-            (void)hipEventRecord(e0, s);
-            launch_conv(p, s);
-            (void)hipEventRecord(e1, s);
-            h->prof_events.push_back({e0, e1});
-            h->prof_flops.push_back(fl); h->prof_main.push_back(main_variant); h->prof_hw.push_back({a.H, a.W});
-            {   // algorithmic HBM bytes of this launch: every operand once (input, shortcut input, residual, output, weights)
-                const double es = (double)dtype_size(a.dtype), px = (double)B * a.H * a.W;
-                double by = px * (w.cin + (w2 ? w2->cin : 0)) * es + px * w.cout * dtype_size(out_dtype) * (res ? 2.0 : 1.0);
-                by += (double)w.ntaps * w.cin * w.cout * es + (w2 ? (double)w2->cin * w2->cout * es : 0.0);
-                if (pyr) by += px * 4 * 4;
-                h->prof_bytes.push_back(by);
-            }
-            char d[160]; snprintf(d, sizeof d, "%-28s H=%3d W=%3d Cin=%3d Cout=%3d taps=%d gn=%d res=%d sc=%d", w.wname.c_str(), a.H, a.W, w.cin, w.cout, w.ntaps, gn != nullptr, res != nullptr, w2 ? w2->cin : 0);
-            h->prof_desc.push_back(d);
-        } else if (h->profile && w.ntaps == 9 && w.cout > 8 && !(a.dtype == DT_F32 && w.cin <= 8)) {
-            // the other implicit-GEMM kernels (conv_v2 on the middle maps, conv_sk on the smallest): MFMA-bound records of the aux list
-            const double es = (double)dtype_size(a.dtype), px = (double)B * a.H * a.W;
-            double by = px * (w.cin + (w2 ? w2->cin : 0)) * es + px * w.cout * dtype_size(out_dtype) * (res ? 2.0 : 1.0);
-            by += (double)w.ntaps * w.cin * w.cout * es + (w2 ? (double)w2->cin * w2->cout * es : 0.0);
-            timed_aux(conv_sk_eligible(p) ? "conv_sk" : conv_v2_eligible(p) ? "conv_v2" : "conv_generic", a.H, a.W, by, [&] { launch_conv(p, s); });
-            h->prof_aux.back().flops = fl;
-        } else if (h->profile && (w.cout <= 8 || (a.dtype == DT_F32 && w.cin <= 8))) {
-            const double px = (double)B * a.H * a.W;
-            const double by = px * w.cin * dtype_size(a.dtype) + px * w.cout * dtype_size(out_dtype) * (res ? 2.0 : 1.0) + (double)w.ntaps * w.cin * w.cout * dtype_size(a.dtype);
-            timed_aux(w.cout <= 8 ? "pyr_conv" : "conv_in", a.H, a.W, by, [&] { launch_conv(p, s); });
-        } else {
-            launch_conv(p, s);
+        const bool main_variant = ch.k == WIDE32 || ch.k == WIDE16;           // the dominant kernel (conv_wide_kernel, large maps)
+        if (!h->profile || (w.ntaps != 9 && !ch.hbm)) { launch_conv(p, s); return o; }       // (the 1x1 convolutions are not timed)
+        // algorithmic HBM bytes of this launch: every operand once (input, shortcut input, residual, output, weights; the dominant kernel's Combine input)
+        const double es = (double)dtype_size(a.dtype), px = (double)B * a.H * a.W;
+        double by = px * (w.cin + (w2 ? w2->cin : 0)) * es + px * w.cout * dtype_size(out_dtype) * (res ? 2.0 : 1.0);
+        by += (double)w.ntaps * w.cin * w.cout * es + (w2 ? (double)w2->cin * w2->cout * es : 0.0);
+        if (pyr && main_variant) by += px * 4 * 4;
+        use_handle::ProfRec* r = timed_aux(ch.label, a.H, a.W, by, [&] { launch_conv(p, s); });
+        r->main = main_variant; r->flops = ch.hbm ? 0.0 : fl;          // (HBM-bound layers: no FLOPs in their records)
+        // listed by USE_HIP_PROFILE_VERBOSE: the dominant kernel's launches and whatever conv_v2 could run (its own launches and, as before, those conv_sk took from it)
+        if (main_variant || (h->profile_all && conv_v2_eligible(d))) {
+            char t[160]; snprintf(t, sizeof t, "%-28s H=%3d W=%3d Cin=%3d Cout=%3d taps=%d gn=%d res=%d sc=%d", w.wname.c_str(), a.H, a.W, w.cin, w.cout, w.ntaps, gn != nullptr, res != nullptr, w2 ? w2->cin : 0);
+            r->desc = t;
         }
         return o;
     }
@@ -581,7 +567,7 @@ struct Fwd {
     // ResnetBlockBigGANpp.forward (reference layerspp.py:282-314). `skip` = second half of the channel concat.
     Act resblock(const Act& x, const Act* skip, const ResW& r, const float* pyr = nullptr, const CombineW* cb = nullptr) {
         const float rs = 0.70710678118654752440f;   // 1/sqrt(2)
-        const float* temb = tembias ? tembias + r.dense_row0 : nullptr;    // unconditional: no Dense_0(temb) term
+        const int temb = h->cfg.unconditional ? -1 : r.dense_row0;         // unconditional: no Dense_0(temb) term
         const int dt = h->act_dtype;
         Act hcur, xr;
         const Act* sx0 = &x; const Act* sx1 = skip;          // inputs of the 1x1 shortcut (Conv_2)
@@ -602,8 +588,8 @@ struct Fwd {
             hcur = conv(x, skip, &r.gn0, 1, r.c0, temb, nullptr, 1.f, nullptr, nullptr, dt, true);
         }
         if (r.has_c2)   // Conv_1 and the Conv_2 shortcut accumulate into the same MFMA tile (one K loop)
-            return conv(hcur, nullptr, &r.gn1, 1, r.c1, nullptr, nullptr, rs, pyr, cb, dt, true, sx0, sx1, &r.c2, r.b12_off);
-        return conv(hcur, nullptr, &r.gn1, 1, r.c1, nullptr, &x, rs, pyr, cb, dt, true);
+            return conv(hcur, nullptr, &r.gn1, 1, r.c1, -1, nullptr, rs, pyr, cb, dt, true, sx0, sx1, &r.c2, r.b12_off);
+        return conv(hcur, nullptr, &r.gn1, 1, r.c1, -1, &x, rs, pyr, cb, dt, true);
     }
 
     // AttnBlockpp.forward (reference layerspp.py:77-93)
@@ -623,9 +609,9 @@ struct Fwd {
             launch_attn_fused(a, dt, B, s);
             return o;
         }
-        Act q = conv(x, nullptr, &aw.gn, 0, aw.q, nullptr, nullptr, 1.f, nullptr, nullptr, dt, false);
-        Act k = conv(x, nullptr, &aw.gn, 0, aw.k, nullptr, nullptr, 1.f, nullptr, nullptr, dt, false);
-        Act v = conv(x, nullptr, &aw.gn, 0, aw.v, nullptr, nullptr, 1.f, nullptr, nullptr, dt, false);
+        Act q = conv(x, nullptr, &aw.gn, 0, aw.q, -1, nullptr, 1.f, nullptr, nullptr, dt, false);
+        Act k = conv(x, nullptr, &aw.gn, 0, aw.k, -1, nullptr, 1.f, nullptr, nullptr, dt, false);
+        Act v = conv(x, nullptr, &aw.gn, 0, aw.v, -1, nullptr, 1.f, nullptr, nullptr, dt, false);
         Act a = new_act(x.C, x.H, x.W, dt, false);
         const int N = x.H * x.W;
         const int ck = dt == DT_F32 ? 32 : 64;
@@ -660,7 +646,7 @@ struct Fwd {
         } else if (!h->dry) {
             launch_attention(q.p, k.p, v.p, a.p, dt, B, N, x.C, s);
         }
-        return conv(a, nullptr, nullptr, 0, aw.o, nullptr, &x, 0.70710678118654752440f, nullptr, nullptr, dt, true);
+        return conv(a, nullptr, nullptr, 0, aw.o, -1, &x, 0.70710678118654752440f, nullptr, nullptr, dt, true);
     }
 
     // NCSNpp.forward (reference ncsnpp.py:324-501): x4 = packed network input, returns the fp32 pyramid [B,F,T,4]
@@ -681,7 +667,7 @@ struct Fwd {
         const int pcp = H->pcp;
         Act xin; xin.p = (void*)x4; xin.C = pcp; xin.H = c.n_freq; xin.W = H->T; xin.dtype = DT_F32;
         std::vector<Act> hs;
-        hs.push_back(conv(xin, nullptr, nullptr, 0, H->conv_in, nullptr, nullptr, 1.f, nullptr, nullptr, dt, true));
+        hs.push_back(conv(xin, nullptr, nullptr, 0, H->conv_in, -1, nullptr, 1.f, nullptr, nullptr, dt, true));
         if (primary) H->debug["h_in"] = hs.back();
         Act ipyr = xin;
         size_t ri = 0, ci = 0;
@@ -722,12 +708,12 @@ struct Fwd {
             }
             const PyrW& pw = H->pyrs[pi++];
             if (!have_pyr) {
-                pyr = conv(hc, nullptr, &pw.gn, 1, pw.conv, nullptr, nullptr, 1.f, nullptr, nullptr, DT_F32, false);
+                pyr = conv(hc, nullptr, &pw.gn, 1, pw.conv, -1, nullptr, 1.f, nullptr, nullptr, DT_F32, false);
                 have_pyr = true;
             } else {
                 Act up = new_act(pcp, pyr.H * 2, pyr.W * 2, DT_F32, false);             // pyramid_upsample
                 if (!H->dry) launch_fir_up2(pyr.p, DT_F32, nullptr, 0, nullptr, up.p, B, pyr.H, pyr.W, pcp, s);
-                pyr = conv(hc, nullptr, &pw.gn, 1, pw.conv, nullptr, &up, 1.f, nullptr, nullptr, DT_F32, false);
+                pyr = conv(hc, nullptr, &pw.gn, 1, pw.conv, -1, &up, 1.f, nullptr, nullptr, DT_F32, false);
             }
             if (lvl != 0) hc = resblock(hc, nullptr, H->res[ri++]);
         }
@@ -1349,34 +1335,28 @@ int use_profile_score(use_handle* h, const void* x, const void* y, const float* 
     int rc = check_ready(h); if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     hipEvent_t t0, t1; HIPCHK(hipEventCreate(&t0)); HIPCHK(hipEventCreate(&t1));
-    h->profile = true; h->prof_events.clear(); h->prof_flops.clear(); h->prof_bytes.clear(); h->prof_desc.clear(); h->prof_main.clear();
-    for (auto& a : h->prof_aux) { if (a.e0) (void)hipEventDestroy(a.e0); if (a.e1) (void)hipEventDestroy(a.e1); }
-    h->prof_aux.clear();
+    h->profile = true;
+    for (auto& r : h->prof) { if (r.e0) (void)hipEventDestroy(r.e0); if (r.e1) (void)hipEventDestroy(r.e1); }
+    h->prof.clear();
     const bool verbose = getenv("USE_HIP_PROFILE_VERBOSE") != nullptr;
     h->profile_all = verbose;                                 // verbose: also list the conv_v2_kernel launches
     HIPCHK(hipEventRecord(t0, s));
     rc = use_score(h, x, y, t, out, stream);
-    h->profile = false;
+    h->profile = false; h->profile_all = false;
     if (rc) return rc;
     HIPCHK(hipEventRecord(t1, s));
     HIPCHK(hipStreamSynchronize(s));
     double ms = 0.0, fl = 0.0, by = 0.0; int nmain = 0;
-    for (size_t i = 0; i < h->prof_events.size(); ++i) {
-        float e = 0.f; HIPCHK(hipEventElapsedTime(&e, h->prof_events[i].first, h->prof_events[i].second));
-        if (h->prof_main[i]) {
-            ms += e; fl += h->prof_flops[i]; by += h->prof_bytes[i]; ++nmain;
-            // also as a record of the aux list, so that callers can break the dominant kernel down by map (bench.py: roofline.by_map)
-            use_handle::AuxProf r; r.name = "conv_v4"; r.H = h->prof_hw[i].first; r.W = h->prof_hw[i].second; r.bytes = h->prof_bytes[i]; r.ms = e; r.flops = h->prof_flops[i];
-            h->prof_aux.push_back(r);
-        }
-        if (verbose) fprintf(stderr, "[use_profile] %s  %8.3f ms  %7.1f TFLOP/s\n", h->prof_desc[i].c_str(), e, h->prof_flops[i] / e / 1e9);
-        (void)hipEventDestroy(h->prof_events[i].first); (void)hipEventDestroy(h->prof_events[i].second);
+    for (auto& r : h->prof) {
+        float e = 0.f; HIPCHK(hipEventElapsedTime(&e, r.e0, r.e1));
+        r.ms = e; (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); r.e0 = r.e1 = nullptr;
+        if (r.main) { ms += e; fl += r.flops; by += r.bytes; ++nmain; }
+        if (verbose && !r.desc.empty()) fprintf(stderr, "[use_profile] %s  %8.3f ms  %7.1f TFLOP/s\n", r.desc.c_str(), e, r.flops / e / 1e9);
     }
-    for (auto& a : h->prof_aux) {
-        if (!a.e0) continue;                                 // (the per-launch records of the dominant kernel appended above)
-        float e = 0.f; HIPCHK(hipEventElapsedTime(&e, a.e0, a.e1));
-        a.ms = e; (void)hipEventDestroy(a.e0); (void)hipEventDestroy(a.e1); a.e0 = a.e1 = nullptr;
-    }
+    // what use_profile_aux reports: the records outside the verbose listing in launch order, then the dominant kernel's own launches
+    // ("conv_v4"), so that callers can break it down by map (bench.py: roofline.by_map)
+    h->prof.erase(std::remove_if(h->prof.begin(), h->prof.end(), [](const use_handle::ProfRec& r) { return !r.main && !r.desc.empty(); }), h->prof.end());
+    std::stable_partition(h->prof.begin(), h->prof.end(), [](const use_handle::ProfRec& r) { return !r.main; });
     float tot = 0.f; HIPCHK(hipEventElapsedTime(&tot, t0, t1));
     (void)hipEventDestroy(t0); (void)hipEventDestroy(t1);
     if (conv_ms) *conv_ms = ms;
@@ -1384,24 +1364,22 @@ int use_profile_score(use_handle* h, const void* x, const void* y, const float* 
     if (conv_bytes) *conv_bytes = by;
     if (conv_launches) *conv_launches = nmain;
     if (total_ms) *total_ms = tot;
-    h->profile_all = false;
-    h->prof_events.clear(); h->prof_flops.clear(); h->prof_bytes.clear(); h->prof_main.clear(); h->prof_hw.clear();
     return USE_OK;
 }
 
 int use_profile_aux(use_handle* h, int index, char* name, int name_cap, int* H, int* W, double* bytes, double* ms) {
     if (!h) return fail(USE_E_INVALID, "null handle");
-    if (index < 0 || index >= (int)h->prof_aux.size()) return 1;          // past the end (not an error: the caller iterates)
-    const auto& a = h->prof_aux[(size_t)index];
-    if (name && name_cap > 0) { strncpy(name, a.name.c_str(), (size_t)name_cap - 1); name[name_cap - 1] = 0; }
+    if (index < 0 || index >= (int)h->prof.size()) return 1;              // past the end (not an error: the caller iterates)
+    const auto& a = h->prof[(size_t)index];
+    if (name && name_cap > 0) { strncpy(name, a.label.c_str(), (size_t)name_cap - 1); name[name_cap - 1] = 0; }
     if (H) *H = a.H; if (W) *W = a.W; if (bytes) *bytes = a.bytes; if (ms) *ms = a.ms;
     return USE_OK;
 }
 
 int use_profile_aux_flops(use_handle* h, int index, double* flops) {
     if (!h) return fail(USE_E_INVALID, "null handle");
-    if (index < 0 || index >= (int)h->prof_aux.size()) return 1;
-    if (flops) *flops = h->prof_aux[(size_t)index].flops;
+    if (index < 0 || index >= (int)h->prof.size()) return 1;
+    if (flops) *flops = h->prof[(size_t)index].flops;
     return USE_OK;
 }
 
@@ -2144,6 +2122,55 @@ __global__ void to_float_kernel(const void* p, float* out, size_t n, int dtype) 
 // use_conv_op::temb_bstride: 0 = Cout (one row per item), -1 = one row shared by the batch, else the stride in elements
 static int op_temb_bstride(const use_conv_op* c) { return c->temb_bstride == 0 ? c->Cout : c->temb_bstride < 0 ? 0 : c->temb_bstride; }
 
+// The network's input convolution as the engine issues it: 3x3 over the 4 (or 8: 6 + 2 padding) packed fp32 input channels.  use_op_conv
+// does not run it (channel counts there are multiples of 32); use_conv_choice answers for it, with the weight copies the engine keeps
+static bool op_is_net_input(int C0, int C1, int XC, int ntaps, int dt) { return dt == DT_F32 && (C0 == 4 || C0 == 8) && C1 == 0 && XC == 0 && ntaps == 9; }
+// The op surface's weight layout as a launch description: Cout padded to 32 or to a multiple of 128, slab-major copies (wb / w2b) wherever
+// conv_wide_kernel's K chunk divides the channels; the dimensions and types; no optional operand
+static ConvDesc op_desc(int H, int W, int C0, int C1, int XC0, int XC1, int Cout, int ntaps, int dt, int odt, int act) {
+    ConvDesc d{};
+    d.H = H; d.W = W; d.C0 = C0; d.C1 = C1; d.XC0 = XC0; d.XC1 = XC1; d.Cout = Cout; d.ntaps = ntaps; d.in_dtype = dt; d.out_dtype = odt; d.act = act;
+    d.cout_pad = Cout <= 32 ? 32 : (Cout + 127) / 128 * 128;
+    const int XC = XC0 + XC1, ck = conv_v4_chunk(dt);
+    d.w = true; d.wb = ntaps == 9 && d.cout_pad % 128 == 0 && (C0 + C1) % ck == 0;
+    if (op_is_net_input(C0, C1, XC, ntaps, dt)) d.wb = odt != DT_F32 && C0 == 4 && d.cout_pad % 128 == 0;    // the engine's split-bf16 copy (lay_conv_in)
+    d.w2 = XC > 0; d.w2b = XC > 0 && XC % ck == 0 && d.cout_pad % 128 == 0;
+    return d;
+}
+// ... of a use_conv_op: the presence flags from the op's own fields (what use_op_conv launches and use_conv_choice asks about)
+static ConvDesc op_conv_desc(const use_conv_op* c) {
+    ConvDesc d = op_desc(c->H, c->W, c->C0, c->C1, c->XC0, c->XC1, c->Cout, c->ntaps == 1 ? 1 : 9, c->dtype, c->out_dtype, c->act);
+    d.coef = c->coef != nullptr; d.res = c->res != nullptr; d.pyr = c->pyr != nullptr; d.temb = c->temb != nullptr; d.stats = c->stats != nullptr;
+    return d;
+}
+// the operands of a use_conv_op other than its weights and its fused shortcut, into the launch arguments
+static void op_conv_operands(const use_conv_op* c, const ConvDesc& d, const float* bias, ConvArgs& a) {
+    a.B = c->B; a.H = c->H; a.W = c->W; a.Cout = c->Cout; a.ntaps = d.ntaps; a.in_dtype = d.in_dtype; a.out_dtype = d.out_dtype;
+    a.src0 = c->src0; a.src1 = c->C1 ? c->src1 : nullptr; a.C0 = c->C0; a.C1 = c->C1; a.coef = c->coef; a.act = c->act;
+    a.bias = bias; a.temb = c->temb; a.temb_bstride = op_temb_bstride(c); a.res = c->res; a.out_scale = c->out_scale;
+    a.out = c->out; a.stats = c->stats;
+}
+// hipMalloc into a list the caller frees; null: out of memory
+static void* dev_alloc(std::vector<void*>& bufs, size_t bytes) { void* q = nullptr; if (hipMalloc(&q, bytes) != hipSuccess) return nullptr; bufs.push_back(q); return q; }
+// Host fp32 weights `hw` [Cout][Cin][ntaps] (and `hw2` [Cout][XC] of the fused shortcut) -> the kernels' layouts as `d` describes them, packed,
+// uploaded into buffers added to `bufs` and entered into the weight fields of `a`.  false: an allocation failed.
+static bool stage_conv_weights(const ConvDesc& d, const float* hw, const float* hw2, std::vector<void*>& bufs, ConvArgs& a) {
+    auto stage = [&](const float* src, int cin, int ntaps, bool slab, const void** dst, const void** dstb) {
+        ConvW w; w.cin = w.cin_src = cin; w.cout = w.cout_src = d.Cout; w.cout_pad = d.cout_pad; w.ntaps = ntaps; w.w_dtype = d.in_dtype;
+        const size_t bytes = (size_t)ntaps * d.cout_pad * cin * dtype_size(d.in_dtype);
+        char* q = (char*)dev_alloc(bufs, bytes); char* qb = slab ? (char*)dev_alloc(bufs, bytes) : nullptr;
+        if (!q || (slab && !qb)) return false;
+        std::vector<char> hp(bytes), hpb(slab ? bytes : 0);
+        pack_conv_raw(src, w, hp.data(), slab ? hpb.data() : nullptr);
+        (void)hipMemcpy(q, hp.data(), bytes, hipMemcpyHostToDevice);
+        if (slab) (void)hipMemcpy(qb, hpb.data(), bytes, hipMemcpyHostToDevice);
+        *dst = q; *dstb = qb;
+        return true;
+    };
+    a.cout_pad = d.cout_pad;
+    return stage(hw, d.C0 + d.C1, d.ntaps, d.wb, &a.w, &a.wb) && (!d.w2 || stage(hw2, d.XC0 + d.XC1, 1, d.w2b, &a.w2, &a.w2b));
+}
+
 int use_conv_bench(const use_conv_case* c, float* out_host, float* stats_host, double* ms_avg, double* flops) {
     if (!c || c->B < 1 || c->H < 1 || c->W < 1 || c->C0 < 1 || c->Cout < 1) return fail(USE_E_INVALID, "bad conv case");
     const int dt = c->dtype;
@@ -2152,18 +2179,15 @@ int use_conv_bench(const use_conv_case* c, float* out_host, float* stats_host, d
     const int Cin = c->C0 + c->C1, XC = c->XC0 + c->XC1;
     const size_t px = (size_t)c->B * c->H * c->W;
     std::vector<void*> bufs;
-    auto dalloc = [&](size_t bytes) -> void* { void* q = nullptr; if (hipMalloc(&q, bytes) != hipSuccess) return nullptr; bufs.push_back(q); return q; };
+    auto dalloc = [&](size_t bytes) { return dev_alloc(bufs, bytes); };
     auto cleanup = [&]() { for (void* q : bufs) (void)hipFree(q); };
     auto fill = [&](void* q, size_t n, int dtype, unsigned seed, float lo, float hi) {
         hipLaunchKernelGGL(fill_uniform_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, q, n, dtype, seed, lo, hi);
     };
-    ConvW w; w.cin = Cin; w.cout = c->Cout; w.ntaps = 9; w.w_dtype = dt; w.cin_src = Cin; w.cout_src = c->Cout;
-    w.cout_pad = c->Cout <= 32 ? 32 : (c->Cout + 127) / 128 * 128;
-    ConvW w2 = w; w2.cin = XC; w2.cin_src = XC; w2.ntaps = 1;
+    const ConvDesc d = op_desc(c->H, c->W, c->C0, c->C1, c->XC0, c->XC1, c->Cout, 9, dt, dt, c->act);
     ConvArgs a{};
     a.B = c->B; a.H = c->H; a.W = c->W; a.Cout = c->Cout; a.ntaps = 9; a.in_dtype = dt; a.out_dtype = dt;
     a.C0 = c->C0; a.C1 = c->C1; a.XC0 = c->XC0; a.XC1 = c->XC1; a.act = c->act; a.out_scale = c->res || XC ? 0.70710678f : 1.f;
-    a.cout_pad = w.cout_pad;
     void* src0 = dalloc(px * c->C0 * es); void* src1 = c->C1 ? dalloc(px * c->C1 * es) : nullptr;
     void* x0 = c->XC0 ? dalloc(px * c->XC0 * es) : nullptr; void* x1 = c->XC1 ? dalloc(px * c->XC1 * es) : nullptr;
     void* res = c->res ? dalloc(px * c->Cout * es) : nullptr;
@@ -2171,12 +2195,9 @@ int use_conv_bench(const use_conv_case* c, float* out_host, float* stats_host, d
     float* outf = (float*)dalloc(px * c->Cout * 4);
     float* coef = c->gn ? (float*)dalloc((size_t)c->B * Cin * 2 * 4) : nullptr;
     float* bias = (float*)dalloc((size_t)c->Cout * 4); float* temb = (float*)dalloc((size_t)c->B * c->Cout * 4);
-    const size_t wbytes = (size_t)9 * w.cout_pad * Cin * es, w2bytes = (size_t)w2.cout_pad * std::max(XC, 1) * es;
-    char* dw = (char*)dalloc(wbytes); char* dwb = (char*)dalloc(wbytes);
-    char* dw2 = XC ? (char*)dalloc(w2bytes) : nullptr; char* dw2b = XC ? (char*)dalloc(w2bytes) : nullptr;
     const size_t stats_bytes = (size_t)c->B * c->Cout * 2 * sizeof(long long);
     long long* stats = c->stats ? (long long*)dalloc(stats_bytes) : nullptr;
-    if (!src0 || !out || !outf || !dw || !dwb || (c->stats && !stats)) { cleanup(); return fail(USE_E_NOMEM, "conv bench allocation failed"); }
+    if (!src0 || !out || !outf || (c->stats && !stats)) { cleanup(); return fail(USE_E_NOMEM, "conv bench allocation failed"); }
     fill(src0, px * c->C0, dt, 1, -2.f, 2.f); if (src1) fill(src1, px * c->C1, dt, 2, -2.f, 2.f);
     if (x0) fill(x0, px * c->XC0, dt, 3, -1.f, 1.f); if (x1) fill(x1, px * c->XC1, dt, 4, -1.f, 1.f);
     if (res) fill(res, px * c->Cout, dt, 5, -1.f, 1.f);
@@ -2189,34 +2210,12 @@ int use_conv_bench(const use_conv_case* c, float* out_host, float* stats_host, d
         const float sc = 1.0f / std::sqrt((float)Cin * 9.f / 3.f);
         for (auto& v : hw) v = rnd() * sc;
         for (auto& v : hw2) v = rnd() * (1.0f / std::sqrt((float)std::max(XC, 1) / 3.f));
-        std::vector<char> hp(wbytes), hpb(wbytes);
-        const bool slab = w.cout_pad % 128 == 0 && Cin % conv_v4_chunk(dt) == 0;
-        pack_conv_raw(hw.data(), w, hp.data(), slab ? hpb.data() : nullptr);
-        (void)hipMemcpy(dw, hp.data(), wbytes, hipMemcpyHostToDevice);
-        if (slab) (void)hipMemcpy(dwb, hpb.data(), wbytes, hipMemcpyHostToDevice);
-        a.w = dw; a.wb = slab ? dwb : nullptr;
-        if (XC) {
-            std::vector<char> hq(w2bytes), hqb(w2bytes);
-            const bool slab2 = XC % conv_v4_chunk(dt) == 0 && w2.cout_pad % 128 == 0;
-            pack_conv_raw(hw2.data(), w2, hq.data(), slab2 ? hqb.data() : nullptr);
-            (void)hipMemcpy(dw2, hq.data(), w2bytes, hipMemcpyHostToDevice);
-            if (slab2) (void)hipMemcpy(dw2b, hqb.data(), w2bytes, hipMemcpyHostToDevice);
-            a.w2 = dw2; a.w2b = slab2 ? dw2b : nullptr;
-        }
+        if (!stage_conv_weights(d, hw.data(), hw2.data(), bufs, a)) { cleanup(); return fail(USE_E_NOMEM, "conv bench allocation failed"); }
     }
     a.src0 = src0; a.src1 = src1; a.x0 = x0; a.x1 = x1; a.coef = coef; a.bias = bias; a.temb = c->temb ? temb : nullptr;
     a.temb_bstride = c->Cout; a.res = res; a.out = out; a.stats = stats;
-    auto run = [&]() -> int {
-        switch (c->variant) {
-            case 0: launch_conv(a, 0); return 0;
-            case 1: launch_conv_generic(a, 0); return 0;
-            case 7: if (!conv_sk_eligible(a)) return -1; launch_conv_sk(a, 0); return 0;
-            case 2: if (!conv_v2_eligible(a)) return -1; launch_conv_v2(a, 0); return 0;
-            case 4: if (conv_v4_unrunnable(a)) return -1; launch_conv_v4(a, 0); return 0;
-            case 5: if (conv_v5_unrunnable(a)) return -1; launch_conv_v5(a, 0); return 0;
-            default: return -1;
-        }
-    };
+    const char* why = nullptr;
+    auto run = [&]() -> int { return launch_conv_variant(a, c->variant, 0, &why); };
     if (getenv("USE_HIP_DBG")) a.dbg = atoi(getenv("USE_HIP_DBG"));     // ablation bits (USE_HIP_ABLATE kernels)
     unsigned long long* trace = nullptr;
     if (getenv("USE_HIP_TRACE")) {                            // bring-up (USE_HIP_TRACE_BUILD kernels): stamps of workgroup $USE_HIP_TRACE
@@ -2225,7 +2224,6 @@ int use_conv_bench(const use_conv_case* c, float* out_host, float* stats_host, d
     }
     if (stats) (void)hipMemset(stats, 0, stats_bytes);
     if (run() != 0) {
-        const char* why = c->variant == 4 ? conv_v4_unrunnable(a) : c->variant == 5 ? conv_v5_unrunnable(a) : nullptr;
         cleanup(); return fail(USE_E_INVALID, "variant %d cannot run this case%s%s", c->variant, why ? ": needs " : "", why ? why : "");
     }
     if (hipDeviceSynchronize() != hipSuccess) { cleanup(); return fail(USE_E_HIP, "conv bench: launch failed: %s", hipGetErrorString(hipGetLastError())); }
@@ -2271,89 +2269,75 @@ int use_conv_bench(const use_conv_case* c, float* out_host, float* stats_host, d
 
 // ---- single operators on caller-owned device tensors (NHWC) with host fp32 weights: the kernels of the path one at a time, so that
 // the per-operator golden vectors of the reference (tests/golden/fir.npz, resblock_*.npz, attn.npz) reach the HIP code itself ----
-int use_op_conv(const use_conv_op* c, use_stream_t stream) {
-    if (!c || c->B < 1 || c->H < 1 || c->W < 1 || c->C0 < 1 || c->Cout < 1 || !c->src0 || !c->w || !c->out) return fail(USE_E_INVALID, "use_op_conv: bad argument");
+// what use_op_conv accepts (`who`: the entry point, for the message; net_input_ok: and the network's input convolution); no HIP call
+static int op_conv_check(const use_conv_op* c, const char* who, bool net_input_ok = false) {
+    if (!c || c->B < 1 || c->H < 1 || c->W < 1 || c->C0 < 1 || c->Cout < 1 || !c->src0 || !c->w || !c->out) return fail(USE_E_INVALID, "%s: bad argument", who);
     const int dt = c->dtype, odt = c->out_dtype;
-    if ((dt != DT_F32 && dt != DT_BF16 && dt != DT_F16) || (odt != DT_F32 && odt != DT_BF16 && odt != DT_F16)) return fail(USE_E_INVALID, "use_op_conv: bad dtype");
-    const int Cin = c->C0 + c->C1, XC = c->XC0 + c->XC1, ntaps = c->ntaps == 1 ? 1 : 9;
-    if (Cin % 32 != 0 || XC % 32 != 0 || (c->C1 && c->C0 % 32) || (c->XC1 && c->XC0 % 32)) return fail(USE_E_INVALID, "use_op_conv: channel counts must be multiples of 32 (zero-pad)");
+    if ((dt != DT_F32 && dt != DT_BF16 && dt != DT_F16) || (odt != DT_F32 && odt != DT_BF16 && odt != DT_F16)) return fail(USE_E_INVALID, "%s: bad dtype", who);
+    const int Cin = c->C0 + c->C1, XC = c->XC0 + c->XC1;
+    if ((Cin % 32 != 0 || XC % 32 != 0 || (c->C1 && c->C0 % 32) || (c->XC1 && c->XC0 % 32)) && !(net_input_ok && op_is_net_input(c->C0, c->C1, XC, c->ntaps == 1 ? 1 : 9, dt)))
+        return fail(USE_E_INVALID, "%s: channel counts must be multiples of 32 (zero-pad)", who);
+    if (c->pyr && !c->w4) return fail(USE_E_INVALID, "%s: pyr without w4", who);
+    if (!c->coef && c->gn_st0 && (!c->gn_gamma || !c->gn_beta || c->gn_groups < 1 || Cin % c->gn_groups || (c->C1 && !c->gn_st1)))
+        return fail(USE_E_INVALID, "%s: in-kernel GroupNorm needs gn_gamma, gn_beta, gn_st1 (with C1) and groups dividing C0 + C1", who);
+    if (XC && (!c->w2 || !c->x0)) return fail(USE_E_INVALID, "%s: shortcut without weights / input", who);
+    return USE_OK;
+}
+int use_op_conv(const use_conv_op* c, use_stream_t stream) {
+    int rc = op_conv_check(c, "use_op_conv"); if (rc) return rc;
+    const ConvDesc d = op_conv_desc(c);
+    const int Cin = c->C0 + c->C1, XC = c->XC0 + c->XC1;
     hipStream_t s = (hipStream_t)stream;
-    const size_t es = dtype_size(dt);
-    ConvW w; w.cin = Cin; w.cout = c->Cout; w.ntaps = ntaps; w.w_dtype = dt; w.cin_src = Cin; w.cout_src = c->Cout;
-    w.cout_pad = c->Cout <= 32 ? 32 : (c->Cout + 127) / 128 * 128;
-    ConvW w2 = w; w2.cin = XC; w2.cin_src = XC; w2.ntaps = 1;
     std::vector<void*> bufs;
-    auto dalloc = [&](size_t bytes) -> void* { void* q = nullptr; if (hipMalloc(&q, bytes) != hipSuccess) return nullptr; bufs.push_back(q); return q; };
+    auto dalloc = [&](size_t bytes) { return dev_alloc(bufs, bytes); };
     auto cleanup = [&]() { for (void* q : bufs) (void)hipFree(q); };
-    const size_t wbytes = (size_t)ntaps * w.cout_pad * Cin * es, w2bytes = (size_t)w2.cout_pad * std::max(XC, 1) * es;
-    const bool slab = ntaps == 9 && w.cout_pad % 128 == 0 && Cin % conv_v4_chunk(dt) == 0;
-    const bool slab2 = XC > 0 && XC % conv_v4_chunk(dt) == 0 && w2.cout_pad % 128 == 0;
-    char* dw = (char*)dalloc(wbytes); char* dwb = slab ? (char*)dalloc(wbytes) : nullptr;
-    char* dw2 = XC ? (char*)dalloc(w2bytes) : nullptr; char* dw2b = slab2 ? (char*)dalloc(w2bytes) : nullptr;
-    float* dbias = (float*)dalloc((size_t)w.cout_pad * 4);
-    float* dw4 = c->pyr ? (float*)dalloc((size_t)w.cout_pad * 5 * 4) : nullptr;     // [cout_pad][4] then b4 [cout_pad], zero-padded
-    if (!dw || !dbias || (slab && !dwb) || (XC && !dw2) || (slab2 && !dw2b) || (c->pyr && !dw4)) { cleanup(); return fail(USE_E_NOMEM, "use_op_conv: allocation failed"); }
-    if (c->pyr && !c->w4) { cleanup(); return fail(USE_E_INVALID, "use_op_conv: pyr without w4"); }
-    if (!c->coef && c->gn_st0 && (!c->gn_gamma || !c->gn_beta || c->gn_groups < 1 || Cin % c->gn_groups || (c->C1 && !c->gn_st1))) {
-        cleanup(); return fail(USE_E_INVALID, "use_op_conv: in-kernel GroupNorm needs gn_gamma, gn_beta, gn_st1 (with C1) and groups dividing C0 + C1");
-    }
+    ConvArgs a{};
+    float* dbias = (float*)dalloc((size_t)d.cout_pad * 4);
+    float* dw4 = c->pyr ? (float*)dalloc((size_t)d.cout_pad * 5 * 4) : nullptr;     // [cout_pad][4] then b4 [cout_pad], zero-padded
+    if (!dbias || (c->pyr && !dw4) || !stage_conv_weights(d, c->w, c->w2, bufs, a)) { cleanup(); return fail(USE_E_NOMEM, "use_op_conv: allocation failed"); }
     {
-        std::vector<char> hp(wbytes), hpb(slab ? wbytes : 0);
-        pack_conv_raw(c->w, w, hp.data(), slab ? hpb.data() : nullptr);
-        (void)hipMemcpy(dw, hp.data(), wbytes, hipMemcpyHostToDevice);
-        if (slab) (void)hipMemcpy(dwb, hpb.data(), wbytes, hipMemcpyHostToDevice);
-        if (XC) {
-            if (!c->w2 || !c->x0) { cleanup(); return fail(USE_E_INVALID, "use_op_conv: shortcut without weights / input"); }
-            std::vector<char> hq(w2bytes), hqb(slab2 ? w2bytes : 0);
-            pack_conv_raw(c->w2, w2, hq.data(), slab2 ? hqb.data() : nullptr);
-            (void)hipMemcpy(dw2, hq.data(), w2bytes, hipMemcpyHostToDevice);
-            if (slab2) (void)hipMemcpy(dw2b, hqb.data(), w2bytes, hipMemcpyHostToDevice);
-        }
-        std::vector<float> hb((size_t)w.cout_pad, 0.f);
+        std::vector<float> hb((size_t)d.cout_pad, 0.f);
         if (c->bias) memcpy(hb.data(), c->bias, (size_t)c->Cout * 4);
         (void)hipMemcpy(dbias, hb.data(), hb.size() * 4, hipMemcpyHostToDevice);
         if (c->pyr) {
-            std::vector<float> h4((size_t)w.cout_pad * 5, 0.f);
+            std::vector<float> h4((size_t)d.cout_pad * 5, 0.f);
             memcpy(h4.data(), c->w4, (size_t)c->Cout * 4 * 4);
-            if (c->b4) memcpy(h4.data() + (size_t)w.cout_pad * 4, c->b4, (size_t)c->Cout * 4);
+            if (c->b4) memcpy(h4.data() + (size_t)d.cout_pad * 4, c->b4, (size_t)c->Cout * 4);
             (void)hipMemcpy(dw4, h4.data(), h4.size() * 4, hipMemcpyHostToDevice);
         }
     }
-    ConvArgs a{};
-    a.B = c->B; a.H = c->H; a.W = c->W; a.Cout = c->Cout; a.ntaps = ntaps; a.in_dtype = dt; a.out_dtype = odt;
-    a.src0 = c->src0; a.src1 = c->C1 ? c->src1 : nullptr; a.C0 = c->C0; a.C1 = c->C1; a.coef = c->coef; a.act = c->act;
-    a.w = dw; a.wb = dwb; a.cout_pad = w.cout_pad;
-    a.x0 = XC ? c->x0 : nullptr; a.x1 = c->XC1 ? c->x1 : nullptr; a.XC0 = c->XC0; a.XC1 = c->XC1; a.w2 = dw2; a.w2b = dw2b;
-    a.bias = dbias; a.temb = c->temb; a.temb_bstride = op_temb_bstride(c); a.res = c->res; a.out_scale = c->out_scale;
-    a.out = c->out; a.stats = c->stats;
-    if (c->pyr) { a.pyr = c->pyr; a.w4 = dw4; a.b4 = dw4 + (size_t)w.cout_pad * 4; }
+    op_conv_operands(c, d, dbias, a);
+    a.x0 = XC ? c->x0 : nullptr; a.x1 = c->XC1 ? c->x1 : nullptr; a.XC0 = c->XC0; a.XC1 = c->XC1;
+    if (c->pyr) { a.pyr = c->pyr; a.w4 = dw4; a.b4 = dw4 + (size_t)d.cout_pad * 4; }
     if (!c->coef && c->gn_st0) {                              // finalised in the kernel, gn_inv_n as Fwd::conv computes it
         a.gn_st0 = c->gn_st0; a.gn_st1 = c->C1 ? c->gn_st1 : nullptr; a.gn_gamma = c->gn_gamma; a.gn_beta = c->gn_beta;
         a.gn_groups = c->gn_groups; a.gn_eps = c->gn_eps;
         a.gn_inv_n = 1.0f / ((float)(Cin / c->gn_groups) * (float)(c->H * c->W));
     }
-    int rc = USE_OK;
     const char* why = nullptr;
-    switch (c->variant) {
-        case 0: launch_conv(a, s); break;
-        case 1: launch_conv_generic(a, s); break;
-        case 2: if (!conv_v2_eligible(a)) rc = fail(USE_E_INVALID, "conv_v2 cannot run this case"); else launch_conv_v2(a, s); break;
-        case 4: if ((why = conv_v4_unrunnable(a))) rc = fail(USE_E_INVALID, "conv_v4 cannot run this case: needs %s", why); else launch_conv_v4(a, s); break;
-        case 5: if ((why = conv_v5_unrunnable(a))) rc = fail(USE_E_INVALID, "conv_v5 cannot run this case: needs %s", why); else launch_conv_v5(a, s); break;
-        case 7: if (!conv_sk_eligible(a)) rc = fail(USE_E_INVALID, "conv_sk cannot run this case"); else launch_conv_sk(a, s); break;
-        default: rc = fail(USE_E_INVALID, "use_op_conv: unknown variant %d", c->variant);
-    }
+    const int lr = launch_conv_variant(a, c->variant, s, &why);
+    if (lr == -2) rc = fail(USE_E_INVALID, "use_op_conv: unknown variant %d", c->variant);
+    else if (lr) rc = fail(USE_E_INVALID, "%s cannot run this case%s%s", c->variant == 2 ? "conv_v2" : c->variant == 4 ? "conv_v4" : c->variant == 5 ? "conv_v5" : "conv_sk",
+                           why ? ": needs " : "", why ? why : "");
     if (hipStreamSynchronize(s) != hipSuccess && rc == USE_OK) rc = fail(USE_E_HIP, "use_op_conv: %s", hipGetErrorString(hipGetLastError()));
     cleanup();
     return rc;
 }
+// The kernel the dispatcher (variant 0) would run this op on under the current options, and the per-workgroup partial GroupNorm totals per
+// (item, channel) that kernel could write (0: atomics only).  Host only: no HIP call, nothing is launched.
+int use_conv_choice(const use_conv_op* c, char* name, int name_cap, int* stats_parts) {
+    int rc = op_conv_check(c, "use_conv_choice", true); if (rc) return rc;
+    const ConvChoice ch = conv_choose(op_conv_desc(c));
+    if (name && name_cap > 0) { strncpy(name, conv_kernel_name(ch.k), (size_t)name_cap - 1); name[name_cap - 1] = 0; }
+    if (stats_parts) *stats_parts = ch.stats_parts;
+    return USE_OK;
+}
 // use_op_conv with the weights already in HBM (fp32 parameter tensors: the training path, where they change every step) and a
 // caller-provided workspace: the weights are laid out by a kernel on `stream`, nothing is allocated and nothing synchronises.
 static size_t conv_dev_layout(const use_conv_op* c, size_t* wbytes, bool* slab, int* cout_pad) {
-    const int Cin = c->C0 + c->C1, ntaps = c->ntaps == 1 ? 1 : 9;
-    *cout_pad = c->Cout <= 32 ? 32 : (c->Cout + 127) / 128 * 128;
-    *wbytes = ((size_t)ntaps * *cout_pad * Cin * dtype_size(c->dtype) + 255) / 256 * 256;
-    *slab = ntaps == 9 && *cout_pad % 128 == 0 && Cin % conv_v4_chunk(c->dtype) == 0;
+    const ConvDesc d = op_conv_desc(c);                       // (the layout rule of the host-weight entries)
+    *cout_pad = d.cout_pad; *slab = d.wb;
+    *wbytes = ((size_t)d.ntaps * d.cout_pad * (d.C0 + d.C1) * dtype_size(d.in_dtype) + 255) / 256 * 256;
     return *wbytes * (*slab ? 2 : 1) + (size_t)*cout_pad * 4;
 }
 size_t use_op_conv_dev_workspace(const use_conv_op* c) {
@@ -2377,11 +2361,8 @@ int use_op_conv_dev(const use_conv_op* c, int w_mode, void* work, size_t work_by
     float* dbias = (float*)(dw + wbytes * (slab ? 2 : 1));
     launch_pack_conv_dev((const float*)c->w, w_mode, c->Cout, Cin, ntaps, cout_pad, dt, conv_v4_chunk(dt), dw, dwb, (const float*)c->bias, dbias, s);
     ConvArgs a{};
-    a.B = c->B; a.H = c->H; a.W = c->W; a.Cout = c->Cout; a.ntaps = ntaps; a.in_dtype = dt; a.out_dtype = odt;
-    a.src0 = c->src0; a.src1 = c->C1 ? c->src1 : nullptr; a.C0 = c->C0; a.C1 = c->C1; a.coef = c->coef; a.act = c->act;
+    op_conv_operands(c, op_conv_desc(c), dbias, a);
     a.w = dw; a.wb = dwb; a.cout_pad = cout_pad;
-    a.bias = dbias; a.temb = c->temb; a.temb_bstride = op_temb_bstride(c); a.res = c->res; a.out_scale = c->out_scale;
-    a.out = c->out; a.stats = c->stats;
     launch_conv(a, s);
     HIPCHK(hipGetLastError());
     return USE_OK;

@@ -83,32 +83,61 @@ struct ConvArgs {
     int dbg;                // ablation bits for kernel bring-up (0 in production)
     unsigned long long* trace;   // optional: s_memtime stamps of workgroup 0 (kernel bring-up), else null
 };
-void launch_conv(const ConvArgs& a, hipStream_t s);
-int conv_stats_parts(const ConvArgs& a);                // partial totals per (item, channel) this launch would write (ConvArgs::stats_part), or 0
-// software-pipelined variant for large maps (use_conv_v2.hip); launch_conv dispatches to it when eligible
-bool conv_v2_eligible(const ConvArgs& a);
+// What the choice of a kernel may depend on, and nothing else: no pointers, so that the dry run that sizes the arenas, the launch, the
+// profile and the host-only query (use_conv_choice) all ask with the same value.
+struct ConvDesc {
+    int H, W, C0, C1, XC0, XC1, Cout, cout_pad, ntaps;
+    int in_dtype, out_dtype, act;
+    bool coef, wb, w2, w2b, res, pyr, temb, stats, w;        // the operand is present (stats: GroupNorm totals wanted, in either form)
+};
+inline ConvDesc conv_desc(const ConvArgs& a) {
+    ConvDesc d{};
+    d.H = a.H; d.W = a.W; d.C0 = a.C0; d.C1 = a.C1; d.XC0 = a.XC0; d.XC1 = a.XC1; d.Cout = a.Cout; d.cout_pad = a.cout_pad; d.ntaps = a.ntaps;
+    d.in_dtype = a.in_dtype; d.out_dtype = a.out_dtype; d.act = a.act;
+    d.coef = a.coef != nullptr; d.w = a.w != nullptr; d.wb = a.wb != nullptr; d.w2 = a.w2 != nullptr; d.w2b = a.w2b != nullptr;
+    d.res = a.res != nullptr; d.pyr = a.pyr != nullptr; d.temb = a.temb != nullptr; d.stats = a.stats != nullptr || a.stats_part != nullptr;
+    return d;
+}
+enum ConvKernel { SK, WIDE32, WIDE16, V2, PYR, PYR_WS, IN, IN_SPLIT, GENERIC };
+struct ConvChoice {
+    ConvKernel k;
+    int stats_parts;        // partial totals per (item, channel) the kernel can write (ConvArgs::stats_part), 0: it only knows the atomic form
+    const char* label;      // the launch's class in use_profile_aux: "conv_v4" (both wide forms), "conv_sk", "conv_v2", "conv_generic", "pyr_conv", "conv_in"
+    bool hbm;               // ... an HBM-bound class ("pyr_conv", "conv_in": the network's pyramid heads and input convolution, on whichever kernel)
+};
+// THE dispatch decision: the order sk -> wide -> v2 -> pyr -> in -> generic, and which kernel knows partial totals (use_kernels.hip)
+ConvChoice conv_choose(const ConvDesc& d);
+const char* conv_kernel_name(ConvKernel k);             // "conv_sk", "conv_v4", "conv_v5", "conv_v2", "pyr_conv", "pyr_conv_ws", "conv_in", "conv_in_split", "conv_generic"
+void launch_conv(const ConvArgs& a, hipStream_t s);     // the kernel conv_choose picks
+// a forced kernel (use_op_conv / use_conv_bench `variant`): 0 the dispatcher, 1 generic (no specialised schedule), 2 conv_v2, 4 conv_v4,
+// 5 conv_v5, 7 conv_sk.  0: launched; -1: the kernel cannot run `a` (*why: the violated condition where the kernel names it, else null);
+// -2: unknown variant
+int launch_conv_variant(const ConvArgs& a, int variant, hipStream_t s, const char** why);
+// The per-kernel predicates below stay beside their kernels (they know the tile constants).  conv_choose and launch_conv_variant call them; the
+// one other caller is use_profile_score's verbose listing, which asks conv_v2_eligible what conv_v2 could run, whichever kernel ran it.
+// software-pipelined variant for large maps (use_conv_v2.hip)
+bool conv_v2_eligible(const ConvDesc& d);
 void launch_conv_v2(const ConvArgs& a, hipStream_t s);
 // wide-tile variant (use_conv_v4.hip): 16x32-pixel tiles, K chunks of conv_v4_chunk() channels, slab-major weights
 inline int conv_v4_chunk(int dtype) { return dtype == DT_F32 ? 16 : 32; }
 inline int conv_v4_tiles(int H, int W) { return ((H + 15) / 16) * ((W + 31) / 32); }
 // split-K variant for the small maps (use_conv_sk.hip): 64-pixel x 32/64-channel tiles, the 8 waves of a workgroup split K
-bool conv_sk_eligible(const ConvArgs& a);
+bool conv_sk_eligible(const ConvDesc& d);
 void conv_sk_set_max_px(long n);                         // largest map (H*W) it is used for (default 16x20)
 void launch_conv_sk(const ConvArgs& a, hipStream_t s);
 // Launches of the calling thread choose conv_sk's tile form from the per-image shape alone (as for a batch of one) while this is
 // on: the two forms add K in passes of different width, so the default choice - by the workgroup count of the whole (sub-)batch -
 // makes an item's bits depend on how many items are evaluated with it.  The per-item sampler (use_sample_items) turns it on.
 void conv_sk_set_per_image(bool on);
-void launch_conv_generic(const ConvArgs& a, hipStream_t s);   // conv_kernel / pyr_conv_kernel / conv_in_kernel only (no specialised schedule)
-void pyr_conv_set_ws(int n);                            // wave-specialised form of the same layer (0: off, 1: on, n > 1: workgroups per launch)
-bool conv_v4_eligible(const ConvArgs& a);
-const char* conv_v4_unrunnable(const ConvArgs& a);         // null if conv_v4 can run `a` (forced launches), else the violated condition
+void pyr_conv_set_ws(int n);                            // wave-specialised form of the pyramid head (0: off, 1: on, n > 1: workgroups per launch)
+bool conv_v4_eligible(const ConvDesc& d);
+const char* conv_v4_unrunnable(const ConvDesc& d);         // null if conv_v4 can run `d` (forced launches), else the violated condition
 void conv_v4_set_min_blocks(long n);                     // smallest grid conv_v4 is used for (default 80 workgroups per image)
 void launch_conv_v4(const ConvArgs& a, hipStream_t s);
 // the same kernel on v_mfma_f32_16x16x32 (conv_wide_kernel<Wide16x16>, use_conv_v4.hip; 16-bit storage): less energy per FLOP than the 32x32x16 shape
-const char* conv_v5_unrunnable(const ConvArgs& a);         // the same for conv_v5: conv_v4's conditions and 16-bit storage (defined beside conv_v4_unrunnable)
+const char* conv_v5_unrunnable(const ConvDesc& d);         // the same for conv_v5: conv_v4's conditions and 16-bit storage (defined beside conv_v4_unrunnable)
 void conv_v5_set(int on);                                // use_set_option("conv_v5", 0 / 1), default 1
-bool conv_v5_enabled(const ConvArgs& a);                 // for a launch conv_v4_eligible() accepted
+bool conv_v5_enabled(const ConvDesc& d);                 // for a launch conv_v4_eligible() accepted
 void launch_conv_v5(const ConvArgs& a, hipStream_t s);
 // GroupNorm finalisation for the consumers that take a coefficient array (FIR resampling kernels): per-(b, group) mean / rstd
 // from the per-channel totals of up to two concatenated sources, folded with gamma/beta into coef[b][c] = (a, b): y = a*x + b.

@@ -692,7 +692,7 @@ __global__ __launch_bounds__(512) void pyr_conv_ws_kernel(ConvArgs p, int tiles_
         }
     }
 }
-static bool pyr_conv_eligible(const ConvArgs& a) {
+static bool pyr_conv_eligible(const ConvDesc& a) {
     return a.in_dtype != DT_F32 && a.out_dtype == DT_F32 && a.ntaps == 9 && a.Cout <= 4 && a.C1 == 0 && a.C0 % PYR_CB == 0 &&
            !a.temb && !a.pyr && !a.stats && a.XC0 + a.XC1 == 0;
 }
@@ -1004,7 +1004,7 @@ __global__ __launch_bounds__(256) void conv_in_split_kernel(ConvArgs p, int tile
     }
 }
 int g_conv_in_wgs = 256;
-static bool conv_in_eligible(const ConvArgs& a) {
+static bool conv_in_eligible(const ConvDesc& a) {
     return a.in_dtype == DT_F32 && a.C0 == 4 && a.C1 == 0 && a.ntaps == 9 && !a.coef && !a.act && !a.res && !a.pyr && !a.temb &&
            a.XC0 + a.XC1 == 0 && a.Cout % 8 == 0;
 }
@@ -1015,14 +1015,45 @@ static void conv_launch_t(const ConvArgs& a, hipStream_t s) {
     hipLaunchKernelGGL((conv_kernel<TIN, TOUT, CK, BN, WM, WN>), grid, dim3(256), 0, s, a);
 }
 
-// Workgroups that would each write one partial total per output channel for this launch (ConvArgs::stats_part), 0 if the kernel the
-// dispatch below picks only knows the atomic form.  Mirrors launch_conv's order.
-int conv_stats_parts(const ConvArgs& a) {
-    if (conv_sk_eligible(a)) return 0;
-    if (conv_v4_eligible(a)) return conv_v4_tiles(a.H, a.W);
-    if (conv_v2_eligible(a)) return 0;
-    if (!pyr_conv_eligible(a) && conv_in_eligible(a) && a.wb && a.out_dtype != DT_F32) return conv_in_split_wgs(a.H, a.W);
-    return 0;
+static int g_pyr_ws = 1;          // wave-specialised head: 0 the one-tile-per-workgroup form, 1 on (256 workgroups per launch), n > 1: n workgroups per launch
+void pyr_conv_set_ws(int n) { g_pyr_ws = n; }
+
+// The kernel of a launch, the workgroups that would each write one partial total per output channel for it (ConvArgs::stats_part;
+// 0: the kernel only knows the atomic form) and its profile class.  specialised = false (forced variant 1): the kernels of this
+// file only - pyramid head, input convolution, conv_kernel.
+static ConvChoice choose(const ConvDesc& d, bool specialised) {
+    ConvKernel k = GENERIC;
+    int parts = 0;
+    if (specialised && conv_sk_eligible(d)) k = SK;
+    else if (specialised && conv_v4_eligible(d)) { k = conv_v5_enabled(d) ? WIDE16 : WIDE32; parts = conv_v4_tiles(d.H, d.W); }
+    else if (specialised && conv_v2_eligible(d)) k = V2;
+    else if (pyr_conv_eligible(d)) k = (d.C0 <= 2 * PYR_CB && g_pyr_ws) ? PYR_WS : PYR;
+    else if (conv_in_eligible(d)) {
+        if (d.wb && d.out_dtype != DT_F32) { k = IN_SPLIT; parts = conv_in_split_wgs(d.H, d.W); } else k = IN;
+    }
+    // the profile lists the network's pyramid heads and its input convolution (HBM-bound layers) under one name each, whichever kernel runs them
+    const bool wide = k == WIDE32 || k == WIDE16, head = !wide && d.Cout <= 8, input = !wide && !head && d.in_dtype == DT_F32 && d.C0 + d.C1 <= 8;
+    return {k, parts, wide ? "conv_v4" : head ? "pyr_conv" : input ? "conv_in" : k == SK ? "conv_sk" : k == V2 ? "conv_v2" : "conv_generic", head || input};
+}
+ConvChoice conv_choose(const ConvDesc& d) { return choose(d, true); }
+const char* conv_kernel_name(ConvKernel k) {
+    static const char* const names[] = {"conv_sk", "conv_v4", "conv_v5", "conv_v2", "pyr_conv", "pyr_conv_ws", "conv_in", "conv_in_split", "conv_generic"};
+    return names[k];
+}
+
+static void launch_conv_basic(const ConvArgs& a, ConvKernel k, hipStream_t s);
+int launch_conv_variant(const ConvArgs& a, int variant, hipStream_t s, const char** why) {
+    const ConvDesc d = conv_desc(a);
+    *why = nullptr;
+    switch (variant) {
+        case 0: launch_conv(a, s); return 0;
+        case 1: launch_conv_basic(a, choose(d, false).k, s); return 0;
+        case 2: if (!conv_v2_eligible(d)) return -1; launch_conv_v2(a, s); return 0;
+        case 4: if ((*why = conv_v4_unrunnable(d))) return -1; launch_conv_v4(a, s); return 0;
+        case 5: if ((*why = conv_v5_unrunnable(d))) return -1; launch_conv_v5(a, s); return 0;
+        case 7: if (!conv_sk_eligible(d)) return -1; launch_conv_sk(a, s); return 0;
+        default: return -2;
+    }
 }
 void launch_conv(const ConvArgs& a, hipStream_t s) {
 #ifdef USE_HIP_SKIPDBG   // timing-only bring-up build: drop the convolutions of maps with lo <= H*W <= hi pixels (USE_HIP_SKIP="lo:hi")
@@ -1032,23 +1063,26 @@ void launch_conv(const ConvArgs& a, hipStream_t s) {
         if ((long)a.H * a.W >= lo && (long)a.H * a.W <= hi) return;
     }
 #endif
-    if (conv_sk_eligible(a)) { launch_conv_sk(a, s); return; }
-    if (conv_v4_eligible(a)) { if (conv_v5_enabled(a)) launch_conv_v5(a, s); else launch_conv_v4(a, s); return; }
-    if (conv_v2_eligible(a)) { launch_conv_v2(a, s); return; }
-    launch_conv_generic(a, s);
+    const ConvKernel k = conv_choose(conv_desc(a)).k;
+    switch (k) {
+        case SK: launch_conv_sk(a, s); break;
+        case WIDE32: launch_conv_v4(a, s); break;
+        case WIDE16: launch_conv_v5(a, s); break;
+        case V2: launch_conv_v2(a, s); break;
+        default: launch_conv_basic(a, k, s);
+    }
 }
 
-static int g_pyr_ws = 1;          // wave-specialised head: 0 the one-tile-per-workgroup form, 1 on (256 workgroups per launch), n > 1: n workgroups per launch
-void pyr_conv_set_ws(int n) { g_pyr_ws = n; }
-void launch_conv_generic(const ConvArgs& a, hipStream_t s) {
-    if (pyr_conv_eligible(a)) {
+// the kernels of this file: k = PYR / PYR_WS / IN / IN_SPLIT / GENERIC as choose() answered
+static void launch_conv_basic(const ConvArgs& a, ConvKernel k, hipStream_t s) {
+    if (k == PYR || k == PYR_WS) {
         static LdsAttrOnce attr_set;
         attr_set.once([&] {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pyr_conv_kernel<__bf16>), hipFuncAttributeMaxDynamicSharedMemorySize, PYR_SMEM);
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pyr_conv_kernel<_Float16>), hipFuncAttributeMaxDynamicSharedMemorySize, PYR_SMEM);
         });
         const int ntiles = tiles_per_image(a.H, a.W);
-        if (a.C0 <= 2 * PYR_CB && g_pyr_ws) {                // wave-specialised form: one 8-wave workgroup per CU, the launch is one round of workgroups
+        if (k == PYR_WS) {                                   // wave-specialised form: one 8-wave workgroup per CU, the launch is one round of workgroups
             static LdsAttrOnce attr3;
             attr3.once([&] {
 #define USE_PYRW_ATTR(T, O, A) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pyr_conv_ws_kernel<T, O, A>), hipFuncAttributeMaxDynamicSharedMemorySize, PYRW_SMEM);
@@ -1072,16 +1106,16 @@ void launch_conv_generic(const ConvArgs& a, hipStream_t s) {
         else                       hipLaunchKernelGGL(pyr_conv_kernel<_Float16>, dim3(ntiles, 1, a.B), dim3(256), PYR_SMEM, s, a);
         return;
     }
-    if (conv_in_eligible(a)) {
+    if (k == IN || k == IN_SPLIT) {
         dim3 grid(tiles_per_image(a.H, a.W), (a.Cout + 127) / 128, a.B);
         const int tpw = conv_in_split_tpw(a.H, a.W);
         dim3 grid_s(conv_in_split_wgs(a.H, a.W), (a.Cout + 127) / 128, a.B);
         const bool full = a.H % TILE_H == 0 && a.W % TILE_W == 0 && a.Cout % 128 == 0;      // whole tiles, whole channel blocks: no masks in the epilogue
 #define USE_CINS_GO(T) { if (full) hipLaunchKernelGGL((conv_in_split_kernel<T, true>), grid_s, dim3(256), 0, s, a, tpw); \
                          else hipLaunchKernelGGL((conv_in_split_kernel<T, false>), grid_s, dim3(256), 0, s, a, tpw); }
-        if (a.out_dtype == DT_BF16)     { if (a.wb) USE_CINS_GO(__bf16)
+        if (a.out_dtype == DT_BF16)     { if (k == IN_SPLIT) USE_CINS_GO(__bf16)
                                           else      hipLaunchKernelGGL((conv_in_kernel<__bf16>), grid, dim3(256), 0, s, a); }
-        else if (a.out_dtype == DT_F16) { if (a.wb) USE_CINS_GO(_Float16)
+        else if (a.out_dtype == DT_F16) { if (k == IN_SPLIT) USE_CINS_GO(_Float16)
                                           else      hipLaunchKernelGGL((conv_in_kernel<_Float16>), grid, dim3(256), 0, s, a); }
 #undef USE_CINS_GO
         else                            hipLaunchKernelGGL((conv_in_kernel<float>), grid, dim3(256), 0, s, a);
