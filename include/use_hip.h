@@ -105,7 +105,8 @@ int use_load_weight_blob(use_handle* h, const char* path);
 int use_num_expected_weights(use_handle* h);
 int use_expected_weight(use_handle* h, int index, const char** name, int64_t* shape4, int* ndim);
 
-/* Workspace for batch B and T' padded frames (multiple of 64).  Re-planning is allowed. */
+/* Workspace for batch B and T' padded frames (multiple of 64).  Re-planning is allowed.
+ * After a failing use_plan the handle has no plan: evaluations answer USE_E_STATE until a use_plan succeeds. */
 int use_plan(use_handle* h, int B, int Tpad);
 int use_workspace_bytes(use_handle* h, size_t* bytes);
 

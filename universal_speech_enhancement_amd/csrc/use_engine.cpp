@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <unordered_map>
@@ -108,6 +109,59 @@ struct Arena {
     }
 };
 
+// Everything use_plan(B, T') builds for one shape.  A plan is a value with one owner - the handle's `plan` (the current one) or a slot of
+// its `parked` list - and its destructor frees what it owns.  Never copied or moved: the arenas point at `dry`, captured graphs hold addresses.
+struct Plan {
+    int B = 0, T = 0;
+    long long opt_gen = -1;                      // g_opt_gen when the plan was built: plans built under other options are not reused
+    Arena arena;                                 // base: the workspace allocation (all sub-batch arenas + GroupNorm totals, arena_plan_bytes)
+    size_t arena_plan_bytes = 0;
+    char* persist = nullptr; size_t persist_bytes = 0;
+    float *x4 = nullptr, *silu_temb = nullptr, *tembias = nullptr, *t_dev = nullptr;
+    float2 *Y = nullptr, *X = nullptr, *Xmean = nullptr, *score = nullptr, *xin = nullptr;
+    float2 *cond_buf = nullptr, *cond2_buf = nullptr;   // cond2: the second conditioning spectrogram of condition="both" (6 input channels)
+    float2 *Cond = nullptr;                      // score conditioning of the sampler: == Y unless use_sample_cond gave another
+    float *lang_partial = nullptr;
+    float* lang_step = nullptr;                  // [B] Langevin steps: one per item (use_sample_items), or [0] for the batch
+    unsigned long long* seeds = nullptr;         // [B] Philox seeds: one per item, or [0] for the shared stream.  Every call uploads its own
+                                                 // before its launches; the kernels read them, so graphs replay with new seeds
+    int lang_blocks = 0;
+    // sampler
+    use_sampler_config sc{};
+    bool sampler_set = false;
+    std::vector<float> timesteps;
+    float* ts_dev = nullptr; float* temb_table = nullptr; float* silu_table = nullptr;
+    float2* noise_copy = nullptr; size_t noise_copy_bytes = 0;
+    // sub-batch pipelining (see run_score): the batch is evaluated as up to MAX_SUB sub-batches (default three) on as many streams, the second started when
+    // the first reaches its small feature maps, so that one half's latency-bound kernels hide behind the other's large ones
+    int nsub = 1, sub_B[MAX_SUB] = {};  // sub-batch sizes (nsub = 1: not split)
+    Arena sub_arena[MAX_SUB];                    // workspaces of sub-batches 1.. (inside the same allocation as `arena`)
+    Arena st_arena[MAX_SUB];                     // per sub-batch: the GroupNorm totals of all its activations, contiguous (one memset per evaluation)
+    std::vector<hipGraphExec_t> graph_exec[4];           // [0]: device RNG, [1]: injected noise, [2], [3]: the same of the per-item loop; one graph per segment of steps
+    hipGraphExec_t score_graph = nullptr;
+    // probability-flow ODE sampler: the configuration belongs to the plan (use_set_ode), the stepper to the handle
+    use_ode_config oc{};
+    bool ode_set = false;
+    // introspection
+    bool dry = false;                            // bookkeeping-only evaluation (sizing, or after an overflow): what the arenas' dry_on_overflow points at
+    std::map<std::string, Act> debug;
+    int debug_B = 0;
+    double flops = 0.0;
+
+    Plan() = default;
+    Plan(const Plan&) = delete;
+    Plan& operator=(const Plan&) = delete;
+    void drop_graphs() {
+        for (auto& v : graph_exec) { for (auto g : v) if (g) (void)hipGraphExecDestroy(g); v.clear(); }
+        if (score_graph) { (void)hipGraphExecDestroy(score_graph); score_graph = nullptr; }
+    }
+    ~Plan() {
+        drop_graphs();
+        for (void* d : {(void*)arena.base, (void*)persist, (void*)temb_table, (void*)silu_table, (void*)ts_dev, (void*)noise_copy})
+            if (d) (void)hipFree(d);
+    }
+};
+
 struct use_handle {
     use_config cfg{};
     int device = 0;
@@ -124,58 +178,28 @@ struct use_handle {
     size_t gfp_off = 0, l1w_off = 0, l1b_off = 0, l2w_off = 0, l2b_off = 0, dense_w_off = 0, dense_b_off = 0,
            outw_off = 0, outb_off = 0;
     size_t blob_bytes = 0;
+    int pcp = 4;                                 // input / pyramid channels as stored: the reference's 2, 4 or 6 zero-padded to 4 or 8
     // weights
     std::unordered_map<std::string, std::vector<float>> host_w;
     char* blob = nullptr; bool weights_ready = false;
-    // plan
-    int B = 0, T = 0;
-    Arena arena;
-    char* persist = nullptr; size_t persist_bytes = 0;
-    size_t arena_alloc = 0, persist_alloc = 0;   // sizes of the two device allocations: kept at their high-water marks across re-plans
-    size_t arena_plan_bytes = 0;                 // what the current plan uses of the first (all sub-batch arenas + GroupNorm totals)
-    float *x4 = nullptr, *silu_temb = nullptr, *tembias = nullptr, *t_dev = nullptr;
-    float2 *Y = nullptr, *X = nullptr, *Xmean = nullptr, *score = nullptr, *xin = nullptr;
-    float2 *cond_buf = nullptr, *cond2_buf = nullptr;   // cond2: the second conditioning spectrogram of condition="both" (6 input channels)
-    int pcp = 4;                                 // input / pyramid channels as stored: the reference's 2, 4 or 6 zero-padded to 4 or 8
-    float2 *Cond = nullptr;                      // score conditioning of the sampler: == Y unless use_sample_cond gave another
-    float *lang_partial = nullptr;
-    float* lang_step = nullptr;                  // [B] Langevin steps: one per item (use_sample_items), or [0] for the batch
-    unsigned long long* seeds = nullptr;         // [B] Philox seeds: one per item, or [0] for the shared stream.  Every call uploads its own
-                                                 // before its launches; the kernels read them, so graphs replay with new seeds
-    int lang_blocks = 0;
-    // sampler
-    use_sampler_config sc{};
-    bool sampler_set = false;
-    std::vector<float> timesteps;
-    float* ts_dev = nullptr; float* temb_table = nullptr; float* silu_table = nullptr;
-    float2* noise_copy = nullptr; size_t noise_copy_bytes = 0;
+    // The current plan (null: use_plan has not been called, or the last one failed) and the plan cache: a predict run over files of
+    // different lengths alternates between a handful of (B, T') shapes; the plans of the most recently used ones are parked - workspace,
+    // state buffers, time-embedding tables and the captured graphs with the addresses they hold - so that a shape that returns is
+    // neither re-planned nor re-captured.  use_set_option("plan_cache", k).
+    std::unique_ptr<Plan> plan;
+    std::vector<std::unique_ptr<Plan>> parked;   // most recently used last
+    long long n_graph_captures = 0, n_plans_built = 0, n_plan_cache_hits = 0;
+    // streams and events of the sub-batch pipeline (run_score) and of graph capture: made once, shared by all plans
     hipStream_t cap_stream = nullptr;
-    // sub-batch pipelining (see run_score): the batch is evaluated as up to MAX_SUB sub-batches (default three) on as many streams, the second started when
-    // the first reaches its small feature maps, so that one half's latency-bound kernels hide behind the other's large ones
-    int nsub = 1, sub_B[MAX_SUB] = {};  // sub-batch sizes (nsub = 1: not split)
-    Arena sub_arena[MAX_SUB];                    // workspaces of sub-batches 1.. (inside the same allocation as `arena`)
-    Arena st_arena[MAX_SUB];                     // per sub-batch: the GroupNorm totals of all its activations, contiguous (one memset per evaluation)
     hipStream_t aux_stream[MAX_SUB] = {};
     hipEvent_t ev_fork = nullptr, ev_stagger[MAX_SUB] = {},
                ev_join[MAX_SUB] = {};
-    int debug_B = 0;
-    std::vector<hipGraphExec_t> graph_exec[4];           // [0]: device RNG, [1]: injected noise, [2], [3]: the same of the per-item loop; one graph per segment of steps
-    hipGraphExec_t score_graph = nullptr;
-    // probability-flow ODE sampler (use_set_ode / use_sample_ode): the configuration belongs to the plan, the stepper's buffers and the
-    // captured step graph to the handle (re-made when the shape, the stepper or a pointer the graph holds changes)
-    use_ode_config oc{};
-    bool ode_set = false;
+    // probability-flow ODE sampler (use_sample_ode): the stepper's buffers and the captured step graph (re-made when the shape, the
+    // stepper or a pointer the graph holds changes)
     use_ode* ode_run = nullptr;
     hipGraphExec_t ode_graph = nullptr;
     std::vector<const void*> ode_graph_key;
     long long ode_steps = 0, ode_rejected = 0, ode_nfev_max = 0;
-    // plan cache: a predict run over files of different lengths alternates between a handful of (B, T') shapes; the plans of the
-    // most recently used ones are parked here - workspace, state buffers, time-embedding tables and the captured graphs with the
-    // addresses they hold - so that a shape that returns is neither re-planned nor re-captured.  use_set_option("plan_cache", k).
-    struct PlanState;
-    std::vector<PlanState*> plan_cache;          // most recently used last
-    long long opt_gen_at_plan = -1;              // g_opt_gen when the current plan was built
-    long long n_graph_captures = 0, n_plans_built = 0, n_plan_cache_hits = 0;
     // scratch for the stand-alone use_sde_* entry points (independent of weights / plan)
     char* sde_buf = nullptr; unsigned long long* sde_seeds = nullptr; float* sde_step = nullptr; float* sde_partial = nullptr;
     static constexpr int SDE_MAX_B = 1024, SDE_BLOCKS = 128;
@@ -185,10 +209,6 @@ struct use_handle {
     bool profile = false, profile_all = false;
     struct ProfRec { std::string label; int H = 0, W = 0; double flops = 0.0, bytes = 0.0; hipEvent_t e0 = nullptr, e1 = nullptr; double ms = 0.0; bool main = false; std::string desc; };
     std::vector<ProfRec> prof;
-    // introspection
-    bool dry = false;
-    std::map<std::string, Act> debug;
-    double flops = 0.0;
 };
 
 static void add_expected(use_handle* h, const std::string& name, std::vector<int64_t> shape) {
@@ -460,8 +480,8 @@ __global__ __launch_bounds__(256) void zero16_kernel(uint4* __restrict__ p, size
 }
 
 struct Fwd {
-    use_handle* h; hipStream_t s;
-    const float* tembias; int temb_bstride;      // [B or 1][dense_rows] (already offset to this sub-batch)
+    use_handle* h; Plan& pl; hipStream_t s;      // pl: the handle's current plan, or the one use_plan is sizing
+    const float* tembias; int temb_bstride;     // [B or 1][dense_rows] (already offset to this sub-batch)
     const float* t; int t_stride;                 // per-item time (stride 0: shared)
     int B = 0;                                    // items of this (sub-)batch
     Arena* arena = nullptr;                       // its activation workspace
@@ -494,7 +514,7 @@ struct Fwd {
     float* gn_coef(const Act& a, const Act* a2, const GNW& g) {
         const int C = a.C + (a2 ? a2->C : 0);
         float* coef = (float*)arena->alloc((size_t)B * C * 2 * 4);
-        if (!h->dry)
+        if (!pl.dry)
             launch_gn_finalize(a.stats, a.C, a2 ? a2->stats : nullptr, a2 ? a2->C : 0, W<float>(g.g_off), W<float>(g.b_off),
                                std::min(C / 4, 32), a.H * a.W, 1e-6f, coef, B, s, a.part, a.ntiles, a2 ? a2->part : nullptr, a2 ? a2->ntiles : 0);
         return coef;
@@ -508,7 +528,7 @@ struct Fwd {
         Act o = new_act(w.cout, a.H, a.W, out_dtype, stats);
         double fl = 2.0 * B * a.H * a.W * (double)w.cout * w.cin * w.ntaps;
         if (w2) fl += 2.0 * B * a.H * a.W * (double)w2->cout * w2->cin;
-        h->flops += fl;
+        pl.flops += fl;
         // large maps: separate finalize launch into a coefficient array (allocated in the dry run as well: the arena is sized by it)
         const bool large = (long)a.H * a.W > g_gn_inline;
         const float* coef_arr = (gn && large) ? gn_coef(a, a2, *gn) : nullptr;
@@ -524,7 +544,7 @@ struct Fwd {
         // knows that form: ch.stats_parts workgroups per item); every consumer of such a map goes through gn_coef (same threshold), which sums them
         long long* part = (stats && g_stats_part && ch.stats_parts > 0 && large)
                               ? (long long*)arena->alloc((size_t)B * ch.stats_parts * w.cout * 2 * sizeof(long long)) : nullptr;
-        if (h->dry) return o;
+        if (pl.dry) return o;
         ConvArgs p{};
         p.src0 = a.p; p.C0 = a.C; p.src1 = a2 ? a2->p : nullptr; p.C1 = a2 ? a2->C : 0; p.in_dtype = a.dtype;
         p.coef = coef_arr; p.act = act; p.w = h->blob + w.w_off; p.cout_pad = w.cout_pad;
@@ -546,7 +566,7 @@ struct Fwd {
         p.B = B; p.H = a.H; p.W = a.W; p.Cout = w.cout; p.ntaps = w.ntaps;
         // consumers that read the totals directly (inline GroupNorm below gn_inline pixels, the fused attention) must never meet a producer
         // that wrote partial totals instead: both sides test the same H * W > gn_inline - checked here, where the input is consumed
-        if (gn && !coef_arr && (a.part || (a2 && a2->part))) { arena->overflow = true; h->dry = true; return o; }   // reported by eval_status as a stale plan
+        if (gn && !coef_arr && (a.part || (a2 && a2->part))) { arena->overflow = true; pl.dry = true; return o; }   // reported by eval_status as a stale plan
         const bool main_variant = ch.k == WIDE32 || ch.k == WIDE16;           // the dominant kernel (conv_wide_kernel, large maps)
         if (!h->profile || (w.ntaps != 9 && !ch.hbm)) { launch_conv(p, s); return o; }       // (the 1x1 convolutions are not timed)
         // algorithmic HBM bytes of this launch: every operand once (input, shortcut input, residual, output, weights; the dominant kernel's Combine input)
@@ -576,7 +596,7 @@ struct Fwd {
             Act hr = new_act(x.C, H2, W2, dt, false);
             xr = new_act(x.C, H2, W2, dt, false);
             float* coef0 = gn_coef(x, skip, r.gn0);          // the resampling kernels take the GroupNorm as a coefficient array
-            if (!h->dry) {
+            if (!pl.dry) {
                 // reads the map once, writes the activated and the raw resampled copy
                 const double by = (double)B * x.H * x.W * x.C * dtype_size(dt) + 2.0 * B * H2 * W2 * x.C * dtype_size(dt);
                 if (r.up) timed_aux("fir_up", x.H, x.W, by, [&] { launch_fir_up2(x.p, dt, coef0, 1, hr.p, xr.p, B, x.H, x.W, x.C, s); });
@@ -597,9 +617,9 @@ struct Fwd {
         const int dt = h->act_dtype;
         if (g_attn_fused && x.stats && attn_fused_eligible(dt, x.H * x.W, x.C)) {       // one launch, MFMA contractions (use_attn.hip)
             Act o = new_act(x.C, x.H, x.W, dt, true);
-            h->flops += 4.0 * 2.0 * B * x.H * x.W * (double)x.C * x.C;                  // the four NIN, as the unfused path counts them
-            if (h->dry) return o;
-            if (x.part) { arena->overflow = true; h->dry = true; return o; }   // (the fused block reads x.stats: a producer with partial totals cannot feed it)
+            pl.flops += 4.0 * 2.0 * B * x.H * x.W * (double)x.C * x.C;                  // the four NIN, as the unfused path counts them
+            if (pl.dry) return o;
+            if (x.part) { arena->overflow = true; pl.dry = true; return o; }   // (the fused block reads x.stats: a producer with partial totals cannot feed it)
             AttnArgs a{};
             a.x = x.p; a.out = o.p; a.N = x.H * x.W;
             a.gn_st = x.stats; a.gn_gamma = W<float>(aw.gn.g_off); a.gn_beta = W<float>(aw.gn.b_off); a.gn_groups = std::min(x.C / 4, 32); a.gn_eps = 1e-6f;
@@ -621,7 +641,7 @@ struct Fwd {
             const size_t es = dtype_size(dt);
             char* sc = (char*)arena->alloc((size_t)B * N * N * es);           // scores -> probabilities, [B][N][N]
             char* vt = (char*)arena->alloc((size_t)B * x.C * N * es);         // [B][C][N]
-            if (!h->dry) {
+            if (!pl.dry) {
                 launch_transpose_nc(v.p, vt, dt, B, N, x.C, s);
                 for (int b = 0; b < B; ++b) {
                     ConvArgs p{};
@@ -643,7 +663,7 @@ struct Fwd {
                     launch_conv(p, s);
                 }
             }
-        } else if (!h->dry) {
+        } else if (!pl.dry) {
             launch_attention(q.p, k.p, v.p, a.p, dt, B, N, x.C, s);
         }
         return conv(a, nullptr, nullptr, 0, aw.o, -1, &x, 0.70710678118654752440f, nullptr, nullptr, dt, true);
@@ -659,31 +679,31 @@ struct Fwd {
         // all GroupNorm totals of this evaluation; a kernel, not hipMemsetAsync: a captured memset node of this (small) size does not
         // clear the region again on the second replay of a graph that holds four or more evaluations (ROCm 7.2; seen as NaN from the
         // second sampler call on for batches of 1-3 items, i.e. without the sub-batch split)
-        if (!H->dry && st_arena->base) {
+        if (!pl.dry && st_arena->base) {
             const size_t n16 = st_arena->cap / 16;
             hipLaunchKernelGGL(zero16_kernel, dim3((unsigned)std::min<size_t>((n16 + 255) / 256, 1024)), dim3(256), 0, s, (uint4*)st_arena->base, n16);
         }
-        if (primary) { H->flops = 0.0; H->debug.clear(); H->debug_B = B; }
+        if (primary) { pl.flops = 0.0; pl.debug.clear(); pl.debug_B = B; }
         const int pcp = H->pcp;
-        Act xin; xin.p = (void*)x4; xin.C = pcp; xin.H = c.n_freq; xin.W = H->T; xin.dtype = DT_F32;
+        Act xin; xin.p = (void*)x4; xin.C = pcp; xin.H = c.n_freq; xin.W = pl.T; xin.dtype = DT_F32;
         std::vector<Act> hs;
         hs.push_back(conv(xin, nullptr, nullptr, 0, H->conv_in, -1, nullptr, 1.f, nullptr, nullptr, dt, true));
-        if (primary) H->debug["h_in"] = hs.back();
+        if (primary) pl.debug["h_in"] = hs.back();
         Act ipyr = xin;
         size_t ri = 0, ci = 0;
         for (int lvl = 0; lvl < L; ++lvl) {
             for (int k = 0; k < nrb; ++k) hs.push_back(resblock(hs.back(), nullptr, H->res[ri++]));
-            if (lvl == std::min(stagger_level, L - 1) && ev_stagger && !H->dry) (void)hipEventRecord(ev_stagger, s);   // small maps follow
+            if (lvl == std::min(stagger_level, L - 1) && ev_stagger && !pl.dry) (void)hipEventRecord(ev_stagger, s);   // small maps follow
             if (lvl != L - 1) {
                 Act nip = new_act(pcp, ipyr.H / 2, ipyr.W / 2, DT_F32, false);        // pyramid_downsample
-                if (!H->dry) launch_fir_down2(ipyr.p, DT_F32, nullptr, 0, nullptr, nip.p, B, ipyr.H, ipyr.W, pcp, s);
+                if (!pl.dry) launch_fir_down2(ipyr.p, DT_F32, nullptr, 0, nullptr, nip.p, B, ipyr.H, ipyr.W, pcp, s);
                 ipyr = nip;
                 if (pcp == 4) {                                // Combine fused into the block's last convolution
                     hs.push_back(resblock(hs.back(), nullptr, H->res[ri++], (const float*)ipyr.p, &H->combines[ci++]));
                 } else {                                       // 6-channel input: Combine as its own pass over the block's output
                     Act o = resblock(hs.back(), nullptr, H->res[ri++]);
                     const CombineW& cb = H->combines[ci++];
-                    if (!H->dry) {
+                    if (!pl.dry) {
                         hipLaunchKernelGGL(zero16_kernel, dim3((unsigned)(((size_t)B * o.C + 255) / 256)), dim3(256), 0, s, (uint4*)o.stats,
                                            (size_t)B * o.C);                                             // totals of the combined map (16 bytes per channel)
                         launch_combine_add(o.p, o.dtype, (const float*)ipyr.p, W<float>(cb.w_off), W<float>(cb.b_off), o.stats, B,
@@ -694,11 +714,11 @@ struct Fwd {
                 }
             }
         }
-        if (primary) H->debug["down_out"] = hs.back();
+        if (primary) pl.debug["down_out"] = hs.back();
         Act hc = resblock(hs.back(), nullptr, H->res[ri++]);
-        if (primary) H->debug["pre_attn"] = hc;
+        if (primary) pl.debug["pre_attn"] = hc;
         hc = attention(hc, H->attn);
-        if (primary) H->debug["post_attn"] = hc;
+        if (primary) pl.debug["post_attn"] = hc;
         hc = resblock(hc, nullptr, H->res[ri++]);
         Act pyr; bool have_pyr = false; size_t pi = 0;
         for (int lvl = L - 1; lvl >= 0; --lvl) {
@@ -712,13 +732,13 @@ struct Fwd {
                 have_pyr = true;
             } else {
                 Act up = new_act(pcp, pyr.H * 2, pyr.W * 2, DT_F32, false);             // pyramid_upsample
-                if (!H->dry) launch_fir_up2(pyr.p, DT_F32, nullptr, 0, nullptr, up.p, B, pyr.H, pyr.W, pcp, s);
+                if (!pl.dry) launch_fir_up2(pyr.p, DT_F32, nullptr, 0, nullptr, up.p, B, pyr.H, pyr.W, pcp, s);
                 pyr = conv(hc, nullptr, &pw.gn, 1, pw.conv, -1, &up, 1.f, nullptr, nullptr, DT_F32, false);
             }
             if (lvl != 0) hc = resblock(hc, nullptr, H->res[ri++]);
         }
-        if (primary) H->debug["h_last"] = hc;
-        if (primary) H->debug["pyramid"] = pyr;
+        if (primary) pl.debug["h_last"] = hc;
+        if (primary) pl.debug["pyramid"] = pyr;
         return pyr;
     }
 };
@@ -736,16 +756,17 @@ static void run_temb(use_handle* h, const float* t, int n, float* silu_buf, floa
 // score = -net(cat[x, y], t): x, y device complex64
 static void run_score(use_handle* h, const float2* x, const float2* y, const float* tembias, int temb_bstride,
                       const float* t, int t_stride, float2* out, hipStream_t s, float sign = -1.f, const float2* y2 = nullptr) {
+    Plan& pl = *h->plan;
     if (h->cfg.no_sigma_scale) t = nullptr;                   // score_out: no division by t
-    const long n_per_b = (long)h->cfg.n_freq * h->T;
+    const long n_per_b = (long)h->cfg.n_freq * pl.T;
     const int pcp = h->pcp;
-    launch_pack_input(x, y, y2, h->x4, (long)h->B * n_per_b, s);
+    launch_pack_input(x, y, y2, pl.x4, (long)pl.B * n_per_b, s);
     const float* outw = (const float*)(h->blob + h->outw_off); const float* outb = (const float*)(h->blob + h->outb_off);
-    if (h->nsub == 1) {
-        Fwd f0{h, s, tembias, temb_bstride, t, t_stride};
-        f0.B = h->B; f0.arena = &h->arena; f0.st_arena = &h->st_arena[0];
-        Act pyr = f0.run(h->x4);
-        if (!h->dry) launch_score_out((const float*)pyr.p, pcp, t, t_stride, outw, outb, out, h->B, n_per_b, sign, s);
+    if (pl.nsub == 1) {
+        Fwd f0{h, pl, s, tembias, temb_bstride, t, t_stride};
+        f0.B = pl.B; f0.arena = &pl.arena; f0.st_arena = &pl.st_arena[0];
+        Act pyr = f0.run(pl.x4);
+        if (!pl.dry) launch_score_out((const float*)pyr.p, pcp, t, t_stride, outw, outb, out, pl.B, n_per_b, sign, s);
         return;
     }
     // Sub-batches on separate streams.  The items are independent inside the network (GroupNorm is per item), so this is
@@ -755,25 +776,25 @@ static void run_score(use_handle* h, const float2* x, const float2* y, const flo
     const bool overlap = !h->profile;                         // per-launch timing wants the kernels one at a time
     if (overlap) (void)hipEventRecord(h->ev_fork, s);
     int b0 = 0;
-    for (int i = 0; i < h->nsub; ++i) {
+    for (int i = 0; i < pl.nsub; ++i) {
         hipStream_t si = (i == 0 || !overlap) ? s : h->aux_stream[i];
         if (overlap && i) {
             (void)hipStreamWaitEvent(si, h->ev_fork, 0);
             (void)hipStreamWaitEvent(si, h->ev_stagger[i - 1], 0);
         }
-        Fwd f{h, si, tembias ? tembias + (size_t)b0 * temb_bstride : nullptr, temb_bstride,
+        Fwd f{h, pl, si, tembias ? tembias + (size_t)b0 * temb_bstride : nullptr, temb_bstride,
               t ? t + (size_t)b0 * t_stride : nullptr, t_stride};
-        f.B = h->sub_B[i]; f.arena = i ? &h->sub_arena[i] : &h->arena; f.st_arena = &h->st_arena[i]; f.primary = i == 0;
-        if (overlap && i + 1 < h->nsub) { f.ev_stagger = h->ev_stagger[i]; f.stagger_level = g_stagger_level; }
-        Act pyr = f.run(h->x4 + (size_t)b0 * n_per_b * pcp);
-        if (!h->dry)
+        f.B = pl.sub_B[i]; f.arena = i ? &pl.sub_arena[i] : &pl.arena; f.st_arena = &pl.st_arena[i]; f.primary = i == 0;
+        if (overlap && i + 1 < pl.nsub) { f.ev_stagger = h->ev_stagger[i]; f.stagger_level = g_stagger_level; }
+        Act pyr = f.run(pl.x4 + (size_t)b0 * n_per_b * pcp);
+        if (!pl.dry)
         launch_score_out((const float*)pyr.p, pcp, t ? t + (size_t)b0 * t_stride : nullptr, t_stride, outw, outb,
-                         out + (size_t)b0 * n_per_b, h->sub_B[i], n_per_b, sign, si);
+                         out + (size_t)b0 * n_per_b, pl.sub_B[i], n_per_b, sign, si);
         if (overlap && i) (void)hipEventRecord(h->ev_join[i], si);
-        b0 += h->sub_B[i];
+        b0 += pl.sub_B[i];
     }
     if (overlap)
-        for (int i = 1; i < h->nsub; ++i) (void)hipStreamWaitEvent(s, h->ev_join[i], 0);
+        for (int i = 1; i < pl.nsub; ++i) (void)hipStreamWaitEvent(s, h->ev_join[i], 0);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -817,99 +838,62 @@ __global__ void set_rng_kernel(unsigned long long* seeds, unsigned long long see
 __global__ void fill_f32_kernel(float* p, float v, int n) { for (int i = threadIdx.x; i < n; i += blockDim.x) p[i] = v; }
 
 // steps [i0, i1) of the loop (i0 == 0: preceded by the prior sampling); the whole loop is run_sampler(h, noise, s, 0, N).
-// per_item (use_sample_items): the SDE updates address the batch as B items - item b's noise from h->seeds[b], its own
+// per_item (use_sample_items): the SDE updates address the batch as B items - item b's noise from pl.seeds[b], its own
 // Langevin step - instead of one item of all n elements; the score evaluations and the stream schedule are the same.
 static void run_sampler(use_handle* h, const float2* noise, hipStream_t s, int i0, int i1, bool per_item = false) {
-    const use_sampler_config& sc = h->sc;
-    const long n = (long)h->B * h->cfg.n_freq * h->T, n_per_b = (long)h->cfg.n_freq * h->T;
-    const int items = per_item ? h->B : 1;
+    Plan& pl = *h->plan;
+    const use_sampler_config& sc = pl.sc;
+    const long n = (long)pl.B * h->cfg.n_freq * pl.T, n_per_b = (long)h->cfg.n_freq * pl.T;
+    const int items = per_item ? pl.B : 1;
     const long n_per_item = n / items;
     const int ncorr = sc.corrector == USE_CORR_NONE ? 0 : sc.corrector_steps;
     // the network's kernel choice must not see the (sub-)batch size either: an item of a sub-batch of 3 has to get the bits it gets alone
     struct PerImage { bool on; PerImage(bool o) : on(o) { if (on) conv_sk_set_per_image(true); } ~PerImage() { if (on) conv_sk_set_per_image(false); } } per_image(per_item);
     auto nz = [&](unsigned d) { return noise ? noise + (size_t)d * n : nullptr; };
     unsigned d = 1 + (unsigned)i0 * (unsigned)(ncorr + (sc.predictor == USE_PRED_NONE ? 0 : 1));   // noise draws consumed so far
-    if (i0 == 0) launch_prior(h->Y, nz(0), SdeRng{h->seeds, 0}, ouve_std(h->cfg, 1.0f), h->X, items, n_per_item, s);
+    if (i0 == 0) launch_prior(pl.Y, nz(0), SdeRng{pl.seeds, 0}, ouve_std(h->cfg, 1.0f), pl.X, items, n_per_item, s);
     for (int i = i0; i < i1; ++i) {
-        const float t = h->timesteps[i];
-        const float* temb = h->temb_table + (size_t)i * h->dense_rows;
+        const float t = pl.timesteps[i];
+        const float* temb = pl.temb_table + (size_t)i * h->dense_rows;
         for (int k = 0; k < ncorr; ++k) {
-            run_score(h, h->X, h->Cond, temb, 0, h->ts_dev + i, 0, h->score, s, -1.f, h->pcp == 8 ? h->cond2_buf : nullptr);
-            const SdeRng rng{h->seeds, d};
+            run_score(h, pl.X, pl.Cond, temb, 0, pl.ts_dev + i, 0, pl.score, s, -1.f, h->pcp == 8 ? pl.cond2_buf : nullptr);
+            const SdeRng rng{pl.seeds, d};
             if (sc.corrector == USE_CORR_LANGEVIN) {
-                launch_langevin_norms(h->score, nz(d), rng, per_item, h->lang_partial, h->B, n_per_b, h->lang_blocks, s);
-                launch_langevin_step(h->lang_partial, h->B, per_item, h->lang_blocks, sc.snr, h->lang_step, s);
-                launch_corrector(h->X, h->score, nz(d), rng, h->lang_step, 0.f, h->X, nullptr, items, n_per_item, s);
+                launch_langevin_norms(pl.score, nz(d), rng, per_item, pl.lang_partial, pl.B, n_per_b, pl.lang_blocks, s);
+                launch_langevin_step(pl.lang_partial, pl.B, per_item, pl.lang_blocks, sc.snr, pl.lang_step, s);
+                launch_corrector(pl.X, pl.score, nz(d), rng, pl.lang_step, 0.f, pl.X, nullptr, items, n_per_item, s);
             } else {                                               // ALD: correctors.py:79-98
                 const float sd = sc.snr * ouve_std(h->cfg, t);
-                launch_corrector(h->X, h->score, nz(d), rng, nullptr, sd * sd * 2.f, h->X, nullptr, items, n_per_item, s);
+                launch_corrector(pl.X, pl.score, nz(d), rng, nullptr, sd * sd * 2.f, pl.X, nullptr, items, n_per_item, s);
             }
             d++;
         }
         if (sc.predictor == USE_PRED_NONE) {
-            if (i == sc.N - 1) (void)hipMemcpyAsync(h->Xmean, h->X, (size_t)n * 8, hipMemcpyDeviceToDevice, s);
+            if (i == sc.N - 1) (void)hipMemcpyAsync(pl.Xmean, pl.X, (size_t)n * 8, hipMemcpyDeviceToDevice, s);
         } else {
-            run_score(h, h->X, h->Cond, temb, 0, h->ts_dev + i, 0, h->score, s, -1.f, h->pcp == 8 ? h->cond2_buf : nullptr);
+            run_score(h, pl.X, pl.Cond, temb, 0, pl.ts_dev + i, 0, pl.score, s, -1.f, h->pcp == 8 ? pl.cond2_buf : nullptr);
             float cd, cs, cn; predictor_coeffs(h->cfg, sc.predictor, t, sc.N, cd, cs, cn);
-            launch_predictor(h->X, h->Y, h->score, nz(d), SdeRng{h->seeds, d}, cd, cs, cn, h->X,
-                             i == sc.N - 1 ? h->Xmean : nullptr, items, n_per_item, s);
+            launch_predictor(pl.X, pl.Y, pl.score, nz(d), SdeRng{pl.seeds, d}, cd, cs, cn, pl.X,
+                             i == sc.N - 1 ? pl.Xmean : nullptr, items, n_per_item, s);
             d++;
         }
     }
 }
 
-static void drop_graphs(use_handle* h) {
-    for (auto& v : h->graph_exec) { for (auto g : v) if (g) (void)hipGraphExecDestroy(g); v.clear(); }
-    if (h->score_graph) { (void)hipGraphExecDestroy(h->score_graph); h->score_graph = nullptr; }
+static void drop_graphs(use_handle* h) {                  // every graph that replays against the current plan
+    if (h->plan) h->plan->drop_graphs();
     if (h->ode_graph) { (void)hipGraphExecDestroy(h->ode_graph); h->ode_graph = nullptr; }
 }
 
-// everything of the handle that belongs to ONE plan (the current plan lives in the handle's own fields)
-#define USE_PLAN_FIELDS(X)                                                                                            \
-    X(B) X(T) X(nsub) X(arena) X(arena_alloc) X(arena_plan_bytes) X(persist) X(persist_bytes) X(persist_alloc) X(x4) X(silu_temb) X(tembias) X(t_dev) \
-    X(Y) X(X) X(Xmean) X(score) X(xin) X(cond_buf) X(cond2_buf) X(Cond) X(lang_partial) X(lang_step) X(seeds) X(lang_blocks)   \
-    X(sc) X(sampler_set) X(timesteps) X(ts_dev) X(temb_table) X(silu_table) X(noise_copy) X(noise_copy_bytes) X(score_graph)      \
-    X(debug) X(debug_B) X(opt_gen_at_plan) X(oc) X(ode_set)
-struct use_handle::PlanState {
-#define X(f) decltype(use_handle::f) f;
-    USE_PLAN_FIELDS(X)
-#undef X
-    int sub_B[MAX_SUB]; Arena sub_arena[MAX_SUB], st_arena[MAX_SUB];
-    std::vector<hipGraphExec_t> graph_exec[4];
-};
 static long long g_opt_gen = 0;                  // bumped by every use_set_option: plans built under other options are not reused
 static int g_plan_cache = 4;                     // plans kept besides the current one
-static void plan_stash(use_handle* h, use_handle::PlanState& p) {      // handle -> p; the handle's plan fields are left empty
-#define X(f) p.f = std::move(h->f);
-    USE_PLAN_FIELDS(X)
-#undef X
-    for (int i = 0; i < MAX_SUB; ++i) { p.sub_B[i] = h->sub_B[i]; p.sub_arena[i] = h->sub_arena[i]; p.st_arena[i] = h->st_arena[i]; }
-    for (int i = 0; i < 4; ++i) { p.graph_exec[i] = std::move(h->graph_exec[i]); h->graph_exec[i].clear(); }
-    h->B = h->T = 0; h->arena = Arena{}; h->arena_alloc = 0; h->persist = nullptr; h->persist_bytes = h->persist_alloc = 0;
-    h->ts_dev = h->temb_table = h->silu_table = nullptr; h->noise_copy = nullptr; h->noise_copy_bytes = 0; h->score_graph = nullptr;
-    h->sampler_set = false; h->timesteps.clear(); h->debug.clear(); h->ode_set = false;
-}
-static void plan_restore(use_handle* h, use_handle::PlanState& p) {    // p -> handle
-#define X(f) h->f = std::move(p.f);
-    USE_PLAN_FIELDS(X)
-#undef X
-    for (int i = 0; i < MAX_SUB; ++i) { h->sub_B[i] = p.sub_B[i]; h->sub_arena[i] = p.sub_arena[i]; h->st_arena[i] = p.st_arena[i]; }
-    for (int i = 0; i < 4; ++i) h->graph_exec[i] = std::move(p.graph_exec[i]);
-}
-static void plan_free(use_handle::PlanState* p) {
-    for (auto& v : p->graph_exec) for (auto g : v) if (g) (void)hipGraphExecDestroy(g);
-    if (p->score_graph) (void)hipGraphExecDestroy(p->score_graph);
-    if (p->arena.base) (void)hipFree(p->arena.base);
-    if (p->persist) (void)hipFree(p->persist);
-    if (p->temb_table) (void)hipFree(p->temb_table);
-    if (p->silu_table) (void)hipFree(p->silu_table);
-    if (p->ts_dev) (void)hipFree(p->ts_dev);
-    if (p->noise_copy) (void)hipFree(p->noise_copy);
-    delete p;
-}
-static void plan_cache_clear(use_handle* h) {                          // weights changed / handle destroyed: every parked plan is stale
-    for (auto* p : h->plan_cache) plan_free(p);
-    h->plan_cache.clear();
+
+// new contents in the weight blob: what the current plan derived from the old ones goes (time-embedding tables, graphs), and every parked plan
+static void weights_changed(use_handle* h) {
+    h->weights_ready = true;
+    if (h->plan) h->plan->sampler_set = false;
+    drop_graphs(h);
+    h->parked.clear();
 }
 
 static int ensure_sde_scratch(use_handle* h) {
@@ -942,11 +926,11 @@ int use_get_stat(use_handle* h, const char* name, long long* value) {
     if (!strcmp(name, "graph_captures")) { *value = h->n_graph_captures; return USE_OK; }      // sampling-loop segments captured so far
     if (!strcmp(name, "plans_built")) { *value = h->n_plans_built; return USE_OK; }
     if (!strcmp(name, "plan_cache_hits")) { *value = h->n_plan_cache_hits; return USE_OK; }
-    if (!strcmp(name, "plans_parked")) { *value = (long long)h->plan_cache.size(); return USE_OK; }
+    if (!strcmp(name, "plans_parked")) { *value = (long long)h->parked.size(); return USE_OK; }
     if (!strcmp(name, "ode_steps")) { *value = h->ode_steps; return USE_OK; }                    // of the last use_sample_ode
     if (!strcmp(name, "ode_rejected")) { *value = h->ode_rejected; return USE_OK; }
     if (!strcmp(name, "ode_nfev_max")) { *value = h->ode_nfev_max; return USE_OK; }
-    if (!strcmp(name, "plan_stale")) { *value = h->B && h->opt_gen_at_plan != g_opt_gen ? 1 : 0; return USE_OK; }   // an option changed since use_plan
+    if (!strcmp(name, "plan_stale")) { *value = h->plan && h->plan->opt_gen != g_opt_gen ? 1 : 0; return USE_OK; }   // an option changed since use_plan
     return fail(USE_E_INVALID, "unknown statistic '%s'", name);
 }
 
@@ -997,7 +981,7 @@ int use_destroy(use_handle* h) {
     if (!h) return USE_OK;
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
-    drop_graphs(h); plan_cache_clear(h);
+    drop_graphs(h);                                           // (the plans themselves go with the handle: delete h)
     if (h->ode_run) (void)use_ode_destroy(h->ode_run);
     if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
     for (int i = 0; i < MAX_SUB; ++i) {
@@ -1006,12 +990,6 @@ int use_destroy(use_handle* h) {
     }
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->blob) (void)hipFree(h->blob);
-    if (h->arena.base) (void)hipFree(h->arena.base);
-    if (h->persist) (void)hipFree(h->persist);
-    if (h->temb_table) (void)hipFree(h->temb_table);
-    if (h->silu_table) (void)hipFree(h->silu_table);
-    if (h->ts_dev) (void)hipFree(h->ts_dev);
-    if (h->noise_copy) (void)hipFree(h->noise_copy);
     if (h->sde_buf) (void)hipFree(h->sde_buf);
     delete h;
     return USE_OK;
@@ -1047,9 +1025,7 @@ int use_alloc_weight_blob(use_handle* h) {
     if (!h) return fail(USE_E_INVALID, "null handle");
     HIPCHK(hipSetDevice(h->device));
     if (!h->blob) HIPCHK(hipMalloc((void**)&h->blob, h->blob_bytes));
-    h->weights_ready = true;   // contents to be filled by the caller's broadcast
-    h->sampler_set = false;    // the time-embedding table was built from the previous contents
-    drop_graphs(h); plan_cache_clear(h);
+    weights_changed(h);        // contents to be filled by the caller's broadcast
     return USE_OK;
 }
 
@@ -1062,9 +1038,7 @@ int use_commit_weights(use_handle* h) {
     if (!h->blob) HIPCHK(hipMalloc((void**)&h->blob, h->blob_bytes));
     HIPCHK(hipMemcpy(h->blob, host.data(), h->blob_bytes, hipMemcpyHostToDevice));
     h->host_w.clear();
-    h->weights_ready = true;
-    h->sampler_set = false;    // the temb table depends on the weights
-    drop_graphs(h); plan_cache_clear(h);
+    weights_changed(h);
     return USE_OK;
 }
 
@@ -1144,9 +1118,7 @@ int use_load_weight_blob(use_handle* h, const char* path) {
     if (!h->blob) HIPCHK(hipMalloc((void**)&h->blob, h->blob_bytes));
     HIPCHK(hipMemcpy(h->blob, host.data(), h->blob_bytes, hipMemcpyHostToDevice));
     h->host_w.clear();
-    h->weights_ready = true;
-    h->sampler_set = false;
-    drop_graphs(h); plan_cache_clear(h);                     // parked plans hold time-embedding tables + graphs of the OLD weights
+    weights_changed(h);
     return USE_OK;
 }
 
@@ -1162,138 +1134,125 @@ int use_plan(use_handle* h, int B, int Tpad) {
     if (B < 1 || Tpad < 64 || Tpad % 64 != 0) return fail(USE_E_INVALID, "plan needs B >= 1 and T' a positive multiple of 64 (got B=%d T'=%d)", B, Tpad);
     if ((Tpad >> (h->cfg.n_levels - 1)) < 1) return fail(USE_E_INVALID, "T' too small for %d levels", h->cfg.n_levels);
     HIPCHK(hipSetDevice(h->device));
-    if (h->arena.base && h->B == B && h->T == Tpad && h->opt_gen_at_plan == g_opt_gen) return USE_OK;     // the current plan
+    auto wanted = [&](const Plan& p) { return p.B == B && p.T == Tpad && p.opt_gen == g_opt_gen; };
+    if (h->plan && wanted(*h->plan)) return USE_OK;           // the current plan
     HIPCHK(hipDeviceSynchronize());
     if (h->ode_graph) { (void)hipGraphExecDestroy(h->ode_graph); h->ode_graph = nullptr; }   // it holds the current plan's workspace
-    use_handle::PlanState* hit = nullptr;                     // the requested plan, if it is parked: taken out BEFORE the current one
-    for (size_t i = 0; i < h->plan_cache.size(); ++i) {       // goes in (else a cycle over capacity + 1 shapes would evict what it needs)
-        use_handle::PlanState* p = h->plan_cache[i];
-        if (p->B == B && p->T == Tpad && p->opt_gen_at_plan == g_opt_gen) { hit = p; h->plan_cache.erase(h->plan_cache.begin() + (long)i); break; }
-    }
-    if (h->arena.base) {                                      // park the current plan (with its graphs)
-        auto* p = new use_handle::PlanState();
-        plan_stash(h, *p);
-        if (g_plan_cache > 0 && p->opt_gen_at_plan == g_opt_gen) h->plan_cache.push_back(p); else plan_free(p);
-        while ((int)h->plan_cache.size() > g_plan_cache) { plan_free(h->plan_cache.front()); h->plan_cache.erase(h->plan_cache.begin()); }
-    }
+    // the requested plan, if it is parked: taken out BEFORE the current one goes in (else a cycle over capacity + 1 shapes would evict what it needs)
+    std::unique_ptr<Plan> hit;
+    for (auto it = h->parked.begin(); it != h->parked.end(); ++it)
+        if (wanted(**it)) { hit = std::move(*it); h->parked.erase(it); break; }
+    // park the current plan (with its graphs), unless it is stale or nothing is kept; the least recently used ones go beyond the capacity
+    if (h->plan && g_plan_cache > 0 && h->plan->opt_gen == g_opt_gen) h->parked.push_back(std::move(h->plan));
+    h->plan.reset();
+    while ((int)h->parked.size() > g_plan_cache) h->parked.erase(h->parked.begin());
     if (hit) {
-        plan_restore(h, *hit);
-        delete hit;
+        h->plan = std::move(hit);
         ++h->n_plan_cache_hits;
         return USE_OK;
     }
+    // A new plan, built in a local owner and installed last: whatever fails on the way, the handle is left without a current plan
     ++h->n_plans_built;
-    h->opt_gen_at_plan = g_opt_gen;
-    h->B = B; h->T = Tpad; h->sampler_set = false; h->ode_set = false;
+    auto built = std::make_unique<Plan>();
+    Plan& pl = *built;
+    pl.opt_gen = g_opt_gen;
+    pl.B = B; pl.T = Tpad;
     // sub-batch pipelining (run_score): `subbatch` sub-batches of at least 2 items each
     // How many sub-batches: a question of grid quantisation on the 256 CUs (same-box sweeps, profiles/r5_e2e_ab_subbatch_sweep.txt).  The 3x3
     // convolutions of the 256 x 320 / 128 x 160 maps launch 160 / 80 workgroups per item: sub-batches of 4 items leave 2.5 / 1.25 rounds (83 % /
     // 62 % of the last round's CUs busy), of 3 items 1.9 / 0.94 - batch 8 runs 1.6 % faster as 3 + 3 + 2 than as 4 + 4 (bf16 and fp16), five or
     // more streams 12-17 % slower; batch 16 is fastest as 8 + 8 (5 / 2.5 rounds; 6 + 5 + 5: +0.7 %).
     const int want = g_subbatch >= 0 ? g_subbatch : (B >= 6 && B <= 11) ? 3 : 2;
-    h->nsub = std::max(1, std::min(std::min(want, MAX_SUB), B / std::max(1, g_subbatch_min_items)));
-    for (int i = 0; i < MAX_SUB; ++i) h->sub_B[i] = i < h->nsub ? B / h->nsub + (i < B % h->nsub ? 1 : 0) : 0;
-    // dry runs to size the activation arenas (one per sub-batch, carved from one allocation).  The allocation itself is kept
-    // when it is large enough: a predict run over files of different lengths re-plans for almost every batch
-    char* old_base = h->arena.base;
-    h->arena = Arena{};
-    h->dry = true;
+    pl.nsub = std::max(1, std::min(std::min(want, MAX_SUB), B / std::max(1, g_subbatch_min_items)));
+    for (int i = 0; i < MAX_SUB; ++i) pl.sub_B[i] = i < pl.nsub ? B / pl.nsub + (i < B % pl.nsub ? 1 : 0) : 0;
+    // dry runs to size the activation arenas (one per sub-batch, carved from one allocation)
+    pl.dry = true;
     size_t caps[MAX_SUB] = {}, stcaps[MAX_SUB] = {}, total = 0;
-    for (int i = 0; i < h->nsub; ++i) {
-        Arena& ar = i ? h->sub_arena[i] : h->arena;
-        ar = Arena{}; h->st_arena[i] = Arena{};
-        Fwd f{h, nullptr, nullptr, 0, nullptr, 0};
-        f.B = h->sub_B[i]; f.arena = &ar; f.st_arena = &h->st_arena[i]; f.primary = i == 0;
+    for (int i = 0; i < pl.nsub; ++i) {
+        Arena& ar = i ? pl.sub_arena[i] : pl.arena;
+        Fwd f{h, pl, nullptr, nullptr, 0, nullptr, 0};
+        f.B = pl.sub_B[i]; f.arena = &ar; f.st_arena = &pl.st_arena[i]; f.primary = i == 0;
         f.run(nullptr);
         caps[i] = (ar.peak + 4096 + 255) & ~(size_t)255; total += caps[i];
-        stcaps[i] = (h->st_arena[i].peak + 255) & ~(size_t)255; total += stcaps[i];
+        stcaps[i] = (pl.st_arena[i].peak + 255) & ~(size_t)255; total += stcaps[i];
     }
-    h->dry = false;
-    char* base = old_base;
-    if (!base || total > h->arena_alloc) {
-        if (base) { HIPCHK(hipFree(base)); base = nullptr; h->arena_alloc = 0; }
-        if (hipMalloc((void**)&base, total) != hipSuccess) {
-            (void)hipGetLastError();
-            plan_cache_clear(h);                              // parked plans hold their workspaces: give them up and try once more
-            if (hipMalloc((void**)&base, total) != hipSuccess)
-                return fail(USE_E_NOMEM, "cannot allocate %.1f MB of activation workspace", total / 1e6);
-        }
-        h->arena_alloc = total;
-    }
-    h->arena.base = base; h->arena.cap = caps[0];             // owns the allocation (arena_alloc bytes); its own slice is caps[0]
-    h->arena_plan_bytes = total;
+    pl.dry = false;
+    auto device_alloc = [&](char** d, size_t bytes) {         // parked plans hold their workspaces: give them up and try once more
+        if (hipMalloc((void**)d, bytes) == hipSuccess) return true;
+        (void)hipGetLastError();
+        h->parked.clear();
+        return hipMalloc((void**)d, bytes) == hipSuccess;
+    };
+    char* base = nullptr;
+    if (!device_alloc(&base, total)) return fail(USE_E_NOMEM, "cannot allocate %.1f MB of activation workspace", total / 1e6);
+    pl.arena.base = base; pl.arena.cap = caps[0];             // owns the allocation (arena_plan_bytes); its own slice is caps[0]
+    pl.arena_plan_bytes = total;
     {
         size_t off = caps[0];
-        for (int i = 1; i < h->nsub; ++i) { h->sub_arena[i].base = base + off; h->sub_arena[i].cap = caps[i]; off += caps[i]; }
-        for (int i = 0; i < h->nsub; ++i) { h->st_arena[i].base = base + off; h->st_arena[i].cap = stcaps[i]; off += stcaps[i]; }
-        h->arena.dry_on_overflow = &h->dry;
-        for (int i = 0; i < h->nsub; ++i) { h->sub_arena[i].dry_on_overflow = &h->dry; h->st_arena[i].dry_on_overflow = &h->dry; }
+        for (int i = 1; i < pl.nsub; ++i) { pl.sub_arena[i].base = base + off; pl.sub_arena[i].cap = caps[i]; off += caps[i]; }
+        for (int i = 0; i < pl.nsub; ++i) { pl.st_arena[i].base = base + off; pl.st_arena[i].cap = stcaps[i]; off += stcaps[i]; }
+        pl.arena.dry_on_overflow = &pl.dry;
+        for (int i = 0; i < pl.nsub; ++i) { pl.sub_arena[i].dry_on_overflow = &pl.dry; pl.st_arena[i].dry_on_overflow = &pl.dry; }
     }
-    if (h->nsub > 1 && !h->ev_fork) HIPCHK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-    for (int i = 0; i < h->nsub; ++i) {
+    if (pl.nsub > 1 && !h->ev_fork) HIPCHK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
+    for (int i = 0; i < pl.nsub; ++i) {
         if (i && !h->aux_stream[i]) HIPCHK(hipStreamCreateWithFlags(&h->aux_stream[i], hipStreamNonBlocking));
-        if (h->nsub > 1 && !h->ev_stagger[i]) {
+        if (pl.nsub > 1 && !h->ev_stagger[i]) {
             HIPCHK(hipEventCreateWithFlags(&h->ev_stagger[i], hipEventDisableTiming));
             HIPCHK(hipEventCreateWithFlags(&h->ev_join[i], hipEventDisableTiming));
         }
     }
     // persistent buffers
     const size_t n = (size_t)B * h->cfg.n_freq * Tpad;
-    h->lang_blocks = (int)std::min<size_t>(256, ((size_t)h->cfg.n_freq * Tpad + 255) / 256);
+    pl.lang_blocks = (int)std::min<size_t>(256, ((size_t)h->cfg.n_freq * Tpad + 255) / 256);
     size_t off = 0;
     auto take = [&](size_t bytes) { off = (off + 255) & ~(size_t)255; size_t o = off; off += bytes; return o; };
     const size_t o_x4 = take(n * 4 * h->pcp), o_c2 = take(h->pcp == 8 ? n * 8 : 0), o_Y = take(n * 8), o_X = take(n * 8), o_Xm = take(n * 8), o_sc = take(n * 8),
                  o_xin = take(n * 8), o_cond = take(n * 8), o_st = take((size_t)B * 4 * h->cfg.nf * 4), o_tb = take((size_t)B * h->dense_rows * 4),
-                 o_t = take((size_t)B * 4), o_lp = take((size_t)B * h->lang_blocks * 2 * 4), o_ls = take((size_t)B * 4),
+                 o_t = take((size_t)B * 4), o_lp = take((size_t)B * pl.lang_blocks * 2 * 4), o_ls = take((size_t)B * 4),
                  o_sd = take((size_t)std::max(B, 1) * 8);
-    h->persist_bytes = off;
-    if (!h->persist || off > h->persist_alloc) {
-        if (h->persist) { HIPCHK(hipFree(h->persist)); h->persist = nullptr; h->persist_alloc = 0; }
-        if (hipMalloc((void**)&h->persist, off) != hipSuccess) {
-            (void)hipGetLastError();
-            plan_cache_clear(h);
-            if (hipMalloc((void**)&h->persist, off) != hipSuccess) return fail(USE_E_NOMEM, "cannot allocate %.1f MB of state", off / 1e6);
-        }
-        h->persist_alloc = off;
-    }
-    h->x4 = (float*)(h->persist + o_x4); h->Y = (float2*)(h->persist + o_Y); h->X = (float2*)(h->persist + o_X);
-    h->Xmean = (float2*)(h->persist + o_Xm); h->score = (float2*)(h->persist + o_sc); h->xin = (float2*)(h->persist + o_xin);
-    h->cond_buf = (float2*)(h->persist + o_cond); h->Cond = h->Y;
-    h->cond2_buf = h->pcp == 8 ? (float2*)(h->persist + o_c2) : nullptr;
-    h->silu_temb = (float*)(h->persist + o_st); h->tembias = (float*)(h->persist + o_tb); h->t_dev = (float*)(h->persist + o_t);
-    h->lang_partial = (float*)(h->persist + o_lp); h->lang_step = (float*)(h->persist + o_ls);
-    h->seeds = (unsigned long long*)(h->persist + o_sd);
-    HIPCHK(hipMemset(h->persist, 0, off));
+    pl.persist_bytes = off;
+    if (!device_alloc(&pl.persist, off)) return fail(USE_E_NOMEM, "cannot allocate %.1f MB of state", off / 1e6);
+    pl.x4 = (float*)(pl.persist + o_x4); pl.Y = (float2*)(pl.persist + o_Y); pl.X = (float2*)(pl.persist + o_X);
+    pl.Xmean = (float2*)(pl.persist + o_Xm); pl.score = (float2*)(pl.persist + o_sc); pl.xin = (float2*)(pl.persist + o_xin);
+    pl.cond_buf = (float2*)(pl.persist + o_cond); pl.Cond = pl.Y;
+    pl.cond2_buf = h->pcp == 8 ? (float2*)(pl.persist + o_c2) : nullptr;
+    pl.silu_temb = (float*)(pl.persist + o_st); pl.tembias = (float*)(pl.persist + o_tb); pl.t_dev = (float*)(pl.persist + o_t);
+    pl.lang_partial = (float*)(pl.persist + o_lp); pl.lang_step = (float*)(pl.persist + o_ls);
+    pl.seeds = (unsigned long long*)(pl.persist + o_sd);
+    HIPCHK(hipMemset(pl.persist, 0, off));
+    h->plan = std::move(built);
     return USE_OK;
 }
 
 int use_workspace_bytes(use_handle* h, size_t* bytes) {
     if (!h || !bytes) return fail(USE_E_INVALID, "null argument");
-    *bytes = h->arena_plan_bytes + h->persist_bytes + h->blob_bytes;
+    *bytes = (h->plan ? h->plan->arena_plan_bytes + h->plan->persist_bytes : 0) + h->blob_bytes;
     return USE_OK;
 }
 
-double use_flops_per_score(use_handle* h) { return h ? h->flops : 0.0; }
+double use_flops_per_score(use_handle* h) { return h && h->plan ? h->plan->flops : 0.0; }
 
 static int check_ready(use_handle* h) {
     if (!h) return fail(USE_E_INVALID, "null handle");
     if (!h->weights_ready) return fail(USE_E_STATE, "weights not committed (use_commit_weights / use_alloc_weight_blob)");
-    if (!h->B) return fail(USE_E_STATE, "use_plan has not been called");
+    if (!h->plan) return fail(USE_E_STATE, "use_plan has not been called");
     // Options are read at plan time (buffer sizes: conv_in_wgs, stats_part, gn_inline, subbatch*; kernel choice: every threshold): a plan
     // built under other options is stale.  An error, not a silent re-plan: a re-plan frees the captured graphs and the sampler tables
     // behind the caller's back (and round 5's answer - overflowing the arena and abort() - was no answer at all).
-    if (h->opt_gen_at_plan != g_opt_gen)
+    if (h->plan->opt_gen != g_opt_gen)
         return fail(USE_E_STATE, "use_set_option was called after use_plan: the plan is stale, call use_plan (and use_set_sampler) again");
     return USE_OK;
 }
 
 // after an evaluation was issued: did every tensor fit its arena?  (defence in depth behind check_ready's stale-plan test)
 static int eval_status(use_handle* h) {
-    bool bad = h->arena.overflow;
-    for (int i = 0; i < MAX_SUB; ++i) bad = bad || h->sub_arena[i].overflow || h->st_arena[i].overflow;
+    Plan& pl = *h->plan;
+    bool bad = pl.arena.overflow;
+    for (int i = 0; i < MAX_SUB; ++i) bad = bad || pl.sub_arena[i].overflow || pl.st_arena[i].overflow;
     if (!bad) return USE_OK;
-    h->arena.overflow = false; h->dry = false;
-    for (int i = 0; i < MAX_SUB; ++i) h->sub_arena[i].overflow = h->st_arena[i].overflow = false;
+    pl.arena.overflow = false; pl.dry = false;
+    for (int i = 0; i < MAX_SUB; ++i) pl.sub_arena[i].overflow = pl.st_arena[i].overflow = false;
     return fail(USE_E_STATE, "activation workspace too small for this evaluation (an option that sizes plan buffers changed after use_plan?): call use_plan again; the output is invalid");
 }
 
@@ -1301,6 +1260,7 @@ static int eval_status(use_handle* h) {
 static int eval_net(use_handle* h, const void* x, const void* y, const float* t, void* out, use_stream_t stream, float sign,
                     const void* y2 = nullptr) {
     int rc = check_ready(h); if (rc) return rc;
+    Plan& pl = *h->plan;
     const use_config& c = h->cfg;
     const bool two_ch = c.input_channels == 2;
     if (!x || !out) return fail(USE_E_INVALID, "null tensor");
@@ -1309,8 +1269,8 @@ static int eval_net(use_handle* h, const void* x, const void* y, const float* t,
     if (two_ch ? y != nullptr : y == nullptr) return fail(USE_E_INVALID, two_ch ? "a 2-channel network takes x alone (y must be null)" : "null tensor");
     if (!t && (!c.unconditional || !c.no_sigma_scale)) return fail(USE_E_INVALID, "this network needs the time t");
     hipStream_t s = (hipStream_t)stream;
-    if (!c.unconditional) run_temb(h, t, h->B, h->silu_temb, h->tembias, s);
-    run_score(h, (const float2*)x, (const float2*)y, c.unconditional ? nullptr : h->tembias, h->dense_rows, t, 1, (float2*)out, s, sign,
+    if (!c.unconditional) run_temb(h, t, pl.B, pl.silu_temb, pl.tembias, s);
+    run_score(h, (const float2*)x, (const float2*)y, c.unconditional ? nullptr : pl.tembias, h->dense_rows, t, 1, (float2*)out, s, sign,
               (const float2*)y2);
     HIPCHK(hipGetLastError());
     return eval_status(h);
@@ -1392,40 +1352,43 @@ int use_timesteps(int N, float t_eps, float* out) {
 
 int use_set_sampler(use_handle* h, const use_sampler_config* sc) {
     int rc = check_ready(h); if (rc) return rc;
+    Plan& pl = *h->plan;
     if (!sc || sc->N < 1) return fail(USE_E_INVALID, "sampler needs N >= 1");
     if (h->cfg.unconditional || h->cfg.input_channels == 2 || h->cfg.no_sigma_scale)
         return fail(USE_E_STATE, "the reverse-SDE sampler needs the conditional 4-channel score network");
     if (sc->predictor < 0 || sc->predictor > 2 || sc->corrector < 0 || sc->corrector > 2) return fail(USE_E_INVALID, "unknown predictor/corrector id");
     if (sc->corrector != USE_CORR_NONE && sc->corrector_steps < 0) return fail(USE_E_INVALID, "negative corrector_steps");
     HIPCHK(hipSetDevice(h->device));
-    if (h->sampler_set && !memcmp(&h->sc, sc, sizeof *sc)) return USE_OK;       // unchanged (e.g. a parked plan taken back): tables and graphs stay
+    if (pl.sampler_set && !memcmp(&pl.sc, sc, sizeof *sc)) return USE_OK;       // unchanged (e.g. a parked plan taken back): tables and graphs stay
     HIPCHK(hipDeviceSynchronize());
     drop_graphs(h);
-    h->sc = *sc;
-    linspace_f32(1.0f, sc->t_eps, sc->N, h->timesteps);         // sampling/__init__.py:63 (sde.T == 1)
-    if (h->temb_table) { HIPCHK(hipFree(h->temb_table)); h->temb_table = nullptr; }
-    if (h->silu_table) { HIPCHK(hipFree(h->silu_table)); h->silu_table = nullptr; }
-    if (h->ts_dev) { HIPCHK(hipFree(h->ts_dev)); h->ts_dev = nullptr; }
-    HIPCHK(hipMalloc((void**)&h->temb_table, (size_t)sc->N * h->dense_rows * 4));
-    HIPCHK(hipMalloc((void**)&h->silu_table, (size_t)sc->N * 4 * h->cfg.nf * 4));
-    HIPCHK(hipMalloc((void**)&h->ts_dev, (size_t)sc->N * 4));
-    HIPCHK(hipMemcpy(h->ts_dev, h->timesteps.data(), (size_t)sc->N * 4, hipMemcpyHostToDevice));
-    run_temb(h, h->ts_dev, sc->N, h->silu_table, h->temb_table, nullptr);   // t is batch-uniform and known up front
+    pl.sc = *sc;
+    linspace_f32(1.0f, sc->t_eps, sc->N, pl.timesteps);         // sampling/__init__.py:63 (sde.T == 1)
+    if (pl.temb_table) { HIPCHK(hipFree(pl.temb_table)); pl.temb_table = nullptr; }
+    if (pl.silu_table) { HIPCHK(hipFree(pl.silu_table)); pl.silu_table = nullptr; }
+    if (pl.ts_dev) { HIPCHK(hipFree(pl.ts_dev)); pl.ts_dev = nullptr; }
+    HIPCHK(hipMalloc((void**)&pl.temb_table, (size_t)sc->N * h->dense_rows * 4));
+    HIPCHK(hipMalloc((void**)&pl.silu_table, (size_t)sc->N * 4 * h->cfg.nf * 4));
+    HIPCHK(hipMalloc((void**)&pl.ts_dev, (size_t)sc->N * 4));
+    HIPCHK(hipMemcpy(pl.ts_dev, pl.timesteps.data(), (size_t)sc->N * 4, hipMemcpyHostToDevice));
+    run_temb(h, pl.ts_dev, sc->N, pl.silu_table, pl.temb_table, nullptr);   // t is batch-uniform and known up front
     HIPCHK(hipDeviceSynchronize());
-    h->sampler_set = true;
+    pl.sampler_set = true;
     return USE_OK;
 }
 
 int use_num_noise_draws(use_handle* h) {
-    if (!h || !h->sampler_set) return fail(USE_E_STATE, "sampler not configured");
-    const int ncorr = h->sc.corrector == USE_CORR_NONE ? 0 : h->sc.corrector_steps;
-    return 1 + h->sc.N * (ncorr + (h->sc.predictor == USE_PRED_NONE ? 0 : 1));
+    if (!h || !h->plan || !h->plan->sampler_set) return fail(USE_E_STATE, "sampler not configured");
+    const Plan& pl = *h->plan;
+    const int ncorr = pl.sc.corrector == USE_CORR_NONE ? 0 : pl.sc.corrector_steps;
+    return 1 + pl.sc.N * (ncorr + (pl.sc.predictor == USE_PRED_NONE ? 0 : 1));
 }
 
 int use_get_timesteps(use_handle* h, float* out, int n) {
-    if (!h || !h->sampler_set || !out) return fail(USE_E_STATE, "sampler not configured");
-    for (int i = 0; i < n && i < (int)h->timesteps.size(); ++i) out[i] = h->timesteps[i];
-    return (int)h->timesteps.size();
+    if (!h || !h->plan || !h->plan->sampler_set || !out) return fail(USE_E_STATE, "sampler not configured");
+    const Plan& pl = *h->plan;
+    for (int i = 0; i < n && i < (int)pl.timesteps.size(); ++i) out[i] = pl.timesteps[i];
+    return (int)pl.timesteps.size();
 }
 
 int use_sample(use_handle* h, const void* y, const void* noise, uint64_t seed, void* out, use_stream_t stream) {
@@ -1439,12 +1402,13 @@ int use_sample_cond(use_handle* h, const void* y, const void* cond, const void* 
 // the sampler's inputs into the plan's buffers: the SDE's y, and the conditioning the network sees beside x - y itself, or a
 // separate one (condition="denoised"), and the second one of condition="both"
 static int load_sampler_inputs(use_handle* h, const void* y, const void* cond, const void* cond2, hipStream_t s) {
-    const size_t n = (size_t)h->B * h->cfg.n_freq * h->T;
-    HIPCHK(hipMemcpyAsync(h->Y, y, n * 8, hipMemcpyDeviceToDevice, s));
-    if (cond2) HIPCHK(hipMemcpyAsync(h->cond2_buf, cond2, n * 8, hipMemcpyDeviceToDevice, s));
-    float2* want = cond ? h->cond_buf : h->Y;
-    if (want != h->Cond) { HIPCHK(hipStreamSynchronize(s)); drop_graphs(h); h->Cond = want; }    // captured graphs hold the pointer
-    if (cond) HIPCHK(hipMemcpyAsync(h->cond_buf, cond, n * 8, hipMemcpyDeviceToDevice, s));
+    Plan& pl = *h->plan;
+    const size_t n = (size_t)pl.B * h->cfg.n_freq * pl.T;
+    HIPCHK(hipMemcpyAsync(pl.Y, y, n * 8, hipMemcpyDeviceToDevice, s));
+    if (cond2) HIPCHK(hipMemcpyAsync(pl.cond2_buf, cond2, n * 8, hipMemcpyDeviceToDevice, s));
+    float2* want = cond ? pl.cond_buf : pl.Y;
+    if (want != pl.Cond) { HIPCHK(hipStreamSynchronize(s)); drop_graphs(h); pl.Cond = want; }    // captured graphs hold the pointer
+    if (cond) HIPCHK(hipMemcpyAsync(pl.cond_buf, cond, n * 8, hipMemcpyDeviceToDevice, s));
     return USE_OK;
 }
 
@@ -1463,10 +1427,10 @@ static void upload_item_seeds(unsigned long long* dst, const uint64_t* seeds_hos
 }
 
 // what every sampler checks first; `set` is the plan's flag that the sampler at hand has been configured
-static int check_sample_args(use_handle* h, bool use_handle::*set, const char* unset, const void* y, const void* cond2, const void* out,
+static int check_sample_args(use_handle* h, bool Plan::*set, const char* unset, const void* y, const void* cond2, const void* out,
                              const char* six_hint) {
     int rc = check_ready(h); if (rc) return rc;
-    if (!(h->*set)) return fail(USE_E_STATE, "%s", unset);
+    if (!((*h->plan).*set)) return fail(USE_E_STATE, "%s", unset);
     if (!y || !out) return fail(USE_E_INVALID, "null tensor");
     if ((h->cfg.input_channels == 6) != (cond2 != nullptr))
         return h->cfg.input_channels == 6 ? fail(USE_E_INVALID, "a 6-channel network samples with two conditioning tensors%s", six_hint)
@@ -1501,55 +1465,56 @@ static int capture_graph(use_handle* h, const char* what, F&& record, hipGraphEx
 // use_sample_cond2 (seeds_host == null, per_item false) and use_sample_items (per_item)
 static int sample_impl(use_handle* h, const void* y, const void* cond, const void* cond2, const void* noise, uint64_t seed,
                        const uint64_t* seeds_host, bool per_item, void* out, use_stream_t stream) {
-    int rc = check_sample_args(h, &use_handle::sampler_set, "use_set_sampler has not been called", y, cond2, out, " (use_sample_cond2)");
+    int rc = check_sample_args(h, &Plan::sampler_set, "use_set_sampler has not been called", y, cond2, out, " (use_sample_cond2)");
     if (rc) return rc;
+    Plan& pl = *h->plan;
     hipStream_t s = (hipStream_t)stream;
-    const size_t n = (size_t)h->B * h->cfg.n_freq * h->T;
+    const size_t n = (size_t)pl.B * h->cfg.n_freq * pl.T;
     rc = load_sampler_inputs(h, y, cond, cond2, s); if (rc) return rc;
-    // both forms keep their seeds in h->seeds, and so do both forms' graphs: each call uploads its own (per item without seeds: all its noise
+    // both forms keep their seeds in pl.seeds, and so do both forms' graphs: each call uploads its own (per item without seeds: all its noise
     // is injected, and its kernels read none)
-    if (per_item) { if (seeds_host) upload_item_seeds(h->seeds, seeds_host, h->B, s); }
-    else hipLaunchKernelGGL(set_rng_kernel, dim3(1), dim3(1), 0, s, h->seeds, (unsigned long long)seed);
-    if (!h->sc.use_graph) {
-        run_sampler(h, (const float2*)noise, s, 0, h->sc.N, per_item);
+    if (per_item) { if (seeds_host) upload_item_seeds(pl.seeds, seeds_host, pl.B, s); }
+    else hipLaunchKernelGGL(set_rng_kernel, dim3(1), dim3(1), 0, s, pl.seeds, (unsigned long long)seed);
+    if (!pl.sc.use_graph) {
+        run_sampler(h, (const float2*)noise, s, 0, pl.sc.N, per_item);
         rc = eval_status(h); if (rc) return rc;
     } else {
         const int gi = (noise ? 1 : 0) + (per_item ? 2 : 0);
         const float2* nz = nullptr;
         if (noise) {
             const size_t nb = (size_t)use_num_noise_draws(h) * n * 8;
-            if (nb > h->noise_copy_bytes) {
+            if (nb > pl.noise_copy_bytes) {
                 HIPCHK(hipStreamSynchronize(s));
-                if (h->noise_copy) HIPCHK(hipFree(h->noise_copy));
-                h->noise_copy = nullptr; h->noise_copy_bytes = 0;
+                if (pl.noise_copy) HIPCHK(hipFree(pl.noise_copy));
+                pl.noise_copy = nullptr; pl.noise_copy_bytes = 0;
                 for (int k = 1; k < 4; k += 2) {                           // both forms' injected-noise graphs hold the address
-                    for (auto g : h->graph_exec[k]) if (g) (void)hipGraphExecDestroy(g);
-                    h->graph_exec[k].clear();
+                    for (auto g : pl.graph_exec[k]) if (g) (void)hipGraphExecDestroy(g);
+                    pl.graph_exec[k].clear();
                 }
-                if (hipMalloc((void**)&h->noise_copy, nb) != hipSuccess) return fail(USE_E_NOMEM, "cannot allocate %.1f MB noise staging", nb / 1e6);
-                h->noise_copy_bytes = nb;
+                if (hipMalloc((void**)&pl.noise_copy, nb) != hipSuccess) return fail(USE_E_NOMEM, "cannot allocate %.1f MB noise staging", nb / 1e6);
+                pl.noise_copy_bytes = nb;
             }
-            HIPCHK(hipMemcpyAsync(h->noise_copy, noise, nb, hipMemcpyDeviceToDevice, s));
-            nz = h->noise_copy;
+            HIPCHK(hipMemcpyAsync(pl.noise_copy, noise, nb, hipMemcpyDeviceToDevice, s));
+            nz = pl.noise_copy;
         }
-        if (h->graph_exec[gi].empty()) {
+        if (pl.graph_exec[gi].empty()) {
             // The loop is captured in segments of at most 64 score evaluations (~16 k kernel nodes each, the size the
             // configs[1] graph has): one graph of the N = 200 config's 400 evaluations (~10^5 nodes) crashes the HIP runtime
             // at instantiation.  The segments are launched back to back on the caller's stream.
             rc = ensure_cap_stream(h); if (rc) return rc;
-            const int ncorr = h->sc.corrector == USE_CORR_NONE ? 0 : h->sc.corrector_steps;
+            const int ncorr = pl.sc.corrector == USE_CORR_NONE ? 0 : pl.sc.corrector_steps;
             const int per_seg = std::max(1, 64 / (ncorr + 1));
-            for (int i0 = 0; i0 < h->sc.N; i0 += per_seg) {
+            for (int i0 = 0; i0 < pl.sc.N; i0 += per_seg) {
                 hipGraphExec_t ge = nullptr;
                 rc = capture_graph(h, "the sampling loop",
-                                   [&](hipStream_t cs) { run_sampler(h, nz, cs, i0, std::min(h->sc.N, i0 + per_seg), per_item); }, &ge);
+                                   [&](hipStream_t cs) { run_sampler(h, nz, cs, i0, std::min(pl.sc.N, i0 + per_seg), per_item); }, &ge);
                 if (rc) { drop_graphs(h); return rc; }
-                h->graph_exec[gi].push_back(ge);
+                pl.graph_exec[gi].push_back(ge);
             }
         }
-        for (auto ge : h->graph_exec[gi]) HIPCHK(hipGraphLaunch(ge, s));
+        for (auto ge : pl.graph_exec[gi]) HIPCHK(hipGraphLaunch(ge, s));
     }
-    HIPCHK(hipMemcpyAsync(out, h->Xmean, n * 8, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(out, pl.Xmean, n * 8, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipGetLastError());
     return USE_OK;
 }
@@ -1766,54 +1731,55 @@ int use_set_ode(use_handle* h, const use_ode_config* oc) {
     if (h->cfg.unconditional || h->cfg.input_channels == 2 || h->cfg.no_sigma_scale)
         return fail(USE_E_STATE, "the ODE sampler needs the conditional 4- or 6-channel score network");
     rc = ode_check_config(oc); if (rc) return rc;
-    h->oc = *oc;
-    h->ode_set = true;
+    h->plan->oc = *oc;
+    h->plan->ode_set = true;
     return USE_OK;
 }
 
 int use_sample_ode(use_handle* h, const void* y, const void* cond, const void* cond2, const void* noise, uint64_t seed, void* out,
                    int* nfev, int* status, use_stream_t stream) {
-    int rc = check_sample_args(h, &use_handle::ode_set, "use_set_ode has not been called", y, cond2, out, "");
+    int rc = check_sample_args(h, &Plan::ode_set, "use_set_ode has not been called", y, cond2, out, "");
     if (rc) return rc;
+    Plan& pl = *h->plan;
     hipStream_t s = (hipStream_t)stream;
-    const long n_per_b = (long)h->cfg.n_freq * h->T, n = (long)h->B * n_per_b;
+    const long n_per_b = (long)h->cfg.n_freq * pl.T, n = (long)pl.B * n_per_b;
     use_ode* o = h->ode_run;
-    if (!o || o->d.B != h->B || o->d.n_per_b != n_per_b || memcmp(&o->cfg, &h->oc, sizeof h->oc)) {
+    if (!o || o->d.B != pl.B || o->d.n_per_b != n_per_b || memcmp(&o->cfg, &pl.oc, sizeof pl.oc)) {
         HIPCHK(hipStreamSynchronize(s));
         if (h->ode_graph) { (void)hipGraphExecDestroy(h->ode_graph); h->ode_graph = nullptr; }   // it holds the old stepper's buffers
         if (o) (void)use_ode_destroy(o);
         h->ode_run = nullptr;
-        rc = use_ode_create(h, h->B, n_per_b, &h->oc, &h->ode_run); if (rc) return rc;
+        rc = use_ode_create(h, pl.B, n_per_b, &pl.oc, &h->ode_run); if (rc) return rc;
         o = h->ode_run;
     }
     rc = load_sampler_inputs(h, y, cond, cond2, s); if (rc) return rc;
-    o->d.ysde = h->Y;
-    const float2* c2 = h->pcp == 8 ? h->cond2_buf : nullptr;
-    auto eval = [&](int row) {                              // the network at the items' stage times, into h->score
-        const float* t = o->d.ts + (size_t)row * h->B;
-        run_temb(h, t, h->B, h->silu_temb, h->tembias, s);
-        run_score(h, o->d.xin, h->Cond, h->tembias, h->dense_rows, t, 1, h->score, s, -1.f, c2);
+    o->d.ysde = pl.Y;
+    const float2* c2 = h->pcp == 8 ? pl.cond2_buf : nullptr;
+    auto eval = [&](int row) {                              // the network at the items' stage times, into pl.score
+        const float* t = o->d.ts + (size_t)row * pl.B;
+        run_temb(h, t, pl.B, pl.silu_temb, pl.tembias, s);
+        run_score(h, o->d.xin, pl.Cond, pl.tembias, h->dense_rows, t, 1, pl.score, s, -1.f, c2);
     };
     auto step = [&](hipStream_t st) {                       // one RK45 attempt per running group: 6 evaluations
         for (int r = 1; r <= 6; ++r) {
-            const float* t = o->d.ts + (size_t)r * h->B;
-            run_temb(h, t, h->B, h->silu_temb, h->tembias, st);
-            run_score(h, o->d.xin, h->Cond, h->tembias, h->dense_rows, t, 1, h->score, st, -1.f, c2);
-            ode_supply_impl(o, h->score, 1, st);
+            const float* t = o->d.ts + (size_t)r * pl.B;
+            run_temb(h, t, pl.B, pl.silu_temb, pl.tembias, st);
+            run_score(h, o->d.xin, pl.Cond, pl.tembias, h->dense_rows, t, 1, pl.score, st, -1.f, c2);
+            ode_supply_impl(o, pl.score, 1, st);
         }
     };
     // 1. prior: draw 0 of the Philox stream (use_sample's), or the given draw
-    hipLaunchKernelGGL(set_rng_kernel, dim3(1), dim3(1), 0, s, h->seeds, (unsigned long long)seed);
-    launch_prior(h->Y, (const float2*)noise, SdeRng{h->seeds, 0}, ouve_std(h->cfg, 1.0f), o->d.xin, 1, n, s);
+    hipLaunchKernelGGL(set_rng_kernel, dim3(1), dim3(1), 0, s, pl.seeds, (unsigned long long)seed);
+    launch_prior(pl.Y, (const float2*)noise, SdeRng{pl.seeds, 0}, ouve_std(h->cfg, 1.0f), o->d.xin, 1, n, s);
     // 2. f0 and select_initial_step
     ode_start_impl(o, s);
-    eval(0); ode_supply_impl(o, h->score, 1, s);
-    if (o->phase == 7) { eval(7); ode_supply_impl(o, h->score, 1, s); }
+    eval(0); ode_supply_impl(o, pl.score, 1, s);
+    if (o->phase == 7) { eval(7); ode_supply_impl(o, pl.score, 1, s); }
     HIPCHK(hipGetLastError());
     rc = eval_status(h); if (rc) return rc;
     // 3. steps until every group is done
-    if (h->oc.use_graph) {
-        const std::vector<const void*> key = {o, o->buf, h->persist, h->arena.base, h->Cond, c2, h->Y, h->blob};   // (use_plan drops it too)
+    if (pl.oc.use_graph) {
+        const std::vector<const void*> key = {o, o->buf, pl.persist, pl.arena.base, pl.Cond, c2, pl.Y, h->blob};   // (use_plan drops it too)
         if (h->ode_graph && key != h->ode_graph_key) { (void)hipGraphExecDestroy(h->ode_graph); h->ode_graph = nullptr; }
         if (!h->ode_graph) {
             rc = ensure_cap_stream(h); if (rc) return rc;
@@ -1827,19 +1793,19 @@ int use_sample_ode(use_handle* h, const void* y, const void* cond, const void* c
         bool done = false;
         rc = ode_all_done(o, s, &done); if (rc) return rc;
         if (done) break;
-        if (h->ode_graph && h->oc.use_graph) HIPCHK(hipGraphLaunch(h->ode_graph, s));
+        if (h->ode_graph && pl.oc.use_graph) HIPCHK(hipGraphLaunch(h->ode_graph, s));
         else { step(s); HIPCHK(hipGetLastError()); rc = eval_status(h); if (rc) return rc; }
     }
     // 4. denoise: one reverse-diffusion step at t_eps without its noise (x_mean); 5. out
-    launch_ode_result(o->d, h->X, s);
-    if (h->oc.denoise) {
-        hipLaunchKernelGGL(fill_f32_kernel, dim3(1), dim3(256), 0, s, h->t_dev, h->oc.t_eps, h->B);
-        run_temb(h, h->t_dev, h->B, h->silu_temb, h->tembias, s);
-        run_score(h, h->X, h->Cond, h->tembias, h->dense_rows, h->t_dev, 1, h->score, s, -1.f, c2);
-        float cd, cs, cn; predictor_coeffs(h->cfg, USE_PRED_REVERSE_DIFFUSION, h->oc.t_eps, h->oc.N, cd, cs, cn);
-        launch_predictor(h->X, h->Y, h->score, nullptr, SdeRng{h->seeds, 1}, cd, cs, cn, h->Xmean, (float2*)out, 1, n, s);
+    launch_ode_result(o->d, pl.X, s);
+    if (pl.oc.denoise) {
+        hipLaunchKernelGGL(fill_f32_kernel, dim3(1), dim3(256), 0, s, pl.t_dev, pl.oc.t_eps, pl.B);
+        run_temb(h, pl.t_dev, pl.B, pl.silu_temb, pl.tembias, s);
+        run_score(h, pl.X, pl.Cond, pl.tembias, h->dense_rows, pl.t_dev, 1, pl.score, s, -1.f, c2);
+        float cd, cs, cn; predictor_coeffs(h->cfg, USE_PRED_REVERSE_DIFFUSION, pl.oc.t_eps, pl.oc.N, cd, cs, cn);
+        launch_predictor(pl.X, pl.Y, pl.score, nullptr, SdeRng{pl.seeds, 1}, cd, cs, cn, pl.Xmean, (float2*)out, 1, n, s);
     } else {
-        HIPCHK(hipMemcpyAsync(out, h->X, (size_t)n * 8, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(out, pl.X, (size_t)n * 8, hipMemcpyDeviceToDevice, s));
     }
     HIPCHK(hipGetLastError());
     rc = eval_status(h); if (rc) return rc;
@@ -2545,10 +2511,12 @@ int use_op_dense_bwd(const float* g, const float* temb, const float* Wd, int B, 
 
 int use_debug_tensor(use_handle* h, const char* name, void** dev_ptr, int* dims4, int* dtype) {
     if (!h || !name) return fail(USE_E_INVALID, "null argument");
-    auto it = h->debug.find(name);
-    if (it == h->debug.end()) return fail(USE_E_INVALID, "no debug tensor '%s'", name);
+    if (!h->plan) return fail(USE_E_INVALID, "no debug tensor '%s'", name);
+    const Plan& pl = *h->plan;
+    auto it = pl.debug.find(name);
+    if (it == pl.debug.end()) return fail(USE_E_INVALID, "no debug tensor '%s'", name);
     if (dev_ptr) *dev_ptr = it->second.p;
-    if (dims4) { dims4[0] = h->debug_B; dims4[1] = it->second.H; dims4[2] = it->second.W; dims4[3] = it->second.C; }
+    if (dims4) { dims4[0] = pl.debug_B; dims4[1] = it->second.H; dims4[2] = it->second.W; dims4[3] = it->second.C; }
     if (dtype) *dtype = it->second.dtype;
     return USE_OK;
 }
