@@ -381,7 +381,8 @@ int use_conv_bench(const use_conv_case* c, float* out_host, float* stats_host, d
 /* ---- single operators of the path on caller-owned device tensors (NHWC: [B][H][W][C], C contiguous) with host fp32 weights.
  * Test / bring-up surface: the per-operator golden vectors of the reference reach the HIP kernels through these.
  * use_op_conv: out = ((conv3x3|1x1(act(a x + b)) + conv1x1(x0|x1) + bias + temb[b]) + res) * out_scale, exactly the fused operator of the
- *   res-block (ResnetBlockBigGANpp, layerspp.py:282-314); channel counts are multiples of 32 (zero-pad smaller ones); `w` is the
+ *   res-block (ResnetBlockBigGANpp, layerspp.py:282-314); channel counts are multiples of 32 (zero-pad smaller ones; the one exception
+ *   is the network's input convolution, below); `w` is the
  *   reference's [Cout][Cin][3][3] (ntaps 9) or [Cout][Cin] (ntaps 1) tensor, `w2` [Cout][XC]; coef = GroupNorm folded to (a, b) per
  *   (item, channel) or null; stats (zeroed by the caller) receives the fixed-point GroupNorm totals of the output.  variant: 0 = the
  *   library's dispatcher, 1 generic, 2 conv_v2, 4 conv_v4, 5 conv_v5, 7 conv_sk; a forced variant that cannot run the case returns
@@ -390,10 +391,22 @@ int use_conv_bench(const use_conv_case* c, float* out_host, float* stats_host, d
  *   ConvArgs: out = ((conv + shortcut + bias + temb) + res) * out_scale + (pyr . w4 + b4)); gn_st0 (with coef null) makes the kernel
  *   finalise GroupNorm(gn_groups, eps gn_eps) of concat(src0, src1) itself from the totals its producers accumulated, with the affine
  *   gn_gamma / gn_beta, as the engine does on the small maps; temb_bstride is the distance between temb's rows (0: Cout, -1: shared).
+ *   stats_part / stats_parts: the GroupNorm totals as per-workgroup partial totals [B][stats_parts][Cout][2], written with plain stores
+ *   (the caller need not zero them) in place of the atomics on `stats`, as the engine's large maps run; stats_parts must be what
+ *   use_conv_choice answers for the same op under the same options (> 0), `stats` must be null, and a forced variant whose kernel only
+ *   knows atomics refuses (USE_E_INVALID, nothing is launched).  Summed over the parts they are the integers `stats` would hold.
+ *   The network's input convolution as the engine issues it also runs here (variant 0 or 1): dtype fp32, ntaps 9, C0 = 4 (or 8: the
+ *   6-channel input, two zero channels), no second source, no shortcut, nothing fused in front or behind (bias, out_scale and the totals
+ *   only), Cout a multiple of 8 (above 32 with C0 = 8); `w` is [Cout][C0][3][3].  With 16-bit output, C0 = 4 and Cout above 32 it runs
+ *   on the engine's split-bf16 weight copy (conv_in_split), else on the fp32 weights (conv_in; C0 = 8: conv_generic).  Variants 2 / 4 /
+ *   5 / 7 refuse it as they refuse any case their kernel cannot run.
  * use_op_fir: upsample_2d / downsample_2d with the [1,3,3,1] kernel (up_or_down_sampling.py:202-264); out_act = FIR(act(a x + b)),
  *   out_raw = FIR(x) (either may be null).
  * use_op_attention: softmax(q k^T / sqrt(C)) v per item (AttnBlockpp core, layerspp.py:84-88), q/k/v/out [B][N][C].
  * use_op_gn_finalize: GroupNorm totals (as accumulated in `stats`) of up to two concatenated sources -> coef[b][c] = (a, b).
+ * use_op_gn_finalize_parts: the same with either form per source: totals st_i [B][C_i][2] (nt_i = 0), or nt_i > 0 per-workgroup partial
+ *   totals pt_i [B][nt_i][C_i][2] (use_conv_op::stats_part) - integer sums, so the coefficients are those of the summed totals bit for
+ *   bit.  USE_E_INVALID (nothing is launched): both or neither form for a source, groups not dividing C0 + C1, a null pointer.
  * use_op_fir and use_op_attention return USE_E_INVALID (nothing is launched) for an unknown dtype, for C that is not a whole number of
  *   16-byte channel chunks (FIR: C % 8 in 16 bit, C % 4 in fp32) and for a row that does not fit the LDS (attention: (C + N) * 4 bytes).
  * The remaining kernels of one score evaluation, one launch each on `stream`, argument check in front, no synchronisation:
@@ -431,12 +444,14 @@ typedef struct use_conv_op {
     int gn_groups;                        /*   groups over C0+C1 channels */
     float gn_eps;
     int temb_bstride;                     /* elements between temb's batch rows: 0 = Cout, -1 = one row shared by the batch */
+    long long* stats_part;                /* device [B][stats_parts][Cout][2] or null: per-workgroup partial totals in place of `stats` */
+    int stats_parts;                      /*   the count use_conv_choice answers for this op */
 } use_conv_op;
 int use_op_conv(const use_conv_op* c, use_stream_t stream);
 /* use_conv_choice: which kernel the library's dispatcher (variant 0) would run this op on under the current options, without running
- *   it (host only: no HIP call; the op is validated as use_op_conv validates it, its variant field is ignored).  It also answers for
- *   the network's input convolution as the engine issues it, which use_op_conv does not run: dtype fp32, ntaps 9, C0 = 4 (or 8: the
- *   6-channel input), no second source and no shortcut; with 16-bit output it then has the engine's split-bf16 weight copy.  name receives one of
+ *   it (host only: no HIP call; the channel counts are validated as use_op_conv validates them, the variant field is ignored).  For
+ *   the network's input convolution (dtype fp32, ntaps 9, C0 = 4 or 8, no second source and no shortcut) it answers for any flags and
+ *   Cout, with the engine's split-bf16 weight copy where the engine keeps one; use_op_conv runs the form the engine issues.  name receives one of
  *   "conv_sk", "conv_v4", "conv_v5", "conv_v2", "pyr_conv", "pyr_conv_ws", "conv_in", "conv_in_split", "conv_generic"; stats_parts the
  *   per-workgroup partial GroupNorm totals per (item, channel) that kernel can write in place of atomics (0: it only knows atomics).
  *   Either may be null. */
@@ -453,6 +468,9 @@ int use_op_fir(const void* src, int dtype, const float* coef, int act, void* out
 int use_op_attention(const void* q, const void* k, const void* v, void* out, int dtype, int B, int N, int C, use_stream_t stream);
 int use_op_gn_finalize(const long long* st0, int C0, const long long* st1, int C1, const float* gamma, const float* beta, int groups,
                        int hw, float eps, float* coef, int B, use_stream_t stream);
+int use_op_gn_finalize_parts(const long long* st0, const long long* pt0, int nt0, int C0, const long long* st1, const long long* pt1, int nt1,
+                             int C1, const float* gamma, const float* beta, int groups, int hw, float eps, float* coef, int B,
+                             use_stream_t stream);
 int use_op_attn_block(const void* x, const long long* gn_st, const float* gamma, const float* beta, int groups, float eps, const void* wq,
                       const void* wk, const void* wv, const void* wo, const float* bq, const float* bk, const float* bv, const float* bo,
                       void* out, long long* stats, int dtype, int B, int N, int C, use_stream_t stream);

@@ -8,7 +8,8 @@ over the same rows, with use_op_conv's padding and slab-weight rule in front (fo
 
 Rows: every distinct convolution of one score evaluation of the benchmark's network (nf 128, ch_mult 1,1,2,2,2,2,2, F = 512, T' = 640) in
 bf16 / fp16 / fp32 storage, both sides of each threshold of the dispatch, and each option that moves the choice.  The network's input
-convolution (4 fp32 channels, or 8 for the 6-channel input) is no use_op_conv op; use_conv_choice answers for it with the weight copies
+convolution (4 fp32 channels, or 8 for the 6-channel input) is the one op whose channel counts are no multiples of 32; use_op_conv runs
+it and use_conv_choice answers for it with the weight copies
 the engine keeps (the split-bf16 copy for 16-bit output and cout_pad a multiple of 128), and its rows pin conv_in against conv_in_split
 and the partial-totals count under conv_in_wgs, which sizes an arena buffer.  The op surface pads Cout to 32 or a multiple of 128 and gives
 every 3x3 convolution whose channels divide the K chunk its slab-major weights, as the engine does: "cout_pad not a multiple of 128" and
@@ -372,9 +373,23 @@ def test_table_covers_the_kernels_and_thresholds():
         assert moved, option
 
 
-def test_use_op_conv_still_refuses_the_input_convolution_shape():
-    """What use_conv_choice accepts beyond use_op_conv is the engine's input op alone: other channel counts that are no multiples of 32 stay refused."""
+def test_only_the_input_convolution_shape_is_accepted_beyond_multiples_of_32():
+    """What use_conv_choice and use_op_conv accept beyond channel counts that are multiples of 32 is the engine's input op alone (fp32, 3x3,
+    C0 = 4 or 8, one source, no shortcut), which use_op_conv runs (tests/test_hip_input_head_kernels.py); other channel counts stay
+    refused by both, use_op_conv before its first HIP call (the pointers below are never dereferenced)."""
+    L = _lib.lib()
     for o in (dict(dt=0, H=16, W=16, C0=12, Cout=64), dict(dt=1, H=16, W=16, C0=4, Cout=64), dict(dt=0, H=16, W=16, C0=4, Cout=64, ntaps=1),
               dict(dt=0, H=16, W=16, C0=4, C1=4, Cout=64)):
         with pytest.raises(AssertionError, match="multiples of 32"):
             conv_choice(o)
+        buf = C.create_string_buffer(64)
+        op = _lib.UseConvOp()
+        op.B, op.H, op.W, op.Cout, op.ntaps, op.dtype, op.out_dtype = 2, o["H"], o["W"], o["Cout"], o.get("ntaps", 9), o["dt"], o["dt"]
+        op.C0, op.C1, op.out_scale = o["C0"], o.get("C1", 0), 1.0
+        op.src0 = op.w = op.out = C.addressof(buf)
+        if op.C1:
+            op.src1 = C.addressof(buf)
+        assert L.use_op_conv(C.byref(op), None) == -1 and b"multiples of 32" in L.use_last_error()
+    # the input op as the engine issues it: what use_op_conv runs, use_conv_choice answers for
+    assert conv_choice(dict(dt=0, odt=1, H=16, W=16, C0=4, Cout=64)) == ("conv_in_split", 2)
+    assert conv_choice(dict(dt=0, H=16, W=16, C0=8, Cout=64)) == ("conv_generic", 0)

@@ -8,6 +8,7 @@ Tolerances (relative to the reference tensor's max magnitude unless stated):
                   sampler outputs <= 3 x (rel-max) / 2 x (rel-L2) the reference's 60-evaluation chain drift; single operators: 4 ulps of the storage type.
   Every test prints what it measured (pytest -s, "[measured]").
 """
+import math
 import os
 
 import numpy as np
@@ -228,8 +229,10 @@ def test_intermediate_taps_match_oracle_fp32(golden_dir, engines, sd_np):
 @pytest.mark.parametrize("prec", ["bf16", "fp16"])
 def test_input_convolution_16bit_modes_match_the_oracle(golden_dir, engines, sd_np, prec):
     """conv_in_split_kernel (16-bit storage modes: the fp32 input convolution as a split-bf16 contraction, x w = xh wh + xh wl +
-    xl wh) against the CPU oracle's fp32 convolution of the same input: the only difference allowed is the rounding of the stored
-    output (bf16: 2^-9, fp16: 2^-12 relative) plus the dropped 2^-16 term."""
+    xl wh) against the CPU oracle's fp32 convolution of the same input, per element: the rounding of the stored output (u |want|), the
+    split's dropped terms (< 2^-16 S, S = conv(|x4|, |w|) + |bias|) and the fp32 accumulation of the kernel (K = 108) and of the oracle
+    itself (K = 36), 2 x 2^-24 sqrt(K) S each - the bound tests/test_hip_input_head_kernels.py derives and holds launch by launch against
+    float64; here on the 512 x 64 map of the whole network."""
     g = dict(np.load(os.path.join(golden_dir, "forward_large.npz")))
     x = torch.from_numpy(g["x"]); t = torch.from_numpy(g["t_b"])
     taps = {}
@@ -241,7 +244,12 @@ def test_input_convolution_16bit_modes_match_the_oracle(golden_dir, engines, sd_
     want = taps["h_in"]
     ulp = 2.0 ** -8 if prec == "bf16" else 2.0 ** -11
     err = (got - want).abs()
-    assert float((err - (ulp * want.abs() + 2e-4)).max()) <= 0, float(err.max())
+    sd = no.to_torch(sd_np)
+    x4 = torch.cat([p for k in range(x.shape[1]) for p in (x[:, [k]].real, x[:, [k]].imag)], dim=1) * 2 - 1.0
+    S = torch.nn.functional.conv2d(x4.double().abs(), sd["all_modules.3.weight"].double().abs(), sd["all_modules.3.bias"].double().abs(), padding=1)
+    bound = ulp * want.abs() + (2.0 ** -16 + 2 * 2.0 ** -24 * (math.sqrt(108) + math.sqrt(36))) * S
+    print(f"[measured] h_in {prec}: worst err / bound {float((err / bound).max()):.3f} (max err {float(err.max()):.3g}; the bound was ulp |want| + 2e-4, now + {float(bound.max() - (ulp * want.abs()).max()):.2g} at most)")
+    assert float((err / bound).max()) <= 1, float(err.max())
 
 
 @pytest.mark.parametrize("prec", ["bf16", "fp16"])

@@ -44,7 +44,8 @@ class UseConvOp(C.Structure):
                 [(k, C.c_void_p) for k in ("src0", "src1", "coef", "w", "bias", "temb", "x0", "x1", "w2", "res")] +
                 [("out_scale", C.c_float), ("out", C.c_void_p), ("stats", C.c_void_p)] +
                 [(k, C.c_void_p) for k in ("pyr", "w4", "b4", "gn_st0", "gn_st1", "gn_gamma", "gn_beta")] +
-                [("gn_groups", C.c_int), ("gn_eps", C.c_float), ("temb_bstride", C.c_int)])
+                [("gn_groups", C.c_int), ("gn_eps", C.c_float), ("temb_bstride", C.c_int)] +
+                [("stats_part", C.c_void_p), ("stats_parts", C.c_int)])
 
 
 class UseHipError(RuntimeError):
@@ -127,6 +128,7 @@ SYMBOLS = {
     "use_op_fir": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "use_op_attention": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "use_op_gn_finalize": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _f, _vp, _i, _vp]),
+    "use_op_gn_finalize_parts": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _f, _vp, _i, _vp]),
     "use_op_attn_block": (_i, [_vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "use_op_combine_add": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i64, _i, _vp]),
     "use_op_temb_mlp": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),

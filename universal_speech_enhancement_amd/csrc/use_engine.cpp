@@ -2088,8 +2088,8 @@ __global__ void to_float_kernel(const void* p, float* out, size_t n, int dtype) 
 // use_conv_op::temb_bstride: 0 = Cout (one row per item), -1 = one row shared by the batch, else the stride in elements
 static int op_temb_bstride(const use_conv_op* c) { return c->temb_bstride == 0 ? c->Cout : c->temb_bstride < 0 ? 0 : c->temb_bstride; }
 
-// The network's input convolution as the engine issues it: 3x3 over the 4 (or 8: 6 + 2 padding) packed fp32 input channels.  use_op_conv
-// does not run it (channel counts there are multiples of 32); use_conv_choice answers for it, with the weight copies the engine keeps
+// The network's input convolution as the engine issues it: 3x3 over the 4 (or 8: 6 + 2 padding) packed fp32 input channels: the one op
+// whose channel counts are no multiples of 32.  use_op_conv runs it and use_conv_choice answers for it, with the weight copies the engine keeps
 static bool op_is_net_input(int C0, int C1, int XC, int ntaps, int dt) { return dt == DT_F32 && (C0 == 4 || C0 == 8) && C1 == 0 && XC == 0 && ntaps == 9; }
 // The op surface's weight layout as a launch description: Cout padded to 32 or to a multiple of 128, slab-major copies (wb / w2b) wherever
 // conv_wide_kernel's K chunk divides the channels; the dimensions and types; no optional operand
@@ -2106,7 +2106,8 @@ static ConvDesc op_desc(int H, int W, int C0, int C1, int XC0, int XC1, int Cout
 // ... of a use_conv_op: the presence flags from the op's own fields (what use_op_conv launches and use_conv_choice asks about)
 static ConvDesc op_conv_desc(const use_conv_op* c) {
     ConvDesc d = op_desc(c->H, c->W, c->C0, c->C1, c->XC0, c->XC1, c->Cout, c->ntaps == 1 ? 1 : 9, c->dtype, c->out_dtype, c->act);
-    d.coef = c->coef != nullptr; d.res = c->res != nullptr; d.pyr = c->pyr != nullptr; d.temb = c->temb != nullptr; d.stats = c->stats != nullptr;
+    d.coef = c->coef != nullptr; d.res = c->res != nullptr; d.pyr = c->pyr != nullptr; d.temb = c->temb != nullptr;
+    d.stats = c->stats != nullptr || c->stats_part != nullptr;
     return d;
 }
 // the operands of a use_conv_op other than its weights and its fused shortcut, into the launch arguments
@@ -2114,7 +2115,7 @@ static void op_conv_operands(const use_conv_op* c, const ConvDesc& d, const floa
     a.B = c->B; a.H = c->H; a.W = c->W; a.Cout = c->Cout; a.ntaps = d.ntaps; a.in_dtype = d.in_dtype; a.out_dtype = d.out_dtype;
     a.src0 = c->src0; a.src1 = c->C1 ? c->src1 : nullptr; a.C0 = c->C0; a.C1 = c->C1; a.coef = c->coef; a.act = c->act;
     a.bias = bias; a.temb = c->temb; a.temb_bstride = op_temb_bstride(c); a.res = c->res; a.out_scale = c->out_scale;
-    a.out = c->out; a.stats = c->stats;
+    a.out = c->out; a.stats = c->stats; a.stats_part = c->stats_part;
 }
 // hipMalloc into a list the caller frees; null: out of memory
 static void* dev_alloc(std::vector<void*>& bufs, size_t bytes) { void* q = nullptr; if (hipMalloc(&q, bytes) != hipSuccess) return nullptr; bufs.push_back(q); return q; }
@@ -2134,6 +2135,23 @@ static bool stage_conv_weights(const ConvDesc& d, const float* hw, const float* 
         return true;
     };
     a.cout_pad = d.cout_pad;
+    if (op_is_net_input(d.C0, d.C1, d.XC0 + d.XC1, d.ntaps, d.in_dtype)) {
+        // the input convolution: the plain [cout_pad][9][C0] fp32 copy and, where op_desc says so, the split-bf16 copy
+        // [cout_pad][CONV_IN_SPLIT_K] in the place of the slab-major one, as pack_conv lays them into the blob
+        const void* none = nullptr;
+        if (!stage(hw, d.C0, 9, false, &a.w, &none)) return false;
+        if (d.wb) {
+            ConvW w; w.cin = w.cin_src = d.C0; w.cout = w.cout_src = d.Cout; w.cout_pad = d.cout_pad; w.ntaps = 9; w.w_dtype = DT_F32;
+            const size_t bytes = (size_t)d.cout_pad * CONV_IN_SPLIT_K * 2;
+            char* q = (char*)dev_alloc(bufs, bytes);
+            if (!q) return false;
+            std::vector<char> hp(bytes);
+            pack_conv_in_split(hw, w, hp.data());
+            (void)hipMemcpy(q, hp.data(), bytes, hipMemcpyHostToDevice);
+            a.wb = q;
+        }
+        return true;
+    }
     return stage(hw, d.C0 + d.C1, d.ntaps, d.wb, &a.w, &a.wb) && (!d.w2 || stage(hw2, d.XC0 + d.XC1, 1, d.w2b, &a.w2, &a.w2b));
 }
 
@@ -2249,10 +2267,37 @@ static int op_conv_check(const use_conv_op* c, const char* who, bool net_input_o
     if (XC && (!c->w2 || !c->x0)) return fail(USE_E_INVALID, "%s: shortcut without weights / input", who);
     return USE_OK;
 }
+// The partial-totals form of a use_op_conv (use_conv_op::stats_part): the count must be the dispatcher's for this op and these options
+// (use_conv_choice), and the kernel the variant runs must know the form.  No HIP call.
+static int op_conv_check_parts(const use_conv_op* c, const ConvDesc& d) {
+    if (!c->stats_part && !c->stats_parts) return USE_OK;
+    if (!c->stats_part || c->stats_parts < 1) return fail(USE_E_INVALID, "use_op_conv: stats_part and stats_parts > 0 go together");
+    if (c->stats) return fail(USE_E_INVALID, "use_op_conv: stats_part and stats are two forms of the same totals (pass one)");
+    const ConvChoice ch = conv_choose(d);
+    const int v = c->variant;
+    // what the variant's kernel writes: the dispatcher's kernel; the wide conv (a case it cannot run is refused below, with its own
+    // message); of the kernels of variant 1 the split input convolution alone
+    const bool knows = v == 0 ? ch.stats_parts > 0 : v == 1 ? ch.k == IN_SPLIT : v == 4 ? !conv_v4_unrunnable(d) : v == 5 ? !conv_v5_unrunnable(d) : false;
+    if ((v == 4 && conv_v4_unrunnable(d)) || (v == 5 && conv_v5_unrunnable(d))) return USE_OK;
+    if (!knows) return fail(USE_E_INVALID, "use_op_conv: the kernel of variant %d (%s) only knows atomic totals (stats)", v, v == 0 ? conv_kernel_name(ch.k) : "forced");
+    if (c->stats_parts != ch.stats_parts)
+        return fail(USE_E_INVALID, "use_op_conv: stats_parts = %d, but %s writes %d partial totals per (item, channel) here (use_conv_choice)",
+                    c->stats_parts, conv_kernel_name(ch.k), ch.stats_parts);
+    return USE_OK;
+}
 int use_op_conv(const use_conv_op* c, use_stream_t stream) {
-    int rc = op_conv_check(c, "use_op_conv"); if (rc) return rc;
+    int rc = op_conv_check(c, "use_op_conv", true); if (rc) return rc;
     const ConvDesc d = op_conv_desc(c);
     const int Cin = c->C0 + c->C1, XC = c->XC0 + c->XC1;
+    if (Cin % 32) {
+        // the input convolution as the engine issues it: nothing in front of it and nothing fused behind it; the kernels store 16-byte
+        // channel chunks, and the generic kernel that takes the 8-channel input stages 128 weight rows
+        if (c->coef || c->gn_st0 || c->act || c->res || c->pyr || c->temb)
+            return fail(USE_E_INVALID, "use_op_conv: the input convolution (C0 = %d) takes no GroupNorm, activation, residual, Combine or temb", c->C0);
+        if (c->Cout % 8 || (c->C0 == 8 && d.cout_pad % 128))
+            return fail(USE_E_INVALID, "use_op_conv: the input convolution needs Cout %% 8 == 0 (and Cout > 32 with C0 = 8), not %d", c->Cout);
+    }
+    if ((rc = op_conv_check_parts(c, d))) return rc;
     hipStream_t s = (hipStream_t)stream;
     std::vector<void*> bufs;
     auto dalloc = [&](size_t bytes) { return dev_alloc(bufs, bytes); };
@@ -2434,6 +2479,22 @@ int use_op_gn_finalize(const long long* st0, int C0, const long long* st1, int C
                        int hw, float eps, float* coef, int B, use_stream_t stream) {
     if (!st0 || !gamma || !beta || !coef || C0 < 1 || groups < 1 || (C0 + C1) % groups) return fail(USE_E_INVALID, "use_op_gn_finalize: bad argument");
     launch_gn_finalize(st0, C0, C1 ? st1 : nullptr, C1, gamma, beta, groups, hw, eps, coef, B, (hipStream_t)stream);
+    return USE_OK;
+}
+// launch_gn_finalize with either form per source: totals st_i [B][C_i][2], or nt_i per-workgroup partial totals pt_i [B][nt_i][C_i][2]
+// (use_conv_op::stats_part) - what Fwd::gn_coef issues for the large maps
+int use_op_gn_finalize_parts(const long long* st0, const long long* pt0, int nt0, int C0, const long long* st1, const long long* pt1, int nt1, int C1,
+                             const float* gamma, const float* beta, int groups, int hw, float eps, float* coef, int B, use_stream_t stream) {
+    if (!gamma || !beta || !coef || C0 < 1 || C1 < 0 || B < 1 || hw < 1) return fail(USE_E_INVALID, "use_op_gn_finalize_parts: bad argument");
+    if (groups < 1 || groups > 65535 || (C0 + C1) % groups) return fail(USE_E_INVALID, "use_op_gn_finalize_parts: %d groups do not divide C0 + C1 = %d", groups, C0 + C1);
+    if ((st0 != nullptr) == (pt0 != nullptr) || (pt0 ? nt0 < 1 : nt0 != 0))
+        return fail(USE_E_INVALID, "use_op_gn_finalize_parts: source 0 is either totals (st0, nt0 = 0) or nt0 > 0 partial totals (pt0)");
+    if (C1 ? ((st1 != nullptr) == (pt1 != nullptr) || (pt1 ? nt1 < 1 : nt1 != 0)) : (st1 || pt1 || nt1))
+        return fail(USE_E_INVALID, "use_op_gn_finalize_parts: source 1 is either totals (st1, nt1 = 0) or nt1 > 0 partial totals (pt1); nothing with C1 = 0");
+    // gn_finalize_part_kernel: one 256-thread block per (item, group) writes the group's coefficients, a thread per channel
+    if ((pt0 || pt1) && (C0 + C1) / groups > 256) return fail(USE_E_INVALID, "use_op_gn_finalize_parts: more than 256 channels per group");
+    launch_gn_finalize(st0, C0, st1, C1, gamma, beta, groups, hw, eps, coef, B, (hipStream_t)stream, pt0, nt0, pt1, nt1);
+    HIPCHK(hipGetLastError());
     return USE_OK;
 }
 
