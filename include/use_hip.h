@@ -540,6 +540,64 @@ int use_timesteps(int N, float t_eps, float* out);
 int use_debug_tensor(use_handle* h, const char* name, void** dev_ptr, int* dims4, int* dtype);
 double use_flops_per_score(use_handle* h);   /* 2*MAC of the conv/linear layers for the current plan */
 
+/* Launch trace (test infrastructure; use_set_option("trace", 1), off by default, not a tuning knob: it does not mark plans stale).
+ * While it is on, the primary sub-batch of every network evaluation (use_score / use_score2 / use_forward*) records one entry per launch
+ * it issues, in launch order; the list belongs to the plan and is replaced by the next evaluation (cleared where the debug tensors are).
+ * No launch changes: the entries are filled from the very argument structs the launches take.  The activation arena is only reset at the
+ * start of an evaluation, so after a synchronise every pointer below is still valid device memory and holds what that launch wrote
+ * (exception: USE_TRACE_COMBINE_ADD rewrites its input in place).  Not recorded: the zeroing of the totals region at the start of an
+ * evaluation (one launch; every totals pointer lies inside it), and the launches of the long-sequence attention path (N > 512 tokens:
+ * transpose, per-item GEMMs, softmax rows) - its q / k / v / NIN_3 convolutions are.
+ *
+ * Tensors are NHWC; dims = (B, H, W, C) with B the items of the sub-batch, dtype = USE_PREC_* of the storage.  Complex64 tensors (the
+ * evaluation's x, y, y2 and its output) are given as fp32 with C = 2.  Totals: [B][C][2] 64-bit fixed point (sum, sum of squares, each
+ * * 2^20) of the stored values; partial totals: [B][parts][C][2] in the same format, to be summed over `parts`.  Where part_in[k] is set the
+ * launch reads those and not totals_in[k] (the pointer is passed all the same, and nothing was written behind it).
+ *
+ * kind                  in[]                                               out[]                       further fields
+ * USE_TRACE_TEMB        -                                                  0: tembias [n,1,1,dense_rows]   t; params W (Fourier), X0..X3 (Linear 1, 2)
+ *                                                                          1: silu(temb) [n,1,1,4 nf]      (the Dense_0 rows: see CONV's DENSE_W / DENSE_B)
+ * USE_TRACE_PACK_INPUT  0: x, 1: y, 2: y2 (absent: ptr null)               0: x4 [B,F,T,4 or 8] fp32       (B: the whole batch)
+ * USE_TRACE_CONV        0, 1: concat halves; 2, 3: shortcut sources;       0                               kernel, act, out_scale, ntaps, gn_* (inline), coef,
+ *                       4: residual; 5: Combine / pyramid input (fp32)                                     totals_in / part_in of in[0], in[1] (inline GroupNorm),
+ *                                                                                                          totals_out or part_out + parts_out, tembias + temb_row
+ *                                                                                                          + temb_stride; params W, B (bias of W), W2, B2 (bias
+ *                                                                                                          of W2: the kernel adds B + B2 as one array), GN_*,
+ *                                                                                                          CB_* (Combine), DENSE_* (the layer whose row is read)
+ * USE_TRACE_FIR_DOWN/UP 0                                                  0: FIR(act(a x + b)) or absent  coef (read; null: out[1] alone, the input pyramid),
+ *                                                                          1: FIR(x)                       act
+ * USE_TRACE_GN_FINALIZE 0, 1: the maps whose totals are read (not read     -                               totals_in / part_in + parts_in, coef_out [B][C0+C1][2],
+ *                       themselves)                                                                        gn_groups, gn_inv_n, gn_eps; params GN_*
+ * USE_TRACE_ATTN_FUSED  0                                                  0                               totals_in[0], totals_out, gn_*; params GN_*, W / B
+ *                                                                                                          (NIN_0), X0..X5 (NIN_1 W, b; NIN_2; NIN_3), out_scale
+ * USE_TRACE_ATTN_CORE   0: q, 1: k, 2: v                                   0
+ * USE_TRACE_COMBINE_ADD 0: the map (in place), 5: pyramid input            0: == in[0]                     totals_out (zeroed by a launch of its own just before);
+ *                                                                                                          params CB_*
+ * USE_TRACE_SCORE_OUT   0: pyramid fp32                                    0: the evaluation's output      t (null: no division), t_stride, out_scale = sign;
+ *                                                                                                          params W, B (output_layer)
+ * Parameter names are the reference state-dict keys (as use_expected_weight reports them); unused roles are null.  The strings belong
+ * to the handle.  use_trace_count: entries of the current plan's last evaluation (0: none, or the trace was off), < 0: error. */
+enum { USE_TRACE_TEMB = 1, USE_TRACE_PACK_INPUT, USE_TRACE_CONV, USE_TRACE_FIR_DOWN, USE_TRACE_FIR_UP, USE_TRACE_GN_FINALIZE,
+       USE_TRACE_ATTN_FUSED, USE_TRACE_ATTN_CORE, USE_TRACE_COMBINE_ADD, USE_TRACE_SCORE_OUT };
+enum { USE_TP_W = 0, USE_TP_B, USE_TP_W2, USE_TP_B2, USE_TP_GN_W, USE_TP_GN_B, USE_TP_CB_W, USE_TP_CB_B, USE_TP_DENSE_W, USE_TP_DENSE_B,
+       USE_TP_X0, USE_TP_X1, USE_TP_X2, USE_TP_X3, USE_TP_X4, USE_TP_X5, USE_TP_COUNT };
+typedef struct use_trace_tensor { const void* ptr; int dims[4]; int dtype; } use_trace_tensor;
+typedef struct use_trace_entry {
+    int kind;
+    char kernel[32];                     /* ConvChoice::label for a convolution, else the launch's name */
+    use_trace_tensor in[6], out[2];
+    const void* totals_in[2]; const void* part_in[2]; int parts_in[2];
+    const void* totals_out; const void* part_out; int parts_out;
+    const void* coef; const void* coef_out;
+    const void* tembias; int temb_row, temb_stride;      /* the launch reads tembias[b * temb_stride + temb_row + c] */
+    const void* t; int t_stride;
+    int act; float out_scale; int ntaps;
+    int gn_groups; float gn_inv_n, gn_eps;               /* gn_groups 0: no GroupNorm finalised by this launch */
+    const char* params[USE_TP_COUNT];
+} use_trace_entry;
+int use_trace_count(use_handle* h);
+int use_trace_entry_get(use_handle* h, int index, use_trace_entry* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -122,7 +122,10 @@ def ncsnpp_forward(
     (biggan blocks, fir, output_skip / input_skip 'sum', fourier, scale_by_sigma, not centered).
 
     x: complex64 [B, 2, F, T] = cat([x_t, Y], dim=1); t: float32 [B].  Returns complex64 [B, 1, F, T].
-    ``taps`` (optional dict) receives named intermediates for per-layer parity tests.
+    ``taps`` (optional dict) receives named intermediates for per-layer parity tests: ``temb``, ``h_in``, ``pre_attn``, ``post_attn``,
+    ``pyramid``, and, named by the index m of the module ``all_modules.m`` that produced them, ``block.m`` (output of the res-block m; of a
+    down block: after the Combine that follows it), ``attn.m`` (the attention block's output), ``pyramid.m`` (the progressive output after
+    the pyramid convolution m of a level) and ``x4`` (the packed, rescaled network input).
 
     ``discriminative=True`` (ncsnpp.py:86-92; the generator of the LSGAN refine stage,
     GAN/generator/ncsnpp/model_wrapper.py:54,114-121): x is complex64 [B, 1, F, T] alone, ``t`` is ignored -- no time
@@ -142,36 +145,43 @@ def ncsnpp_forward(
     input_pyramid = x4
     hs: List[torch.Tensor] = [F.conv2d(x4, sd[f"all_modules.{m}.weight"], sd[f"all_modules.{m}.bias"], padding=1)]
     m += 1
+    def tap(name, v):
+        if taps is not None:
+            taps[name] = v
+        return v
+
     if taps is not None:
-        taps["temb"] = temb; taps["h_in"] = hs[0]
+        taps["temb"] = temb; taps["h_in"] = hs[0]; taps["x4"] = x4
     for lvl in range(L):
         for _ in range(num_res_blocks):
-            h = resblock_biggan(hs[-1], temb, sd, f"all_modules.{m}"); m += 1
+            h = tap(f"block.{m}", resblock_biggan(hs[-1], temb, sd, f"all_modules.{m}")); m += 1
             hs.append(h)
         if lvl != L - 1:
+            mb = m
             h = resblock_biggan(hs[-1], temb, sd, f"all_modules.{m}", down=True); m += 1
             input_pyramid = fir_downsample2(input_pyramid)                     # ncsnpp.py:404
             h = F.conv2d(input_pyramid, sd[f"all_modules.{m}.Conv_0.weight"],  # Combine 'sum', layerspp.py:50-55
                          sd[f"all_modules.{m}.Conv_0.bias"]) + h
             m += 1
-            hs.append(h)
+            hs.append(tap(f"block.{mb}", h))
     h = hs[-1]
-    h = resblock_biggan(h, temb, sd, f"all_modules.{m}"); m += 1
+    h = tap(f"block.{m}", resblock_biggan(h, temb, sd, f"all_modules.{m}")); m += 1
     if taps is not None:
         taps["pre_attn"] = h
-    h = attn_block(h, sd, f"all_modules.{m}"); m += 1
+    h = tap(f"attn.{m}", attn_block(h, sd, f"all_modules.{m}")); m += 1
     if taps is not None:
         taps["post_attn"] = h
-    h = resblock_biggan(h, temb, sd, f"all_modules.{m}"); m += 1
+    h = tap(f"block.{m}", resblock_biggan(h, temb, sd, f"all_modules.{m}")); m += 1
     pyramid = None
     for lvl in reversed(range(L)):
         for _ in range(num_res_blocks + 1):
-            h = resblock_biggan(torch.cat([h, hs.pop()], dim=1), temb, sd, f"all_modules.{m}"); m += 1
+            h = tap(f"block.{m}", resblock_biggan(torch.cat([h, hs.pop()], dim=1), temb, sd, f"all_modules.{m}")); m += 1
         ph = F.silu(_gn(h, sd, f"all_modules.{m}")); m += 1                    # ncsnpp.py:443,457
-        ph = F.conv2d(ph, sd[f"all_modules.{m}.weight"], sd[f"all_modules.{m}.bias"], padding=1); m += 1
-        pyramid = ph if pyramid is None else fir_upsample2(pyramid) + ph      # ncsnpp.py:456-461
+        ph = F.conv2d(ph, sd[f"all_modules.{m}.weight"], sd[f"all_modules.{m}.bias"], padding=1)
+        pyramid = tap(f"pyramid.{m}", ph if pyramid is None else fir_upsample2(pyramid) + ph)   # ncsnpp.py:456-461
+        m += 1
         if lvl != 0:
-            h = resblock_biggan(h, temb, sd, f"all_modules.{m}", up=True); m += 1
+            h = tap(f"block.{m}", resblock_biggan(h, temb, sd, f"all_modules.{m}", up=True)); m += 1
     assert not hs
     if taps is not None:
         taps["pyramid"] = pyramid

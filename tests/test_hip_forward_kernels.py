@@ -391,6 +391,25 @@ def _ratio(got, ref, part, dt):
     return float(r.max())
 
 
+def _fused_totals_ratio(stats, got, dt):
+    """Output totals of the fused attention block (int64 [B,C,2]) against the float64 sums of the stored out [B,N,C] (module docstring)."""
+    v = got.double()
+    got_s, got_q = stats[..., 0].double() / 2 ** 20, stats[..., 1].double() / 2 ** 20
+    tol_s = (48 * U32 + UNIT[dt]) * v.abs().sum(1) + 2.0 ** -20
+    tol_q = (48 * U32 + 2.01 * UNIT[dt]) * (v * v).sum(1) + 2.0 ** -20
+    return max(float(((got_s - v.sum(1)).abs() / tol_s).max()), float(((got_q - (v * v).sum(1)).abs() / tol_q).max()))
+
+
+def _combine_totals_ratio(stats, got, pix):
+    """Totals of combine_add (int64 [B,C,2]) against the float64 sums of the stored map [B,pix,C] (module docstring)."""
+    v = got.double()
+    st = stats.double() / 2 ** 20
+    nblk = (pix + 63) // 64
+    tol_s = 64 * U32 * v.abs().sum(1) + nblk * 2.0 ** -21
+    tol_q = 64 * U32 * (v * v).sum(1) + nblk * 2.0 ** -21
+    return max(float(((st[..., 0] - v.sum(1)).abs() / tol_s).max()), float(((st[..., 1] - (v * v).sum(1)).abs() / tol_q).max()))
+
+
 ATTN_NS = (1, 2, 40, 80, 96, 255, 256, 257, 600)
 ATTN_CS = (32, 64, 256, 384)
 ATTN_KINDS = ("ordinary", "peaked", "flat")
@@ -795,11 +814,7 @@ def test_fused_attention_block_matches_float64_reference(c):
     r_st = 0.0
     if stats is not None:
         assert bool((sbuf[-TAIL:] == 0x5A5A5A5A5A5A).all()), "write past the end of stats"
-        v = got.double()
-        got_s, got_q = stats.cpu()[..., 0].double() / 2 ** 20, stats.cpu()[..., 1].double() / 2 ** 20
-        tol_s = (48 * U32 + UNIT[dt]) * v.abs().sum(1) + 2.0 ** -20
-        tol_q = (48 * U32 + 2.01 * UNIT[dt]) * (v * v).sum(1) + 2.0 ** -20
-        r_st = max(float(((got_s - v.sum(1)).abs() / tol_s).max()), float(((got_q - (v * v).sum(1)).abs() / tol_q).max()))
+        r_st = _fused_totals_ratio(stats.cpu(), got, dt)
     print(f"[fused] {_fused_id(c)}: out {r_out:.3f} h {r_h:.3f} (|h err| / max |H| {rel_h:.2e}, mean |H| / mean |x| "
           f"{float(H.abs().mean() / x.abs().mean()):.2f}) totals {r_st:.3f}")
     _measured(_fused_id(c), max(r_out, r_h, r_st))
@@ -852,12 +867,7 @@ def test_combine_add_matches_float64_reference(dt, Cc):
         ref, part = combine_reference(h, pyr, w8, b8)
         got = d_h.cpu()
         worst = max(worst, _ratio(got, ref, part, dt))
-        v = got.double()
-        st = sbuf[:B * Cc * 2].view(B, Cc, 2).cpu().double() / 2 ** 20
-        nblk = (pix + 63) // 64
-        tol_s = 64 * U32 * v.abs().sum(1) + nblk * 2.0 ** -21
-        tol_q = 64 * U32 * (v * v).sum(1) + nblk * 2.0 ** -21
-        worst_st = max(worst_st, float(((st[..., 0] - v.sum(1)).abs() / tol_s).max()), float(((st[..., 1] - (v * v).sum(1)).abs() / tol_q).max()))
+        worst_st = max(worst_st, _combine_totals_ratio(sbuf[:B * Cc * 2].view(B, Cc, 2).cpu(), got, pix))
     print(f"[measured] combine_add_kernel-{DT_NAME[dt]}-C{Cc} totals: worst |err| / bound {worst_st:.3f}")
     _measured(f"combine_add_kernel-{DT_NAME[dt]}-C{Cc}", max(worst, worst_st))
 

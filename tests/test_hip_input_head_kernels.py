@@ -153,6 +153,15 @@ def _totals_ratio(stats, out, n_ser, n_sq, parts):
     return max(float(((got_s - want_s).abs() / tol_s).max()), float(((got_q - want_q).abs() / tol_q).max()))
 
 
+def _finalize_ratios(got, want, mean, std, beta, HW, cpg):
+    """Finalised GroupNorm coefficients got [B,C,2] against float64 ones: worst |err| / bound of a and of b (module docstring); mean, std
+    [B,groups] of the map's groups, cpg channels per group."""
+    bnd = (1.5 * (1 + (mean / std) ** 2) * (math.log2(HW) + 2) * U32).repeat_interleave(cpg, 1)
+    ra = float(((got[..., 0] - want[..., 0]).abs() / (bnd * want[..., 0].abs())).max())
+    rb = float(((got[..., 1] - want[..., 1]).abs() / (2 * bnd * (beta.double().abs()[None] + (mean.repeat_interleave(cpg, 1) * want[..., 0]).abs()))).max())
+    return ra, rb
+
+
 def _worst(got, ref, bound):
     r = (got - ref).abs() / bound
     return float(r.max()), tuple(int(i) for i in np.unravel_index(int(r.argmax()), r.shape))
@@ -556,11 +565,7 @@ def test_finalize_from_partials_matches_finalize_from_totals(C0, nt0, C1, nt1, g
     want = gn_coef_reference(y.reshape(B, 32, 40, Cc), gamma, beta, groups)
     yg = y.permute(0, 2, 1).reshape(B, groups, -1)
     mean, std = yg.mean(-1), yg.std(-1, unbiased=False)
-    cpg = Cc // groups
-    bnd = (1.5 * (1 + (mean / std) ** 2) * (math.log2(HW) + 2) * U32).repeat_interleave(cpg, 1)
-    got = coef_p.double().cpu()
-    ra = float(((got[..., 0] - want[..., 0]).abs() / (bnd * want[..., 0].abs())).max())
-    rb = float(((got[..., 1] - want[..., 1]).abs() / (2 * bnd * (beta.double().abs()[None] + (mean.repeat_interleave(cpg, 1) * want[..., 0]).abs()))).max())
+    ra, rb = _finalize_ratios(coef_p.double().cpu(), want, mean, std, beta, HW, Cc // groups)
     print(f"[fin] C {C0}+{C1} partials {nt0}/{nt1} groups {groups} (|mean|/std up to {float((mean.abs() / std).max()):.0f}): a err/bound {ra:.3f}, b {rb:.3f}")
     assert ra < 1.0 and rb < 1.0
 

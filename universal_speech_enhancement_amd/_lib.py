@@ -48,6 +48,27 @@ class UseConvOp(C.Structure):
                 [("stats_part", C.c_void_p), ("stats_parts", C.c_int)])
 
 
+class UseTraceTensor(C.Structure):
+    _fields_ = [("ptr", C.c_void_p), ("dims", C.c_int * 4), ("dtype", C.c_int)]
+
+
+TRACE_KINDS = {1: "temb", 2: "pack_input", 3: "conv", 4: "fir_down", 5: "fir_up", 6: "gn_finalize", 7: "attn_fused", 8: "attn_core",
+               9: "combine_add", 10: "score_out"}                       # USE_TRACE_*
+TRACE_PARAMS = ("w", "b", "w2", "b2", "gn_w", "gn_b", "cb_w", "cb_b", "dense_w", "dense_b", "x0", "x1", "x2", "x3", "x4", "x5")   # USE_TP_*
+
+
+class UseTraceEntry(C.Structure):
+    _fields_ = [("kind", C.c_int), ("kernel", C.c_char * 32), ("inp", UseTraceTensor * 6), ("out", UseTraceTensor * 2),
+                ("totals_in", C.c_void_p * 2), ("part_in", C.c_void_p * 2), ("parts_in", C.c_int * 2),
+                ("totals_out", C.c_void_p), ("part_out", C.c_void_p), ("parts_out", C.c_int),
+                ("coef", C.c_void_p), ("coef_out", C.c_void_p),
+                ("tembias", C.c_void_p), ("temb_row", C.c_int), ("temb_stride", C.c_int),
+                ("t", C.c_void_p), ("t_stride", C.c_int),
+                ("act", C.c_int), ("out_scale", C.c_float), ("ntaps", C.c_int),
+                ("gn_groups", C.c_int), ("gn_inv_n", C.c_float), ("gn_eps", C.c_float),
+                ("params", C.c_char_p * len(TRACE_PARAMS))]
+
+
 class UseHipError(RuntimeError):
     pass
 
@@ -114,6 +135,8 @@ SYMBOLS = {
     "use_sde_predictor": (_i, [_vp, _i, _f, _i, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _i64, _vp]),
     "use_sde_corrector": (_i, [_vp, _i, _f, _f, _i, _vp, _vp, _vp, _u64, _vp, _vp, _i64, _vp]),
     "use_debug_tensor": (_i, [_vp, C.c_char_p, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i)]),
+    "use_trace_count": (_i, [_vp]),
+    "use_trace_entry_get": (_i, [_vp, _i, C.POINTER(UseTraceEntry)]),
     "use_flops_per_score": (C.c_double, [_vp]),
     "use_get_stat": (_i, [_vp, C.c_char_p, C.POINTER(C.c_longlong)]),
     "use_profile_aux": (_i, [_vp, _i, C.c_char_p, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -146,6 +146,8 @@ struct Plan {
     bool dry = false;                            // bookkeeping-only evaluation (sizing, or after an overflow): what the arenas' dry_on_overflow points at
     std::map<std::string, Act> debug;
     int debug_B = 0;
+    std::vector<use_trace_entry> trace;          // use_set_option("trace", 1): the launches of the last evaluation's primary sub-batch
+    size_t trace_head = 0;                       // ... of which this many were recorded ahead of Fwd::run (time embedding, pack_input)
     double flops = 0.0;
 
     Plan() = default;
@@ -474,6 +476,24 @@ static long g_gn_inline = 128L * 160L;
 static int g_attn_fused = 1;                     // use_set_option("attn_fused", 0): the unfused attention block (3 NIN, core, NIN_3)
 static int g_stats_part = 1;                     // use_set_option("stats_part", 0): GroupNorm totals by atomics on the large maps too
 static int g_stagger_level = 2;                  // use_set_option("stagger_level", l): the next sub-batch starts after level l
+static int g_trace = 0;                          // use_set_option("trace", 1): record every launch of an evaluation (use_trace_entry, use_hip.h)
+
+// ---- launch trace: what each launch read and wrote, for the layer-by-layer tests.  Filled from the launch's own arguments ----
+static use_trace_tensor trace_tensor(const void* p, int B, int H, int W, int C, int dtype) {
+    use_trace_tensor t{}; t.ptr = p; t.dims[0] = B; t.dims[1] = H; t.dims[2] = W; t.dims[3] = C; t.dtype = dtype; return t;
+}
+static use_trace_entry trace_new(int kind, const char* kernel) {
+    use_trace_entry e{}; e.kind = kind; snprintf(e.kernel, sizeof e.kernel, "%s", kernel); return e;
+}
+static const char* trace_pname(const use_handle* h, const std::string& name) {      // the handle's own copy of a state-dict key
+    auto it = h->expected_index.find(name);
+    return it == h->expected_index.end() ? nullptr : h->expected[it->second].name.c_str();
+}
+// entries ahead of Fwd::run (which drops what the previous evaluation left): the first of them starts the new list
+static void trace_push_head(Plan& pl, const use_trace_entry& e) {
+    if (!pl.trace_head) pl.trace.clear();
+    pl.trace.push_back(e); pl.trace_head = pl.trace.size();
+}
 
 __global__ __launch_bounds__(256) void zero16_kernel(uint4* __restrict__ p, size_t n16) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) p[i] = make_uint4(0, 0, 0, 0);
@@ -490,6 +510,8 @@ struct Fwd {
     hipEvent_t ev_stagger = nullptr;              // recorded when the large maps of the down path are done (or null)
     int stagger_level = 2;                        // ... i.e. after this level of the down path
     template <typename T> const T* W(size_t off) const { return (const T*)(h->blob + off); }
+
+    use_trace_tensor tt(const Act& a) const { return trace_tensor(a.p, B, a.H, a.W, a.C, a.dtype); }
 
     Act new_act(int C, int H, int Wd, int dtype, bool stats) {
         Act a; a.C = C; a.H = H; a.W = Wd; a.dtype = dtype;
@@ -514,10 +536,50 @@ struct Fwd {
     float* gn_coef(const Act& a, const Act* a2, const GNW& g) {
         const int C = a.C + (a2 ? a2->C : 0);
         float* coef = (float*)arena->alloc((size_t)B * C * 2 * 4);
+        if (g_trace && primary && !pl.dry) {
+            const int groups = std::min(C / 4, 32);
+            use_trace_entry e = trace_new(USE_TRACE_GN_FINALIZE, (a.part || (a2 && a2->part)) ? "gn_finalize_part" : "gn_finalize");
+            e.in[0] = tt(a); e.totals_in[0] = a.stats; e.part_in[0] = a.part; e.parts_in[0] = a.ntiles;
+            if (a2) { e.in[1] = tt(*a2); e.totals_in[1] = a2->stats; e.part_in[1] = a2->part; e.parts_in[1] = a2->ntiles; }
+            e.coef_out = coef; e.gn_groups = groups; e.gn_inv_n = 1.0f / ((float)(C / groups) * (float)(a.H * a.W)); e.gn_eps = 1e-6f;
+            e.params[USE_TP_GN_W] = trace_pname(h, g.prefix + ".weight"); e.params[USE_TP_GN_B] = trace_pname(h, g.prefix + ".bias");
+            pl.trace.push_back(e);
+        }
         if (!pl.dry)
             launch_gn_finalize(a.stats, a.C, a2 ? a2->stats : nullptr, a2 ? a2->C : 0, W<float>(g.g_off), W<float>(g.b_off),
                                std::min(C / 4, 32), a.H * a.W, 1e-6f, coef, B, s, a.part, a.ntiles, a2 ? a2->part : nullptr, a2 ? a2->ntiles : 0);
         return coef;
+    }
+
+    // the trace entry of one convolution launch, from the arguments it is about to be launched with
+    void trace_conv(const ConvArgs& p, const ConvChoice& ch, const GNW* gn, const ConvW& w, const ConvW* w2, const CombineW* cb, int temb_row) {
+        use_trace_entry e = trace_new(USE_TRACE_CONV, conv_kernel_name(ch.k));
+        e.in[0] = trace_tensor(p.src0, p.B, p.H, p.W, p.C0, p.in_dtype);
+        if (p.src1) e.in[1] = trace_tensor(p.src1, p.B, p.H, p.W, p.C1, p.in_dtype);
+        if (p.x0) e.in[2] = trace_tensor(p.x0, p.B, p.H, p.W, p.XC0, p.in_dtype);
+        if (p.x1) e.in[3] = trace_tensor(p.x1, p.B, p.H, p.W, p.XC1, p.in_dtype);
+        if (p.res) e.in[4] = trace_tensor(p.res, p.B, p.H, p.W, p.Cout, p.out_dtype);
+        if (p.pyr) e.in[5] = trace_tensor(p.pyr, p.B, p.H, p.W, h->pcp, DT_F32);
+        e.out[0] = trace_tensor(p.out, p.B, p.H, p.W, p.Cout, p.out_dtype);
+        e.totals_in[0] = p.gn_st0; e.totals_in[1] = p.gn_st1; e.coef = p.coef;
+        e.totals_out = p.stats; e.part_out = p.stats_part; e.parts_out = p.stats_part ? ch.stats_parts : 0;
+        if (p.temb) { e.tembias = tembias; e.temb_row = temb_row; e.temb_stride = p.temb_bstride; }
+        e.act = p.act; e.out_scale = p.out_scale; e.ntaps = p.ntaps;
+        if (p.gn_st0) { e.gn_groups = p.gn_groups; e.gn_inv_n = p.gn_inv_n; e.gn_eps = p.gn_eps; }
+        e.params[USE_TP_W] = trace_pname(h, w.wname); e.params[USE_TP_B] = trace_pname(h, w.bname);
+        if (w2) { e.params[USE_TP_W2] = trace_pname(h, w2->wname); e.params[USE_TP_B2] = trace_pname(h, w2->bname); }
+        if (gn && p.gn_st0) { e.params[USE_TP_GN_W] = trace_pname(h, gn->prefix + ".weight"); e.params[USE_TP_GN_B] = trace_pname(h, gn->prefix + ".bias"); }
+        if (cb) {
+            const std::string c = "all_modules." + std::to_string(cb->idx) + ".Conv_0";
+            e.params[USE_TP_CB_W] = trace_pname(h, c + ".weight"); e.params[USE_TP_CB_B] = trace_pname(h, c + ".bias");
+        }
+        if (p.temb)
+            for (const ResW& r : h->res)
+                if (r.dense_row0 == temb_row) {
+                    const std::string d = "all_modules." + std::to_string(r.idx) + ".Dense_0";
+                    e.params[USE_TP_DENSE_W] = trace_pname(h, d + ".weight"); e.params[USE_TP_DENSE_B] = trace_pname(h, d + ".bias");
+                }
+        pl.trace.push_back(e);
     }
 
     // gn != null: the input concat(a, a2) goes through this GroupNorm, finalised inside the conv kernel from the producers' totals
@@ -567,6 +629,7 @@ struct Fwd {
         // consumers that read the totals directly (inline GroupNorm below gn_inline pixels, the fused attention) must never meet a producer
         // that wrote partial totals instead: both sides test the same H * W > gn_inline - checked here, where the input is consumed
         if (gn && !coef_arr && (a.part || (a2 && a2->part))) { arena->overflow = true; pl.dry = true; return o; }   // reported by eval_status as a stale plan
+        if (g_trace && primary) trace_conv(p, ch, gn, w, w2, cb, temb_row);
         const bool main_variant = ch.k == WIDE32 || ch.k == WIDE16;           // the dominant kernel (conv_wide_kernel, large maps)
         if (!h->profile || (w.ntaps != 9 && !ch.hbm)) { launch_conv(p, s); return o; }       // (the 1x1 convolutions are not timed)
         // algorithmic HBM bytes of this launch: every operand once (input, shortcut input, residual, output, weights; the dominant kernel's Combine input)
@@ -596,6 +659,11 @@ struct Fwd {
             Act hr = new_act(x.C, H2, W2, dt, false);
             xr = new_act(x.C, H2, W2, dt, false);
             float* coef0 = gn_coef(x, skip, r.gn0);          // the resampling kernels take the GroupNorm as a coefficient array
+            if (g_trace && primary && !pl.dry) {
+                use_trace_entry e = trace_new(r.up ? USE_TRACE_FIR_UP : USE_TRACE_FIR_DOWN, r.up ? "fir_up" : "fir_down");
+                e.in[0] = tt(x); e.out[0] = tt(hr); e.out[1] = tt(xr); e.coef = coef0; e.act = 1;
+                pl.trace.push_back(e);
+            }
             if (!pl.dry) {
                 // reads the map once, writes the activated and the raw resampled copy
                 const double by = (double)B * x.H * x.W * x.C * dtype_size(dt) + 2.0 * B * H2 * W2 * x.C * dtype_size(dt);
@@ -626,6 +694,18 @@ struct Fwd {
             a.wq = h->blob + aw.q.w_off; a.wk = h->blob + aw.k.w_off; a.wv = h->blob + aw.v.w_off; a.wo = h->blob + aw.o.w_off;
             a.bq = W<float>(aw.q.b_off); a.bk = W<float>(aw.k.b_off); a.bv = W<float>(aw.v.b_off); a.bo = W<float>(aw.o.b_off);
             a.stats = o.stats;
+            if (g_trace && primary) {
+                use_trace_entry e = trace_new(USE_TRACE_ATTN_FUSED, "attn_fused");
+                e.in[0] = tt(x); e.out[0] = tt(o); e.totals_in[0] = a.gn_st; e.totals_out = a.stats;
+                e.gn_groups = a.gn_groups; e.gn_inv_n = 1.0f / ((float)(x.C / a.gn_groups) * (float)a.N); e.gn_eps = a.gn_eps;   // (inv_n: the kernel's own, from N and C)
+                e.out_scale = 0.70710678118654752440f;
+                e.params[USE_TP_GN_W] = trace_pname(h, aw.gn.prefix + ".weight"); e.params[USE_TP_GN_B] = trace_pname(h, aw.gn.prefix + ".bias");
+                e.params[USE_TP_W] = trace_pname(h, aw.q.wname); e.params[USE_TP_B] = trace_pname(h, aw.q.bname);
+                e.params[USE_TP_X0] = trace_pname(h, aw.k.wname); e.params[USE_TP_X1] = trace_pname(h, aw.k.bname);
+                e.params[USE_TP_X2] = trace_pname(h, aw.v.wname); e.params[USE_TP_X3] = trace_pname(h, aw.v.bname);
+                e.params[USE_TP_X4] = trace_pname(h, aw.o.wname); e.params[USE_TP_X5] = trace_pname(h, aw.o.bname);
+                pl.trace.push_back(e);
+            }
             launch_attn_fused(a, dt, B, s);
             return o;
         }
@@ -664,6 +744,11 @@ struct Fwd {
                 }
             }
         } else if (!pl.dry) {
+            if (g_trace && primary) {
+                use_trace_entry e = trace_new(USE_TRACE_ATTN_CORE, "attention");
+                e.in[0] = tt(q); e.in[1] = tt(k); e.in[2] = tt(v); e.out[0] = tt(a);
+                pl.trace.push_back(e);
+            }
             launch_attention(q.p, k.p, v.p, a.p, dt, B, N, x.C, s);
         }
         return conv(a, nullptr, nullptr, 0, aw.o, -1, &x, 0.70710678118654752440f, nullptr, nullptr, dt, true);
@@ -683,7 +768,7 @@ struct Fwd {
             const size_t n16 = st_arena->cap / 16;
             hipLaunchKernelGGL(zero16_kernel, dim3((unsigned)std::min<size_t>((n16 + 255) / 256, 1024)), dim3(256), 0, s, (uint4*)st_arena->base, n16);
         }
-        if (primary) { pl.flops = 0.0; pl.debug.clear(); pl.debug_B = B; }
+        if (primary) { pl.flops = 0.0; pl.debug.clear(); pl.debug_B = B; pl.trace.resize(pl.trace_head); pl.trace_head = 0; }
         const int pcp = H->pcp;
         Act xin; xin.p = (void*)x4; xin.C = pcp; xin.H = c.n_freq; xin.W = pl.T; xin.dtype = DT_F32;
         std::vector<Act> hs;
@@ -696,6 +781,11 @@ struct Fwd {
             if (lvl == std::min(stagger_level, L - 1) && ev_stagger && !pl.dry) (void)hipEventRecord(ev_stagger, s);   // small maps follow
             if (lvl != L - 1) {
                 Act nip = new_act(pcp, ipyr.H / 2, ipyr.W / 2, DT_F32, false);        // pyramid_downsample
+                if (g_trace && primary && !pl.dry) {
+                    use_trace_entry e = trace_new(USE_TRACE_FIR_DOWN, "fir_down");
+                    e.in[0] = tt(ipyr); e.out[1] = tt(nip);
+                    pl.trace.push_back(e);
+                }
                 if (!pl.dry) launch_fir_down2(ipyr.p, DT_F32, nullptr, 0, nullptr, nip.p, B, ipyr.H, ipyr.W, pcp, s);
                 ipyr = nip;
                 if (pcp == 4) {                                // Combine fused into the block's last convolution
@@ -703,6 +793,13 @@ struct Fwd {
                 } else {                                       // 6-channel input: Combine as its own pass over the block's output
                     Act o = resblock(hs.back(), nullptr, H->res[ri++]);
                     const CombineW& cb = H->combines[ci++];
+                    if (g_trace && primary && !pl.dry) {
+                        use_trace_entry e = trace_new(USE_TRACE_COMBINE_ADD, "combine_add");
+                        e.in[0] = tt(o); e.in[5] = tt(ipyr); e.out[0] = tt(o); e.totals_out = o.stats;
+                        const std::string cn = "all_modules." + std::to_string(cb.idx) + ".Conv_0";
+                        e.params[USE_TP_CB_W] = trace_pname(h, cn + ".weight"); e.params[USE_TP_CB_B] = trace_pname(h, cn + ".bias");
+                        pl.trace.push_back(e);
+                    }
                     if (!pl.dry) {
                         hipLaunchKernelGGL(zero16_kernel, dim3((unsigned)(((size_t)B * o.C + 255) / 256)), dim3(256), 0, s, (uint4*)o.stats,
                                            (size_t)B * o.C);                                             // totals of the combined map (16 bytes per channel)
@@ -732,6 +829,11 @@ struct Fwd {
                 have_pyr = true;
             } else {
                 Act up = new_act(pcp, pyr.H * 2, pyr.W * 2, DT_F32, false);             // pyramid_upsample
+                if (g_trace && primary && !pl.dry) {
+                    use_trace_entry e = trace_new(USE_TRACE_FIR_UP, "fir_up");
+                    e.in[0] = tt(pyr); e.out[1] = tt(up);
+                    pl.trace.push_back(e);
+                }
                 if (!pl.dry) launch_fir_up2(pyr.p, DT_F32, nullptr, 0, nullptr, up.p, B, pyr.H, pyr.W, pcp, s);
                 pyr = conv(hc, nullptr, &pw.gn, 1, pw.conv, -1, &up, 1.f, nullptr, nullptr, DT_F32, false);
             }
@@ -746,11 +848,29 @@ struct Fwd {
 // time embedding for `rows` time values (batch items, or sampler steps) -> tembias[rows][dense_rows]
 static void run_temb(use_handle* h, const float* t, int n, float* silu_buf, float* out, hipStream_t s) {
     const int nf = h->cfg.nf;
+    if (g_trace && h->plan && !h->plan->dry) {
+        use_trace_entry e = trace_new(USE_TRACE_TEMB, "temb_mlp+temb_dense");
+        e.t = t; e.t_stride = 1;
+        e.out[0] = trace_tensor(out, n, 1, 1, h->dense_rows, DT_F32); e.out[1] = trace_tensor(silu_buf, n, 1, 1, 4 * nf, DT_F32);
+        e.params[USE_TP_W] = trace_pname(h, "all_modules.0.W");
+        e.params[USE_TP_X0] = trace_pname(h, "all_modules.1.weight"); e.params[USE_TP_X1] = trace_pname(h, "all_modules.1.bias");
+        e.params[USE_TP_X2] = trace_pname(h, "all_modules.2.weight"); e.params[USE_TP_X3] = trace_pname(h, "all_modules.2.bias");
+        trace_push_head(*h->plan, e);
+    }
     launch_temb_mlp(t, 1, (const float*)(h->blob + h->gfp_off), (const float*)(h->blob + h->l1w_off),
                     (const float*)(h->blob + h->l1b_off), (const float*)(h->blob + h->l2w_off),
                     (const float*)(h->blob + h->l2b_off), silu_buf, n, nf, s);
     launch_temb_dense(silu_buf, (const float*)(h->blob + h->dense_w_off), (const float*)(h->blob + h->dense_b_off), out,
                       n, h->dense_rows, 4 * nf, s);
+}
+
+static void trace_score_out(use_handle* h, Plan& pl, const Act& pyr, int B, const float* t, int t_stride, const float2* out, float sign) {
+    use_trace_entry e = trace_new(USE_TRACE_SCORE_OUT, "score_out");
+    e.in[0] = trace_tensor(pyr.p, B, pyr.H, pyr.W, pyr.C, pyr.dtype);
+    e.out[0] = trace_tensor(out, B, pyr.H, pyr.W, 2, DT_F32);
+    e.t = t; e.t_stride = t_stride; e.out_scale = sign;
+    e.params[USE_TP_W] = trace_pname(h, "output_layer.weight"); e.params[USE_TP_B] = trace_pname(h, "output_layer.bias");
+    pl.trace.push_back(e);
 }
 
 // score = -net(cat[x, y], t): x, y device complex64
@@ -760,12 +880,21 @@ static void run_score(use_handle* h, const float2* x, const float2* y, const flo
     if (h->cfg.no_sigma_scale) t = nullptr;                   // score_out: no division by t
     const long n_per_b = (long)h->cfg.n_freq * pl.T;
     const int pcp = h->pcp;
+    if (g_trace && !pl.dry) {
+        use_trace_entry e = trace_new(USE_TRACE_PACK_INPUT, "pack_input");
+        e.in[0] = trace_tensor(x, pl.B, h->cfg.n_freq, pl.T, 2, DT_F32);
+        if (y) e.in[1] = trace_tensor(y, pl.B, h->cfg.n_freq, pl.T, 2, DT_F32);
+        if (y2) e.in[2] = trace_tensor(y2, pl.B, h->cfg.n_freq, pl.T, 2, DT_F32);
+        e.out[0] = trace_tensor(pl.x4, pl.B, h->cfg.n_freq, pl.T, pcp, DT_F32);
+        trace_push_head(pl, e);
+    }
     launch_pack_input(x, y, y2, pl.x4, (long)pl.B * n_per_b, s);
     const float* outw = (const float*)(h->blob + h->outw_off); const float* outb = (const float*)(h->blob + h->outb_off);
     if (pl.nsub == 1) {
         Fwd f0{h, pl, s, tembias, temb_bstride, t, t_stride};
         f0.B = pl.B; f0.arena = &pl.arena; f0.st_arena = &pl.st_arena[0];
         Act pyr = f0.run(pl.x4);
+        if (g_trace && !pl.dry) trace_score_out(h, pl, pyr, pl.B, t, t_stride, out, sign);
         if (!pl.dry) launch_score_out((const float*)pyr.p, pcp, t, t_stride, outw, outb, out, pl.B, n_per_b, sign, s);
         return;
     }
@@ -787,6 +916,7 @@ static void run_score(use_handle* h, const float2* x, const float2* y, const flo
         f.B = pl.sub_B[i]; f.arena = i ? &pl.sub_arena[i] : &pl.arena; f.st_arena = &pl.st_arena[i]; f.primary = i == 0;
         if (overlap && i + 1 < pl.nsub) { f.ev_stagger = h->ev_stagger[i]; f.stagger_level = g_stagger_level; }
         Act pyr = f.run(pl.x4 + (size_t)b0 * n_per_b * pcp);
+        if (g_trace && i == 0 && !pl.dry) trace_score_out(h, pl, pyr, pl.sub_B[0], t, t_stride, out, sign);
         if (!pl.dry)
         launch_score_out((const float*)pyr.p, pcp, t ? t + (size_t)b0 * t_stride : nullptr, t_stride, outw, outb,
                          out + (size_t)b0 * n_per_b, pl.sub_B[i], n_per_b, sign, si);
@@ -936,6 +1066,7 @@ int use_get_stat(use_handle* h, const char* name, long long* value) {
 
 int use_set_option(const char* name, long long value) {
     if (!name) return fail(USE_E_INVALID, "option name is null");
+    if (!strcmp(name, "trace")) { g_trace = value != 0; return USE_OK; }   // records launches, changes none: no plan goes stale
     ++g_opt_gen;                                               // plans built under the previous options are not reused
     if (!strcmp(name, "attn_fused")) { g_attn_fused = (int)value; return USE_OK; }
     if (!strcmp(name, "plan_cache")) { g_plan_cache = (int)std::max(0LL, std::min(16LL, value)); return USE_OK; }   // parked plans per handle
@@ -2567,6 +2698,17 @@ int use_op_dense_bwd(const float* g, const float* temb, const float* Wd, int B, 
     if (B < 1 || K < 1 || Cout < 1) return fail(USE_E_INVALID, "use_op_dense_bwd: bad argument (B, K and Cout must be at least 1)");
     launch_dense_bwd(g, temb, Wd, B, K, Cout, dW, db, dtemb, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
+    return USE_OK;
+}
+
+int use_trace_count(use_handle* h) {
+    if (!h) return fail(USE_E_INVALID, "null handle");
+    return h->plan ? (int)h->plan->trace.size() : 0;
+}
+int use_trace_entry_get(use_handle* h, int index, use_trace_entry* out) {
+    if (!h || !out) return fail(USE_E_INVALID, "null argument");
+    if (!h->plan || index < 0 || index >= (int)h->plan->trace.size()) return fail(USE_E_INVALID, "no trace entry %d", index);
+    *out = h->plan->trace[(size_t)index];
     return USE_OK;
 }
 

@@ -460,6 +460,33 @@ class HipScoreEngine:
             raw = raw.view(torch.float16)
         return raw.float().view(*dims[:])
 
+    def trace(self) -> list:
+        """The launches of the last evaluation's primary sub-batch (``use_set_option("trace", 1)``; ``use_trace_entry`` in use_hip.h), one
+        dict per launch: ``kind`` and ``kernel`` as strings, ``in`` / ``out`` lists of ``(ptr, (B, H, W, C), dtype)`` or None, ``params`` a
+        dict role -> state-dict key, the remaining fields under their C names (pointers as int or None)."""
+        def tens(t):
+            return (t.ptr, tuple(t.dims), t.dtype) if t.ptr else None
+        out = []
+        for i in range(check(self.L.use_trace_count(self.h), "use_trace_count")):
+            e = _lib.UseTraceEntry()
+            check(self.L.use_trace_entry_get(self.h, i, C.byref(e)), "use_trace_entry_get")
+            d = {"index": i, "kind": _lib.TRACE_KINDS[e.kind], "kernel": e.kernel.decode(), "in": [tens(t) for t in e.inp],
+                 "out": [tens(t) for t in e.out], "totals_in": list(e.totals_in), "part_in": list(e.part_in), "parts_in": list(e.parts_in),
+                 "params": {r: n.decode() for r, n in zip(_lib.TRACE_PARAMS, e.params) if n}}
+            for k in ("totals_out", "part_out", "parts_out", "coef", "coef_out", "tembias", "temb_row", "temb_stride", "t", "t_stride", "act",
+                      "out_scale", "ntaps", "gn_groups", "gn_inv_n", "gn_eps"):
+                d[k] = getattr(e, k)
+            out.append(d)
+        return out
+
+    def read_device(self, ptr: int, n: int, typestr: str) -> "np.ndarray":
+        """Host copy of ``n`` elements of library-owned device memory (``typestr``: "<f4", "<u2", "<i8"): the tensors a trace entry names."""
+        class _Iface:
+            pass
+        o = _Iface()
+        o.__cuda_array_interface__ = {"shape": (int(n),), "typestr": typestr, "data": (int(ptr), False), "version": 2}
+        return torch.as_tensor(o, device=f"cuda:{self.device}").cpu().numpy()
+
     # ---- stand-alone SDE element-wise updates (use_sde_*) ----------------------------------------------
     def sde_prior(self, y, noise=None, seed=0):
         y = _require_cuda_c64("y", y)
