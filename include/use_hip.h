@@ -403,6 +403,14 @@ int use_conv_bench(const use_conv_case* c, float* out_host, float* stats_host, d
  * use_op_fir: upsample_2d / downsample_2d with the [1,3,3,1] kernel (up_or_down_sampling.py:202-264); out_act = FIR(act(a x + b)),
  *   out_raw = FIR(x) (either may be null).
  * use_op_attention: softmax(q k^T / sqrt(C)) v per item (AttnBlockpp core, layerspp.py:84-88), q/k/v/out [B][N][C].
+ * use_op_attention_gemm: the same core in the form the engine runs above 512 tokens (N = H W; the refine generator's 64x80 bottleneck): vt =
+ *   v^T, per item the scores as a 1x1 convolution of q whose weights are the item's keys (out_scale C^-0.5, no bias), the softmax over all
+ *   B N rows in place, per item a second 1x1 convolution of the probabilities whose weights are the item's vt; 2 + 2 B launches on `stream`,
+ *   no synchronisation.  Scores and probabilities are stored in `dtype` between the launches.  The workspace (16-byte aligned,
+ *   use_op_attention_gemm_workspace bytes; 0 for a shape the form does not run) holds, in `dtype`, the probabilities [B][N][N] at offset 0
+ *   and vt [B][C][N] at the next multiple of 256 bytes behind them: both can be read back after a synchronise.  USE_E_INVALID (nothing is
+ *   launched): a shape outside N > 512, N % 128 == 0, C % 128 == 0 (what the engine tests before it takes this form), a workspace too
+ *   small, an unknown dtype, a null pointer.
  * use_op_gn_finalize: GroupNorm totals (as accumulated in `stats`) of up to two concatenated sources -> coef[b][c] = (a, b).
  * use_op_gn_finalize_parts: the same with either form per source: totals st_i [B][C_i][2] (nt_i = 0), or nt_i > 0 per-workgroup partial
  *   totals pt_i [B][nt_i][C_i][2] (use_conv_op::stats_part) - integer sums, so the coefficients are those of the summed totals bit for
@@ -466,6 +474,9 @@ int use_op_conv_dev(const use_conv_op* c, int w_mode, void* work, size_t work_by
 int use_op_fir(const void* src, int dtype, const float* coef, int act, void* out_act, void* out_raw, int B, int H, int W, int C, int up,
                use_stream_t stream);
 int use_op_attention(const void* q, const void* k, const void* v, void* out, int dtype, int B, int N, int C, use_stream_t stream);
+size_t use_op_attention_gemm_workspace(int dtype, int B, int N, int C);
+int use_op_attention_gemm(const void* q, const void* k, const void* v, void* out, void* work, size_t work_bytes, int dtype, int B, int H, int W,
+                          int C, use_stream_t stream);
 int use_op_gn_finalize(const long long* st0, int C0, const long long* st1, int C1, const float* gamma, const float* beta, int groups,
                        int hw, float eps, float* coef, int B, use_stream_t stream);
 int use_op_gn_finalize_parts(const long long* st0, const long long* pt0, int nt0, int C0, const long long* st1, const long long* pt1, int nt1,
@@ -545,9 +556,8 @@ double use_flops_per_score(use_handle* h);   /* 2*MAC of the conv/linear layers 
  * it issues, in launch order; the list belongs to the plan and is replaced by the next evaluation (cleared where the debug tensors are).
  * No launch changes: the entries are filled from the very argument structs the launches take.  The activation arena is only reset at the
  * start of an evaluation, so after a synchronise every pointer below is still valid device memory and holds what that launch wrote
- * (exception: USE_TRACE_COMBINE_ADD rewrites its input in place).  Not recorded: the zeroing of the totals region at the start of an
- * evaluation (one launch; every totals pointer lies inside it), and the launches of the long-sequence attention path (N > 512 tokens:
- * transpose, per-item GEMMs, softmax rows) - its q / k / v / NIN_3 convolutions are.
+ * (exceptions: USE_TRACE_COMBINE_ADD and USE_TRACE_SOFTMAX_ROWS rewrite their input in place).  Not recorded: the zeroing of the totals
+ * region at the start of an evaluation (one launch; every totals pointer lies inside it).
  *
  * Tensors are NHWC; dims = (B, H, W, C) with B the items of the sub-batch, dtype = USE_PREC_* of the storage.  Complex64 tensors (the
  * evaluation's x, y, y2 and its output) are given as fp32 with C = 2.  Totals: [B][C][2] 64-bit fixed point (sum, sum of squares, each
@@ -575,10 +585,18 @@ double use_flops_per_score(use_handle* h);   /* 2*MAC of the conv/linear layers 
  *                                                                                                          params CB_*
  * USE_TRACE_SCORE_OUT   0: pyramid fp32                                    0: the evaluation's output      t (null: no division), t_stride, out_scale = sign;
  *                                                                                                          params W, B (output_layer)
+ * The GEMM form of the attention core (N > 512 tokens, use_op_attention_gemm), 2 + 2 B entries between the NIN_0..2 and the NIN_3 convolutions:
+ * USE_TRACE_TRANSPOSE   0: v [B,1,N,C]                                     0: vt [B,1,C,N]
+ * USE_TRACE_ATTN_GEMM   0: one item's operand [1,H,W,K], 1: its "weights"   0: the item's output slice     kernel (conv_choose's answer for this launch), out_scale,
+ *                       [1,1,Cout,K].  Scores: q and the item's keys       [1,H,W,Cout] (of the score     ntaps = 1, act = 0; no bias and no parameter: every
+ *                       (K = C, Cout = N); P.V: the item's probabilities   buffer; of the block's         operand is an activation.  One entry per launch: B
+ *                       and its slice of vt (K = N, Cout = C)              output)                        for the scores, the softmax, then B for P.V
+ * USE_TRACE_SOFTMAX_ROWS 0: the score buffer [B,N,1,N] (in place)          0: == in[0]
  * Parameter names are the reference state-dict keys (as use_expected_weight reports them); unused roles are null.  The strings belong
  * to the handle.  use_trace_count: entries of the current plan's last evaluation (0: none, or the trace was off), < 0: error. */
 enum { USE_TRACE_TEMB = 1, USE_TRACE_PACK_INPUT, USE_TRACE_CONV, USE_TRACE_FIR_DOWN, USE_TRACE_FIR_UP, USE_TRACE_GN_FINALIZE,
-       USE_TRACE_ATTN_FUSED, USE_TRACE_ATTN_CORE, USE_TRACE_COMBINE_ADD, USE_TRACE_SCORE_OUT };
+       USE_TRACE_ATTN_FUSED, USE_TRACE_ATTN_CORE, USE_TRACE_COMBINE_ADD, USE_TRACE_SCORE_OUT,
+       USE_TRACE_TRANSPOSE, USE_TRACE_ATTN_GEMM, USE_TRACE_SOFTMAX_ROWS };
 enum { USE_TP_W = 0, USE_TP_B, USE_TP_W2, USE_TP_B2, USE_TP_GN_W, USE_TP_GN_B, USE_TP_CB_W, USE_TP_CB_B, USE_TP_DENSE_W, USE_TP_DENSE_B,
        USE_TP_X0, USE_TP_X1, USE_TP_X2, USE_TP_X3, USE_TP_X4, USE_TP_X5, USE_TP_COUNT };
 typedef struct use_trace_tensor { const void* ptr; int dims[4]; int dtype; } use_trace_tensor;

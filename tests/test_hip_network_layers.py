@@ -11,7 +11,13 @@ option sets: "default" (every map is small: GroupNorm finalised inside the consu
 conv_v4_min_blocks 1: the 32x64 level as the benchmark's large maps - wide kernel, per-workgroup partial totals, gn_finalize_part,
 coefficient arrays into the convolutions).  fp32 storage sends every map of at most 4096 pixels to conv_sk, which only knows atomic
 totals: the fp32 workload case reads coefficient arrays but no kernel of it writes partial totals; that assertion is made in bf16 / fp16.
-The long-sequence attention path (N > 512 tokens) is out of scope: its launches are not traced and no case here reaches it.
+The long-sequence attention path (N > 512 tokens, launch_attention_gemm) has a network of its own, "refine_long": the unconditional
+2-channel generator with ch_mult (1, 2) on a 40 x 64 input (use_plan takes T' in multiples of 64, which rules out 32 x 80), two items; its
+bottleneck is 20 x 32 = 640 tokens of 256 channels, the smallest map that takes the form.  Its 2 + 2 B launches are traced as transpose /
+attn_gemm (one per item and GEMM) / softmax_rows and checked with the references of tests/test_hip_attention_gemm.py.  The softmax rewrites
+the scores in place: each score GEMM is issued again through use_op_conv on the operands the trace names and held to its bound, and
+use_op_softmax_rows of those scores must give the engine's probabilities bit for bit.  Four items in bf16 (2 + 2 sub-batches: the form on
+a secondary stream) equal the unsplit batch and the two-item evaluation bit for bit.
 
 Per launch (test_every_launch_holds_its_bound): inputs copied back as stored, the reference evaluated on them, every element of every
 stored output held to the operation's own bound.  Inline GroupNorm: coefficients from the very integers the consumer reads (partial
@@ -43,18 +49,23 @@ bound at the layer, bf16 / fp16, and in brackets the end-to-end error as a multi
     Combine bias omitted                                3.0 / 24         (4.3 / 30)
     activated FIR output into the shortcut              11 / 88          (9.2 / 65)
     the two skips of the coarsest level swapped         18 / 140         (17 / 123)
+and on the refine_long network (end to end: lp.refine_bound x 1.25; the unmutated walk: 0.38 / 0.22):
+    item 1's score GEMM on item 0's keys                6.5 / 52         (1.7 / 6.6)
+    item 1's P.V GEMM on item 0's slice of vt           83 / 648         (1.5 / 6.3)
 With these random weights and two far-apart times most mutants are gross end to end as well; the epsilon is not, and one partial of four
 exceeds the bf16 end-to-end bound by a factor of 2.3 only, with a quarter of the map missing from the statistics.  No arithmetic
 exemption was needed.  The swap of the skip tensors is made inside a level (its two skips have the same shape); across levels the shapes
 differ in this network, so that swap cannot be built.
 
-Measured on the MI355X, worst |err| / bound per entry kind over the nine cases (each case prints its own line): input convolution conv_in
+Measured on the MI355X, worst |err| / bound per entry kind over the nine cases of the 4-level networks (each case prints its own line): input convolution conv_in
 0.34 (fp32), conv_in_split 0.990 (bf16) / 0.937 (fp16), conv_generic on 8 channels 0.995 - store-bound kernels at the bottom of a binade,
 as in their own file; conv_sk 0.19, conv_v2 0.19, conv_v5 0.21, pyr_conv_ws 0.019, convolution + combine_add 0.15; res-block FIR 0.61
 (fp32) / 0.999 (16-bit, the store rounding), pyramid FIR 0.55; gn_finalize 0.22, gn_finalize_part 0.12; attn_fused 0.46, attention_kernel
 0.009; score_out 0.31, temb_dense 0.013, temb_mlp 0.002, pack_input exact; totals: conv_in 0.07, conv_in_split 0.10, conv_generic 0.06,
 conv_sk 0.12, conv_v2 0.15, conv_v5 0.13, attn_fused 0.36, combine_add 0.10.  End to end |err| / max: fp32 2.8e-5, bf16 1.7e-2 (6-channel
-2.6e-2), fp16 2.0e-3.  No composition error and no engine bug was found.  Every GPU case takes under 2 s, the CPU part about 25 s (the
+2.6e-2), fp16 2.0e-3.  The three refine_long cases, fp32 / bf16 / fp16: score GEMMs 0.004 / 0.025 / 0.025 (conv_sk in fp32, conv_generic in
+16 bit), softmax_rows 0.27 / 0.995 / 0.98, P.V GEMMs 0.14 / 0.50 / 0.50, transpose_nc exact, conv_generic (the 256-channel 1x1 NIN on a 640-pixel
+map, 16 bit) 0.25; end to end 1.3e-6 / 1.04e-2 / 1.5e-3.  No composition error and no engine bug was found.  Every GPU case takes under 2 s, the CPU part about 25 s (the
 mutation controls re-walk the network behind each mutated layer)."""
 import functools
 
@@ -63,10 +74,11 @@ import pytest
 import torch
 
 import lowprec as lp
-from test_hip_conv_kernels import DT_NAME, GN_EPS, SQRT1_2, UNIT, _bound, _check_stats, conv_reference, gn_coef_reference, q
+from test_hip_attention_gemm import UNDERFLOW, _score_gemm, expected_kernels
+from test_hip_conv_kernels import DT_NAME, GN_EPS, SQRT1_2, TD, UNIT, _bound, _check_stats, conv_reference, gn_coef_reference, q
 from test_hip_forward_kernels import (_combine_totals_ratio, _fused_totals_ratio, _ratio, attention_reference, attn_block_reference,
                                       combine_reference, dense_reference, fir_reference, gn_coef_from_totals, pack_reference,
-                                      score_out_reference, temb_reference)
+                                      score_out_reference, softmax_rows_reference, temb_reference)
 from test_hip_input_head_kernels import _finalize_ratios, _in_bound, _n_ser, _split_model, _totals_ratio
 
 NF, CH_MULT, NRB, NFREQ, TP, NB = 128, (1, 1, 2, 2), 1, 32, 64, 2
@@ -74,10 +86,27 @@ TS = (0.83, 0.21)
 GN_INLINE_DEFAULT = 128 * 160
 OPTSETS = {"default": {"gn_inline": GN_INLINE_DEFAULT, "conv_v4_min_blocks": 80}, "workload": {"gn_inline": 1024, "conv_v4_min_blocks": 1}}
 VARIANTS = {"score": dict(input_channels=4, conditional=True), "both": dict(input_channels=6, conditional=True),
-            "refine": dict(input_channels=2, conditional=False)}
+            "refine": dict(input_channels=2, conditional=False), "refine_long": dict(input_channels=2, conditional=False)}
+# "refine_long": two levels on a 40 x 64 input - the bottleneck is 20 x 32 = 640 tokens of 256 channels, the smallest map that takes the
+# GEMM form of the attention core (N > 512; use_plan takes T' in multiples of 64, which rules out a 32 x 80 input); every other variant:
+# CH_MULT on NFREQ x TP
+GEOM = {"refine_long": ((1, 2), 40, 64)}
+LONG = ("refine_long",)
+
+
+def _geom(variant):
+    """(ch_mult, n_freq, T')"""
+    return GEOM.get(variant, (CH_MULT, NFREQ, TP))
+
+
+def _is_refine(variant):
+    return not VARIANTS[variant]["conditional"]
+
+
 PREC = {"fp32": 0, "bf16": 1, "fp16": 2}
 CASES = [("score", p, o) for p in ("fp32", "bf16", "fp16") for o in ("default", "workload")] + \
-        [("both", "bf16", "workload"), ("refine", "fp32", "default"), ("refine", "bf16", "default")]
+        [("both", "bf16", "workload"), ("refine", "fp32", "default"), ("refine", "bf16", "default")] + \
+        [("refine_long", p, "default") for p in ("fp32", "bf16", "fp16")]
 CASE_IDS = ["-".join(c) for c in CASES]
 
 
@@ -87,16 +116,17 @@ CASE_IDS = ["-".join(c) for c in CASES]
 @functools.lru_cache(maxsize=None)
 def _state_dict(variant):
     from universal_speech_enhancement_amd.testing import weights as tw
-    return tw.make_state_dict(4321, nf=NF, ch_mult=CH_MULT, num_res_blocks=NRB, **VARIANTS[variant])
+    return tw.make_state_dict(4321, nf=NF, ch_mult=_geom(variant)[0], num_res_blocks=NRB, **VARIANTS[variant])
 
 
 @functools.lru_cache(maxsize=None)
 def _inputs(variant):
     """(x, y, y2, t): complex64 [B,1,F,T'] (y, y2 None where the network has no such input), t float32 [B] (None: unconditional)."""
     from universal_speech_enhancement_amd.testing import noise as tn
-    mk = lambda s: torch.from_numpy(tn.complex_normal(77, s, (NB, 1, NFREQ, TP))) * 0.5
+    _, nfreq, tp = _geom(variant)
+    mk = lambda s: torch.from_numpy(tn.complex_normal(77, s, (NB, 1, nfreq, tp))) * 0.5
     ic = VARIANTS[variant]["input_channels"]
-    return mk("x"), (mk("y") if ic >= 4 else None), (mk("y2") if ic == 6 else None), (torch.tensor(TS) if variant != "refine" else None)
+    return mk("x"), (mk("y") if ic >= 4 else None), (mk("y2") if ic == 6 else None), (torch.tensor(TS) if not _is_refine(variant) else None)
 
 
 @functools.lru_cache(maxsize=None)
@@ -108,8 +138,8 @@ def _oracle(variant):
     xin = torch.cat([v for v in (x, y, y2) if v is not None], 1).to(torch.complex128)
     taps = {}
     with torch.no_grad():
-        out = no.ncsnpp_forward(sd, xin, t.double() if t is not None else None, ch_mult=CH_MULT, num_res_blocks=NRB, taps=taps,
-                                discriminative=variant == "refine")
+        out = no.ncsnpp_forward(sd, xin, t.double() if t is not None else None, ch_mult=_geom(variant)[0], num_res_blocks=NRB, taps=taps,
+                                discriminative=_is_refine(variant))
     taps = {k: v.permute(0, 2, 3, 1).contiguous() for k, v in taps.items() if v is not None and v.dim() == 4}
     return torch.view_as_real(out[:, 0]).contiguous(), taps
 
@@ -242,6 +272,35 @@ def op_attn_core(qq, kk, vv, dt):
     return [(ref, (lambda got: _ratio(got, ref, part, dt if dt is not None else 0)), q(ref, dt))]
 
 
+def op_transpose(v):
+    """v [B,1,N,C] stored -> vt [B,1,C,N], bit for bit"""
+    want = v.transpose(2, 3).contiguous()
+    return [(want, (lambda got: 0.0 if torch.equal(got.double(), want) else float("inf")), want)]
+
+
+def op_attn_gemm(x, w, scale, dt):
+    """One GEMM of the long-sequence attention: x [1,H,W,K] and the "weights" w [Cout,K], both activations as stored; no bias."""
+    ref, S = conv_reference(x, None, 0, w, dt, scale=scale)
+    if dt is None:
+        return [(ref, None, ref)]
+    bound = _bound(ref, S, dt, dt, scale, x.shape[-1])
+    return [(ref, (lambda got: _worst0(got, ref, bound)), q(ref, dt))]
+
+
+def op_softmax_rows(x, dt):
+    """x [B,N,1,N]: the stored scores (bound: tests/test_hip_attention_gemm.py, "softmax")"""
+    ref, bound = softmax_rows_reference(x, dt)
+    if dt is None:
+        return [(ref, None, ref)]
+    full = UNIT[dt] * ref + bound + UNDERFLOW
+    return [(ref, (lambda got: _worst0(got, ref, full)), q(ref, dt))]
+
+
+def attention_gemm_eligible(N, Cc):
+    """attention_gemm_eligible of csrc/use_kernels.hip (N % 128 == 0 implies the K-chunk condition of either storage width)"""
+    return N > 512 and N % 128 == 0 and Cc % 128 == 0
+
+
 def op_combine(h, pyr, sd, p, dt, no_bias=False):
     """h [B,P,C] stored, pyr [B,P,8]"""
     ref, part = combine_reference(h, pyr, _weight(sd, p["cb_w"], pyr.shape[-1], h.shape[-1]), _vec(sd, p["cb_b"], h.shape[-1]), "bias" if no_bias else None)
@@ -280,6 +339,7 @@ class Walk:
         self.store = 0 if dt is None else dt
         ic = VARIANTS[variant]["input_channels"]
         self.pc, self.pcp, self.cond = ic, (8 if ic > 4 else 4), VARIANTS[variant]["conditional"]
+        self.ch_mult, self.nfreq, self.tp = _geom(variant)
         self.sign = sign
         self.layers, self.taps, self.mut_layer, self.mut_ratio = [], {}, None, None
         self.run()
@@ -445,7 +505,7 @@ class Walk:
         p = f"all_modules.{idx}"
         B, H, Wd, Cc = x.shape
         gn = p + ".GroupNorm_0"
-        if self.dt in (1, 2):                                 # the fused block (16-bit storage, C 256, N <= 96)
+        if self.dt in (1, 2) and Cc == 256 and H * Wd <= 96:  # the fused block (16-bit storage, C 256, N <= 96)
             params = {"gn_w": gn + ".weight", "gn_b": gn + ".bias", "w": p + ".NIN_0.W", "b": p + ".NIN_0.b", "x0": p + ".NIN_1.W", "x1": p + ".NIN_1.b",
                       "x2": p + ".NIN_2.W", "x3": p + ".NIN_2.b", "x4": p + ".NIN_3.W", "x5": p + ".NIN_3.b"}
             coef = self.coef_inline(x, None, gn)
@@ -455,6 +515,29 @@ class Walk:
                 return [(r[0].reshape(B, H, Wd, Cc), (lambda got: r[1](got.reshape(B, H * Wd, Cc))), r[2].reshape(B, H, Wd, Cc))]
             return self.emit("attn_fused", params, [(B, H, Wd, Cc)], fn, tap=f"attn.{idx}")[0]
         qkv = [self.conv(x, None, gn, 0, p + f".NIN_{k}.W", p + f".NIN_{k}.b", Cc) for k in range(3)]
+        if attention_gemm_eligible(H * Wd, Cc):               # launch_attention_gemm: transpose, B score GEMMs, softmax rows, B P.V GEMMs
+            N, dt = H * Wd, self.dt
+            qq, kk, vv = qkv
+            scale = float(np.float32(1.0) / np.sqrt(np.float32(Cc)))
+            vt = self.emit("transpose", {}, [(B, 1, Cc, N)], lambda: op_transpose(vv.reshape(B, 1, N, Cc)))[0]
+            sc = []
+            for b in range(B):
+                kb = kk[0 if (b and self.hit("keys_of_item_0")) else b].reshape(N, Cc)
+                was = self.pending_mut
+                sc.append(self.emit("attn_gemm", {}, [(1, H, Wd, N)], lambda: op_attn_gemm(qq[b:b + 1], kb, scale, dt))[0])
+                if was:
+                    self.mutated(sc[-1])
+            scores = torch.cat(sc).reshape(B, N, 1, N)
+            pr = self.emit("softmax_rows", {}, [(B, N, 1, N)], lambda: op_softmax_rows(scores, dt))[0]
+            outs = []
+            for b in range(B):
+                vb = vt[0 if (b and self.hit("vt_stale")) else b, 0]
+                was = self.pending_mut
+                outs.append(self.emit("attn_gemm", {}, [(1, H, Wd, Cc)], lambda: op_attn_gemm(pr[b].reshape(1, H, Wd, N), vb, 1.0, dt))[0])
+                if was:
+                    self.mutated(outs[-1])
+            a = torch.cat(outs)
+            return self.conv(a, None, None, 0, p + ".NIN_3.W", p + ".NIN_3.b", Cc, res=x, scale=SQRT1_2, tap=f"attn.{idx}")
 
         def fn():
             r = op_attn_core(*(v.reshape(B, H * Wd, Cc) for v in qkv), self.dt)[0]
@@ -467,7 +550,7 @@ class Walk:
         sd, dt, pcp, pc = self.sd, self.dt, self.pcp, self.pc
         x, y, y2, t = _inputs(self.variant)
         self.part_count = {}
-        L = len(CH_MULT)
+        L = len(self.ch_mult)
         # module indices as the reference numbers them (ncsnpp.py:181-316)
         m = 3 if self.cond else 1
         m_in = m
@@ -476,17 +559,17 @@ class Walk:
         plan, mm, in_ch, hs_c = [], m, NF, [NF]
         for lvl in range(L):
             for _ in range(NRB):
-                plan.append((mm, CH_MULT[lvl] * NF)); mm += 1; hs_c.append(CH_MULT[lvl] * NF)
+                plan.append((mm, self.ch_mult[lvl] * NF)); mm += 1; hs_c.append(self.ch_mult[lvl] * NF)
             if lvl != L - 1:
-                plan.append((mm, CH_MULT[lvl] * NF)); mm += 2; hs_c.append(CH_MULT[lvl] * NF)
+                plan.append((mm, self.ch_mult[lvl] * NF)); mm += 2; hs_c.append(self.ch_mult[lvl] * NF)
         plan.append((mm, hs_c[-1])); mm += 2
         plan.append((mm, hs_c[-1])); mm += 1
         for lvl in reversed(range(L)):
             for _ in range(NRB + 1):
-                plan.append((mm, CH_MULT[lvl] * NF)); mm += 1
+                plan.append((mm, self.ch_mult[lvl] * NF)); mm += 1
             mm += 2
             if lvl != 0:
-                plan.append((mm, CH_MULT[lvl] * NF)); mm += 1
+                plan.append((mm, self.ch_mult[lvl] * NF)); mm += 1
         self.dense_row, r0 = {}, 0
         for idx, oc in plan:
             self.dense_row[idx] = r0; r0 += oc
@@ -507,16 +590,16 @@ class Walk:
         def pack_fn():
             v = pack_reference(xs[0].reshape(-1, 2), None if xs[1] is None else xs[1].reshape(-1, 2), None if xs[2] is None else xs[2].reshape(-1, 2))
             if dt is None:                                    # (the unrounded walk: 2 v - 1 in float64, as the oracle; pack_input itself is fp32)
-                v = torch.cat([u.reshape(-1, 2).double() if u is not None else torch.full((NB * NFREQ * TP, 2), 0.5, dtype=torch.float64)
+                v = torch.cat([u.reshape(-1, 2).double() if u is not None else torch.full((NB * self.nfreq * self.tp, 2), 0.5, dtype=torch.float64)
                                for u in (xs[:2] if pcp == 4 else xs + [None])], -1) * 2.0 - 1.0
-            v = v.double().reshape(NB, NFREQ, TP, pcp)
+            v = v.double().reshape(NB, self.nfreq, self.tp, pcp)
             return [(v, (lambda got: 0.0 if torch.equal(got.double(), v) else float("inf")), v)]
-        x4 = self.emit("pack_input", {}, [(NB, NFREQ, TP, pcp)], pack_fn, tap="x4")[0]
+        x4 = self.emit("pack_input", {}, [(NB, self.nfreq, self.tp, pcp)], pack_fn, tap="x4")[0]
         hs = [self.conv(x4, None, None, 0, f"all_modules.{m_in}.weight", f"all_modules.{m_in}.bias", NF, parts=self.in_parts(), tap="h_in")]
         ipyr = x4
         in_ch = NF
         for lvl in range(L):
-            oc = CH_MULT[lvl] * NF
+            oc = self.ch_mult[lvl] * NF
             for _ in range(NRB):
                 hs.append(self.resblock(hs[-1], None, m, in_ch, oc)); m += 1; in_ch = oc
             if lvl != L - 1:
@@ -543,7 +626,7 @@ class Walk:
         hc = self.resblock(hc, None, m, in_ch, in_ch); m += 1
         pyr = None
         for lvl in reversed(range(L)):
-            oc = CH_MULT[lvl] * NF
+            oc = self.ch_mult[lvl] * NF
             for k in range(NRB + 1):
                 if lvl == L - 1 and k == 0 and self.hit("skip_swap"):   # the two skips of the coarsest level (same shape) in each other's place
                     hs[-1], hs[-2] = hs[-2], hs[-1]
@@ -563,7 +646,7 @@ class Walk:
         assert not hs
         B, H, Wd, _ = pyr.shape
         names = {"w": "output_layer.weight", "b": "output_layer.bias"}
-        tt = t if (t is not None and self.variant != "refine") else None
+        tt = t if (t is not None and not _is_refine(self.variant)) else None
         final = pyr
         self.out = self.emit("score_out", names, [(B, H, Wd, 2)], lambda: [
             (r[0].reshape(B, H, Wd, 2), (lambda got: r[1](got.reshape(B, H * Wd, 2))), r[2].reshape(B, H, Wd, 2))
@@ -571,7 +654,7 @@ class Walk:
 
     def in_parts(self):
         """partial totals of the input convolution on a large map: conv_in_split writes one per 8 x 16 tile"""
-        return ((NFREQ + 7) // 8) * ((TP + 15) // 16) if (self.dt in (1, 2) and self.pcp == 4 and NFREQ * TP > self.gn_inline) else 1
+        return ((self.nfreq + 7) // 8) * ((self.tp + 15) // 16) if (self.dt in (1, 2) and self.pcp == 4 and self.nfreq * self.tp > self.gn_inline) else 1
 
     def listing(self):
         return [(l["kind"], tuple(sorted(l["params"].items())), tuple(l["shapes"])) for l in self.layers]
@@ -579,7 +662,7 @@ class Walk:
 
 @functools.lru_cache(maxsize=None)
 def _walk(variant, dt, gn_inline=GN_INLINE_DEFAULT, compute=True):
-    return Walk(variant, dt, gn_inline, compute, sign=1.0 if variant == "refine" else -1.0)
+    return Walk(variant, dt, gn_inline, compute, sign=1.0 if _is_refine(variant) else -1.0)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -590,7 +673,7 @@ def test_walk_without_rounding_is_the_oracle(variant):
     """float64 against float64 (fp32 weights widened): the output and every tap to 1e-9 of the maximum."""
     w = _walk(variant, None)
     out, taps = _oracle(variant)
-    sign = 1.0 if variant == "refine" else -1.0
+    sign = 1.0 if _is_refine(variant) else -1.0
     worst = {"out": float((w.out - sign * out).abs().max() / out.abs().max())}
     for name, v in w.taps.items():
         want = taps[name]
@@ -620,27 +703,41 @@ def test_rounded_walk_holds_every_layer_bound_and_the_end_to_end_bound(dt):
 
 
 MUTANTS = ("eps", "partial", "inv_n", "temb_row", "scale_before_res", "shortcut_src", "combine_bias", "fir_act_raw", "skip_swap")
+LONG_MUTANTS = ("keys_of_item_0", "vt_stale")              # the GEMM form of the attention core: item 1 on item 0's keys / on item 0's slice of vt
+MUTANT_SETS = {"score": (1024, MUTANTS), "refine_long": (GN_INLINE_DEFAULT, LONG_MUTANTS)}
 
 
 @pytest.mark.parametrize("dt", [1, 2])
 def test_mutation_controls(dt):
     """One layer wrong at a time in the rounded walk (workload-like options: partial totals exist).  At its layer every mutant exceeds
     the per-element bound; end to end (printed, not asserted) most of them stay under lp.fwd_bound - what the existing tests allow."""
-    base = _walk("score", dt, 1024)
-    out, _ = _oracle("score")
+    _mutation_controls("score", dt)
+
+
+@pytest.mark.parametrize("dt", [1, 2])
+def test_mutation_controls_long_attention(dt):
+    """The same for the GEMM form of the attention core, on the two-level refine generator (end to end: lp.refine_bound)."""
+    _mutation_controls("refine_long", dt)
+
+
+def _mutation_controls(variant, dt):
+    gn_inline, names = MUTANT_SETS[variant]
+    base = _walk(variant, dt, gn_inline)
+    out, _ = _oracle(variant)
+    sign = 1.0 if _is_refine(variant) else -1.0
     mx = float(out.abs().max())
-    e2e0 = float((base.out + out).abs().max()) / mx
-    bound = lp.fwd_bound(DT_NAME[dt], 1.25)                    # (inputs other than the fixture's: factor 1.25, tests/lowprec.py)
-    print(f"[mut] {DT_NAME[dt]}: unmutated end-to-end {e2e0:.3e} = {e2e0 / bound:.2f} x lp.fwd_bound ({bound:.3e})")
+    e2e0 = float((base.out - sign * out).abs().max()) / mx
+    bound = (lp.refine_bound if _is_refine(variant) else lp.fwd_bound)(DT_NAME[dt], 1.25)      # (inputs other than the fixture's: factor 1.25, tests/lowprec.py)
+    print(f"[mut] {variant} {DT_NAME[dt]}: unmutated end-to-end {e2e0:.3e} = {e2e0 / bound:.2f} x the end-to-end bound ({bound:.3e})")
     bad = []
-    for name in MUTANTS:
-        w = Walk("score", dt, 1024, mut=name, base=base)
+    for name in names:
+        w = Walk(variant, dt, gn_inline, mut=name, base=base, sign=sign)
         assert w.mut_layer is not None, name
         i, ratio = w.mut_layer, w.mut_ratio                    # (a wrong input tensor: at the first convolution that reads it)
-        e2e = float((w.out + out).abs().max()) / mx
+        e2e = float((w.out - sign * out).abs().max()) / mx
         lay = w.layers[i]
         print(f"[mut] {DT_NAME[dt]} {name:17s} at layer {i:2d} ({lay['kind']} {lay['params'].get('w', lay['params'].get('gn_w', ''))}): |err| / bound {ratio:9.2f} | "
-              f"end to end {e2e:.3e} = {e2e / bound:.2f} x lp.fwd_bound -> {'MISSED' if e2e < bound else 'caught'} by the end-to-end bound")
+              f"end to end {e2e:.3e} = {e2e / bound:.2f} x the bound -> {'MISSED' if e2e < bound else 'caught'} by the end-to-end bound")
         if not ratio > 1.0:
             bad.append((name, ratio))
     assert not bad, bad
@@ -670,21 +767,27 @@ def _fetch_i64(e, ptr, shape):
     return torch.from_numpy(e.read_device(ptr, int(np.prod(shape)), "<i8").copy()).reshape(*shape)
 
 
+def _engine(variant, prec):
+    from universal_speech_enhancement_amd.hip_engine import HipScoreEngine
+    v = VARIANTS[variant]
+    ch_mult, nfreq, _ = _geom(variant)
+    e = HipScoreEngine(nf=NF, ch_mult=ch_mult, num_res_blocks=NRB, n_freq=nfreq, precision=prec, input_channels=v["input_channels"],
+                       conditional=v["conditional"], scale_by_sigma=v["conditional"])
+    e.load_state_dict(_state_dict(variant))
+    return e
+
+
 @functools.lru_cache(maxsize=None)
 def _case(variant, prec, optset):
     """One evaluation with the trace on: (trace entries with every named tensor copied to the host, output [B,F,T,2], device inputs)."""
-    from universal_speech_enhancement_amd.hip_engine import HipScoreEngine
-    v = VARIANTS[variant]
     x, y, y2, t = _inputs(variant)
     try:
         for k, val in OPTSETS[optset].items():
             _set_option(k, val)
         _set_option("trace", 1)
-        e = HipScoreEngine(nf=NF, ch_mult=CH_MULT, num_res_blocks=NRB, n_freq=NFREQ, precision=prec, input_channels=v["input_channels"],
-                           conditional=v["conditional"], scale_by_sigma=v["conditional"])
-        e.load_state_dict(_state_dict(variant))
+        e = _engine(variant, prec)
         dx = [None if a is None else a.cuda().contiguous() for a in (x, y, y2)]
-        if variant == "refine":
+        if _is_refine(variant):
             out = e.forward(dx[0])
         else:
             out = e.score(dx[0], dx[1], t.cuda(), dx[2])
@@ -732,7 +835,11 @@ def test_every_launch_holds_its_bound(variant, prec, optset):
     kernels = {e["kernel"] for e in tr}
     kinds = [e["kind"] for e in tr]
     # the kernels the case is meant to reach did run
-    if dt == 0:
+    if variant in LONG:                                        # (no map of at most 320 pixels: conv_sk takes nothing in 16-bit storage)
+        assert {"transpose_nc", "softmax_rows"} <= kernels and not kernels & {"attention", "attn_fused"}, kernels
+        assert kinds.count("attn_gemm") == 2 * NB and kinds.count("transpose") == 1 and kinds.count("softmax_rows") == 1
+        assert ({"conv_sk", "conv_in"} <= kernels) if dt == 0 else ("conv_v2" in kernels and "conv_sk" not in kernels), kernels
+    elif dt == 0:
         assert {"conv_sk", "conv_in", "attention"} <= kernels, kernels
     else:
         assert "attn_fused" in kernels and "conv_sk" in kernels, kernels
@@ -745,7 +852,7 @@ def test_every_launch_holds_its_bound(variant, prec, optset):
         assert any(e["kind"] == "conv" and e["coef"] for e in tr), "no convolution read a coefficient array"
     else:
         assert not any(e["kind"] == "conv" and e["coef"] for e in tr)
-    assert ("combine_add" in kinds) == (variant == "both") and ("temb" in kinds) == (variant != "refine")
+    assert ("combine_add" in kinds) == (variant == "both") and ("temb" in kinds) == (not _is_refine(variant))
     combined = {e["out"][0][0]: e for e in tr if e["kind"] == "combine_add"}
     worst = {}
 
@@ -825,12 +932,44 @@ def test_every_launch_holds_its_bound(variant, prec, optset):
             B, H, Wd, Cc = ins[0].shape
             r = op_attn_core(*(v.double().reshape(B, H * Wd, Cc) for v in ins[:3]), dt)[0]
             note("attention", r[1](outs[0].reshape(B, H * Wd, Cc)))
+        elif kind == "transpose":
+            assert e["in"][0][1][2:] == e["out"][0][1][:1:-1] and e["in"][0][0] == next(u for u in tr if u["params"].get("w", "").endswith(".NIN_2.W"))["out"][0][0]
+            note("transpose_nc", op_transpose(ins[0].double())[0][1](outs[0]))
+        elif kind == "attn_gemm":
+            _, H, Wd, K = ins[0].shape
+            cout = outs[0].shape[-1]
+            assert e["ntaps"] == 1 and e["act"] == 0 and ins[1].shape == (1, 1, cout, K) and not e["params"], (e["ntaps"], e["act"], ins[1].shape)
+            is_scores = K != H * Wd
+            assert e["kernel"] == expected_kernels(dt, H * Wd, cout if K == H * Wd else K)[0 if is_scores else 1], e["kernel"]
+            if is_scores:
+                # the softmax has rewritten this launch's output: the launch again through use_op_conv on the operands it read (as
+                # tests/test_hip_attention_gemm.py does), tied to the engine's own by the softmax entry below (bit for bit)
+                assert e["out_scale"] == float(np.float32(1.0) / np.sqrt(np.float32(K)))
+                got = _score_gemm(ins[0].cuda(), ins[1][0, 0].double(), H, Wd, dt).cpu().reshape(1, H, Wd, cout)
+                e["scores_t"] = got
+            else:
+                assert e["out_scale"] == 1.0
+                got = outs[0]
+            note("attn_gemm:" + ("scores" if is_scores else "pv"), op_attn_gemm(ins[0].double(), ins[1][0, 0].double(), e["out_scale"], dt)[0][1](got))
+        elif kind == "softmax_rows":
+            from test_hip_forward_kernels import _lib, _ok, _p, _stream
+            B, N = outs[0].shape[:2]
+            assert e["in"][0] == e["out"][0]
+            gem = [u for u in tr if u["kind"] == "attn_gemm" and "scores_t" in u]
+            es = 4 if dt == 0 else 2
+            assert [u["out"][0][0] for u in gem] == [e["out"][0][0] + b * N * N * es for b in range(B)], "the score GEMMs do not write the items' slices of this buffer"
+            scores = torch.cat([u["scores_t"] for u in gem]).reshape(B, N, 1, N)
+            d = scores.cuda().contiguous()
+            _ok(_lib().lib().use_op_softmax_rows(_p(d), dt, B * N, N, _stream()), "use_op_softmax_rows")
+            torch.cuda.synchronize()
+            assert torch.equal(d.cpu(), outs[0]), "the score GEMMs through use_op_conv do not reproduce the engine's probabilities bit for bit"
+            note("softmax_rows", op_softmax_rows(scores.double(), dt)[0][1](outs[0]))
         elif kind == "combine_add":
             B, H, Wd, Cc = outs[0].shape
             note("totals:combine_add", _combine_totals_ratio(e["totals_out_t"], outs[0].reshape(B, H * Wd, Cc), H * Wd))
         elif kind == "score_out":
             B, H, Wd, pcq = ins[0].shape
-            assert (e["t"] is None or e["t"] == 0) == (variant == "refine") and e["out_scale"] == (1.0 if variant == "refine" else -1.0)
+            assert (e["t"] is None or e["t"] == 0) == _is_refine(variant) and e["out_scale"] == (1.0 if _is_refine(variant) else -1.0)
             r = op_score_out(ins[0].double().reshape(B, H * Wd, pcq), e["t_t"], sd, p, e["out_scale"])[0]
             note("score_out", r[1](outs[0].reshape(B, H * Wd, 2)))
             assert torch.equal(outs[0].reshape(c["out"].shape), c["out"]), "the traced output is not what the evaluation returned"
@@ -840,10 +979,10 @@ def test_every_launch_holds_its_bound(variant, prec, optset):
     assert all(v <= 1.0 for v in worst.values()), {k: v for k, v in worst.items() if not v <= 1.0}
     # end to end, as the existing tests hold it
     out, _ = _oracle(variant)
-    sign = 1.0 if variant == "refine" else -1.0
+    sign = 1.0 if _is_refine(variant) else -1.0
     err = float((c["out"].double() - sign * out).abs().max() / out.abs().max())
     print(f"[measured] {variant}-{prec}-{optset}: end-to-end |err| / max {err:.3e}")
-    assert err < (5e-4 if dt == 0 else (lp.refine_bound(prec, 1.25) if variant == "refine" else lp.fwd_bound(prec, 1.25)))
+    assert err < (5e-4 if dt == 0 else (lp.refine_bound(prec, 1.25) if _is_refine(variant) else lp.fwd_bound(prec, 1.25)))
 
 
 @pytest.mark.gpu
@@ -867,10 +1006,16 @@ def _labels(c):
     """Trace -> (label per entry, {label: labels of what it reads}) with the finalise launches dropped and the attention block collapsed."""
     tr = c["trace"]
     writer = dict((p, "input:" + n) for p, n in c["evin"].items())
-    graph, nfir = {}, {}
+    graph, nfir, spans = {}, {}, []
+
+    def source(s, sliced):
+        """the label of what wrote the tensor at s[0]; sliced (the per-item GEMMs of the long attention): of the tensor s lies inside"""
+        if s[0] in writer or not sliced:
+            return writer[s[0]]
+        return next(lab for lo, hi, lab in spans if lo <= s[0] < hi)
     for e in tr:
         p = e["params"]
-        attn = e["kind"] in ("attn_fused", "attn_core") or ".NIN_" in p.get("w", "")
+        attn = e["kind"] in ("attn_fused", "attn_core", "transpose", "attn_gemm", "softmax_rows") or ".NIN_" in p.get("w", "")
         if e["kind"] == "gn_finalize":
             continue
         if attn:
@@ -880,7 +1025,7 @@ def _labels(c):
             label = f"{e['kind']}({src})"
         else:
             label = e["kind"] + ":" + p.get("w", p.get("cb_w", ""))
-        srcs = tuple(None if s is None else writer[s[0]] for s in e["in"])
+        srcs = tuple(None if s is None else source(s, e["kind"] == "attn_gemm") for s in e["in"])
         if attn:
             srcs = tuple(s for s in srcs if s is not None and not s.startswith("attn"))
             graph[label] = tuple(sorted(set(graph.get(label, ()) + srcs)))
@@ -890,6 +1035,7 @@ def _labels(c):
         for k, s in enumerate(e["out"]):
             if s is not None:
                 writer[s[0]] = label + (f"[{k}]" if e["kind"] in ("fir_down", "fir_up") else "")
+                spans.append((s[0], s[0] + int(np.prod(s[1])) * (4 if s[2] == 0 else 2), writer[s[0]]))
     return graph
 
 
@@ -900,6 +1046,11 @@ def test_wiring_graph_is_the_same_in_every_mode():
     assert len(first) > 30
     for k, g in graphs.items():
         assert g == first, (k, {n: (g.get(n), first.get(n)) for n in set(g) | set(first) if g.get(n) != first.get(n)})
+    # the GEMM form of the attention core collapses to the same node: one "attn" that reads the block in front of it and nothing else
+    longs = {p: _labels(_case("refine_long", p, "default")) for p in ("fp32", "bf16", "fp16")}
+    for k, g in longs.items():
+        assert g == longs["fp32"], (k, {n: (g.get(n), longs["fp32"].get(n)) for n in set(g) | set(longs["fp32"]) if g.get(n) != longs["fp32"].get(n)})
+    assert len(longs["fp32"]["attn"]) == 1 and longs["fp32"]["attn"][0].startswith("conv:") and len(first["attn"]) == 1, (longs["fp32"]["attn"], first["attn"])
 
 
 @pytest.mark.gpu
@@ -908,14 +1059,35 @@ def test_trace_is_complete(variant, prec, optset):
     c = _case(variant, prec, optset)
     written = dict((p, -1) for p in c["evin"])
     used, wcount = set(), {}
+    spans, nwrites = [], {}                                    # (byte range of every written tensor; writes per buffer of the long attention)
+    nbytes = lambda s: int(np.prod(s[1])) * (4 if s[2] == 0 else 2)
+
+    def inside(s):
+        """a per-item slice (the GEMMs of the long attention): wholly inside one tensor an earlier launch wrote"""
+        return any(lo <= s[0] and s[0] + nbytes(s) <= hi for lo, hi in spans)
     for i, e in enumerate(c["trace"]):
         if e["kind"] != "gn_finalize":                         # (a finalise launch names the maps whose totals it reads, and reads the totals alone)
             for s in e["in"]:
-                assert s is None or s[0] in written, (i, e["kind"], "reads what no earlier launch wrote")
+                assert s is None or s[0] in written or (e["kind"] == "attn_gemm" and inside(s)), (i, e["kind"], "reads what no earlier launch wrote")
         for s in e["out"]:
             if s is not None:
-                assert s[0] not in written or e["kind"] == "combine_add", (i, e["kind"], "a second writer")
+                assert s[0] not in written or e["kind"] in ("combine_add", "softmax_rows"), (i, e["kind"], "a second writer")
+                assert e["kind"] in ("combine_add", "softmax_rows") or not any(lo < s[0] + nbytes(s) and s[0] < hi for lo, hi in spans), (i, e["kind"], "overlaps a written tensor")
                 written[s[0]] = i
+                spans.append((s[0], s[0] + nbytes(s)))
+        if e["kind"] == "softmax_rows":                        # in place: every item's slice written once (its score GEMM) and rewritten here, once
+            lo, hi = e["out"][0][0], e["out"][0][0] + nbytes(e["out"][0])
+            B, N = e["out"][0][1][:2]
+            gem = [u["out"][0] for u in c["trace"][:i] if u["kind"] == "attn_gemm" and lo <= u["out"][0][0] < hi]
+            assert sorted(g[0] for g in gem) == [lo + b * (hi - lo) // B for b in range(B)] and all(nbytes(g) == (hi - lo) // B for g in gem), "sc is not written once"
+            assert not any(u["kind"] == "attn_gemm" and lo <= u["out"][0][0] < hi for u in c["trace"][i + 1:]), "sc is written after the softmax"
+            nwrites["sc"] = nwrites.get("sc", 0) + 1
+        if e["kind"] == "transpose":
+            nwrites["vt"] = nwrites.get("vt", 0) + 1
+            lo, hi = e["out"][0][0], e["out"][0][0] + nbytes(e["out"][0])
+            readers = [u for u in c["trace"][i + 1:] if u["kind"] == "attn_gemm" and lo <= u["in"][1][0] < hi]
+            B = e["out"][0][1][0]
+            assert [u["in"][1][0] for u in readers] == [lo + b * (hi - lo) // B for b in range(B)], "the P.V GEMMs do not read the items' slices of vt"
         for tot, part in zip(e["totals_in"], e["part_in"]):     # (given partial totals the launch reads those, not the totals pointer beside them)
             assert not (part or tot) or (part or tot) in written, (i, e["kind"], "totals nobody wrote")
         for tot in (e["totals_out"], e["part_out"], e["coef_out"]):
@@ -927,8 +1099,9 @@ def test_trace_is_complete(variant, prec, optset):
             n = e["params"].get(role)
             if n and e["kind"] in ("conv", "attn_fused", "combine_add", "score_out"):
                 wcount[n] = wcount.get(n, 0) + 1
+    assert nwrites == ({"sc": 1, "vt": 1} if variant in LONG else {}), nwrites
     expected = set(c["expected"])
-    if variant == "refine":                                    # unconditional: the module list has them, no launch reads them
+    if _is_refine(variant):                                    # unconditional: the module list has them, no launch reads them
         unused = expected - used
         assert unused == {"all_modules.0.W"} | {n for n in expected if ".Dense_0." in n}, unused
         expected -= unused
@@ -938,7 +1111,7 @@ def test_trace_is_complete(variant, prec, optset):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("variant,optset", [("score", "default"), ("score", "workload"), ("refine", "default")])
+@pytest.mark.parametrize("variant,optset", [("score", "default"), ("score", "workload"), ("refine", "default"), ("refine_long", "default")])
 def test_fp32_traced_outputs_are_the_oracles_taps(variant, optset):
     c = _case(variant, "fp32", optset)
     _, taps = _oracle(variant)
@@ -967,12 +1140,32 @@ def test_fp32_traced_outputs_are_the_oracles_taps(variant, optset):
 @pytest.mark.gpu
 @pytest.mark.parametrize("prec", ["fp32", "bf16", "fp16"])
 def test_trace_changes_no_bit_and_is_empty_when_off(prec):
-    from universal_speech_enhancement_amd.hip_engine import HipScoreEngine
-    x, y, _, t = _inputs("score")
-    on = _case("score", prec, "default")["out"]
-    e = HipScoreEngine(nf=NF, ch_mult=CH_MULT, num_res_blocks=NRB, n_freq=NFREQ, precision=prec)
-    e.load_state_dict(_state_dict("score"))
-    off = _cplx(e.score(x.cuda(), y.cuda(), t.cuda()).cpu())
-    assert e.trace() == []
-    e.close()
-    assert torch.equal(on, off)
+    for variant in ("score", "refine_long"):
+        x, y, _, t = _inputs(variant)
+        on = _case(variant, prec, "default")["out"]
+        e = _engine(variant, prec)
+        off = _cplx((e.forward(x.cuda()) if _is_refine(variant) else e.score(x.cuda(), y.cuda(), t.cuda())).cpu())
+        assert e.trace() == [], variant
+        e.close()
+        assert torch.equal(on, off), variant
+
+
+@pytest.mark.gpu
+def test_long_attention_on_a_secondary_stream_is_bit_identical():
+    """bf16, four items: 2 + 2 sub-batches (the second runs the GEMM form on its own stream and in its own arena) against the same batch
+    unsplit, and its items 0 / 1 against the two-item evaluation of the cases above."""
+    from universal_speech_enhancement_amd.testing import noise as tn
+    x = _inputs("refine_long")[0]
+    x4 = torch.cat([x, torch.from_numpy(tn.complex_normal(78, "x", tuple(x.shape))) * 0.5]).cuda().contiguous()
+    outs = {}
+    try:
+        for n in (-1, 0):
+            _set_option("subbatch", n)
+            e = _engine("refine_long", "bf16")
+            outs[n] = _cplx(e.forward(x4).cpu())
+            e.close()
+    finally:
+        _set_option("subbatch", -1)
+    assert torch.equal(outs[-1], outs[0]), "2 + 2 sub-batches differ from the unsplit batch"
+    assert torch.equal(outs[-1][:NB], _case("refine_long", "bf16", "default")["out"]), "items 0 / 1 of the four differ from the two-item evaluation"
+    assert not torch.equal(outs[-1][:NB], outs[-1][NB:])

@@ -113,10 +113,12 @@ def test_lsgan_refine_generator_matches_reference(golden_dir, prec, tol, tol_wav
         w.net(torch.from_numpy(g["x"]).cuda().repeat(1, 2, 1, 1))   # a discriminative network takes Y alone
 
 
-@pytest.mark.parametrize("prec,tol", [("fp32", 5e-4), ("bf16", lp.refine_bound("bf16", 1.25))])   # bf16: 1.25 x the reference's own error on this input (tests/lowprec.py)
+@pytest.mark.parametrize("prec,tol", [("fp32", 5e-4), ("bf16", lp.refine_bound("bf16", 1.25)),   # bf16: 1.25 x the reference's own error on this input (tests/lowprec.py)
+                                      ("fp16", lp.refine_bound("fp16", 1.25))])  # fp16: the bf16 figure / 4 (tests/lowprec.py), x 1.25
 def test_refine_generator_long_sequence_attention(prec, tol):
     """T' = 128: the bottleneck of the 4-level refine generator is 64 x 16 = 1024 tokens, which takes the GEMM form of the
-    attention core (scores and P.V as implicit GEMMs on conv_kernel + row softmax).  Against the CPU oracle."""
+    attention core (scores and P.V as implicit GEMMs + row softmax; fp32: both GEMMs on conv_sk, 16 bit: on conv_kernel; stage by stage
+    in tests/test_hip_attention_gemm.py).  Against the CPU oracle."""
     from universal_speech_enhancement_amd.sgmse.backbones.ncsnpp import NCSNpp
     sd_np = tw.make_state_dict(4321, **tw.REFINE)
     sd = {k: torch.from_numpy(v) for k, v in sd_np.items()}

@@ -53,7 +53,7 @@ class UseTraceTensor(C.Structure):
 
 
 TRACE_KINDS = {1: "temb", 2: "pack_input", 3: "conv", 4: "fir_down", 5: "fir_up", 6: "gn_finalize", 7: "attn_fused", 8: "attn_core",
-               9: "combine_add", 10: "score_out"}                       # USE_TRACE_*
+               9: "combine_add", 10: "score_out", 11: "transpose", 12: "attn_gemm", 13: "softmax_rows"}     # USE_TRACE_*
 TRACE_PARAMS = ("w", "b", "w2", "b2", "gn_w", "gn_b", "cb_w", "cb_b", "dense_w", "dense_b", "x0", "x1", "x2", "x3", "x4", "x5")   # USE_TP_*
 
 
@@ -150,6 +150,8 @@ SYMBOLS = {
     "use_op_conv_dev": (_i, [C.POINTER(UseConvOp), _i, _vp, C.c_size_t, _vp]),
     "use_op_fir": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "use_op_attention": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "use_op_attention_gemm_workspace": (C.c_size_t, [_i, _i, _i, _i]),
+    "use_op_attention_gemm": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_size_t, _i, _i, _i, _i, _i, _vp]),
     "use_op_gn_finalize": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _f, _vp, _i, _vp]),
     "use_op_gn_finalize_parts": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _f, _vp, _i, _vp]),
     "use_op_attn_block": (_i, [_vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),

@@ -680,6 +680,29 @@ struct Fwd {
         return conv(hcur, nullptr, &r.gn1, 1, r.c1, -1, &x, rs, pyr, cb, dt, true);
     }
 
+    // the trace entries of the GEMM form of the attention core (launch_attention_gemm calls this in front of each of its launches): a
+    // GEMM's from the ConvArgs it is about to be launched with and the very conv_choose(conv_desc(p)) launch_conv evaluates
+    struct AttnGemmTrace { Fwd* f; int N, C, dt; };
+    static void trace_attn_gemm(void* ctx, int stage, const ConvArgs* p, const void* in, const void* out) {
+        const AttnGemmTrace& c = *(const AttnGemmTrace*)ctx;
+        Fwd& f = *c.f;
+        use_trace_entry e{};
+        if (stage == ATTN_GEMM_TRANSPOSE) {
+            e = trace_new(USE_TRACE_TRANSPOSE, "transpose_nc");
+            e.in[0] = trace_tensor(in, f.B, 1, c.N, c.C, c.dt); e.out[0] = trace_tensor(out, f.B, 1, c.C, c.N, c.dt);
+        } else if (stage == ATTN_GEMM_SOFTMAX) {
+            e = trace_new(USE_TRACE_SOFTMAX_ROWS, "softmax_rows");
+            e.in[0] = e.out[0] = trace_tensor(out, f.B, c.N, 1, c.N, c.dt);
+        } else {
+            e = trace_new(USE_TRACE_ATTN_GEMM, conv_kernel_name(conv_choose(conv_desc(*p)).k));
+            e.in[0] = trace_tensor(p->src0, 1, p->H, p->W, p->C0, p->in_dtype);
+            e.in[1] = trace_tensor(p->w, 1, 1, p->Cout, p->C0, p->in_dtype);
+            e.out[0] = trace_tensor(p->out, 1, p->H, p->W, p->Cout, p->out_dtype);
+            e.act = p->act; e.out_scale = p->out_scale; e.ntaps = p->ntaps;
+        }
+        f.pl.trace.push_back(e);
+    }
+
     // AttnBlockpp.forward (reference layerspp.py:77-93)
     Act attention(const Act& x, const AttnW& aw) {
         const int dt = h->act_dtype;
@@ -714,34 +737,15 @@ struct Fwd {
         Act v = conv(x, nullptr, &aw.gn, 0, aw.v, -1, nullptr, 1.f, nullptr, nullptr, dt, false);
         Act a = new_act(x.C, x.H, x.W, dt, false);
         const int N = x.H * x.W;
-        const int ck = dt == DT_F32 ? 32 : 64;
-        if (N > 512 && N % 128 == 0 && x.C % 128 == 0 && N % ck == 0) {
-            // long sequences (64x80 bottleneck of the refine generator): per batch item two implicit GEMMs on conv_kernel.
-            // The key tensor [N][C] already is a packed 1x1 weight [Cout = N][1][Cin = C]; v^T plays that part for P.V
+        if (attention_gemm_eligible(dt, N, x.C)) {
+            // long sequences (64x80 bottleneck of the refine generator): per batch item two implicit GEMMs on the kernel conv_choose
+            // answers for each (launch_attention_gemm, use_kernels.hip)
             const size_t es = dtype_size(dt);
             char* sc = (char*)arena->alloc((size_t)B * N * N * es);           // scores -> probabilities, [B][N][N]
             char* vt = (char*)arena->alloc((size_t)B * x.C * N * es);         // [B][C][N]
             if (!pl.dry) {
-                launch_transpose_nc(v.p, vt, dt, B, N, x.C, s);
-                for (int b = 0; b < B; ++b) {
-                    ConvArgs p{};
-                    p.src0 = (char*)q.p + (size_t)b * N * x.C * es; p.C0 = x.C; p.in_dtype = dt;
-                    p.w = (char*)k.p + (size_t)b * N * x.C * es; p.cout_pad = N;
-                    p.out_scale = 1.0f / std::sqrt((float)x.C);               // int(C) ** -0.5 (layerspp.py:84)
-                    p.out = sc + (size_t)b * N * N * es; p.out_dtype = dt;
-                    p.B = 1; p.H = x.H; p.W = x.W; p.Cout = N; p.ntaps = 1;
-                    launch_conv(p, s);
-                }
-                launch_softmax_rows(sc, dt, (long)B * N, N, s);
-                for (int b = 0; b < B; ++b) {
-                    ConvArgs p{};
-                    p.src0 = sc + (size_t)b * N * N * es; p.C0 = N; p.in_dtype = dt;
-                    p.w = vt + (size_t)b * x.C * N * es; p.cout_pad = x.C;
-                    p.out_scale = 1.f;
-                    p.out = (char*)a.p + (size_t)b * N * x.C * es; p.out_dtype = dt;
-                    p.B = 1; p.H = x.H; p.W = x.W; p.Cout = x.C; p.ntaps = 1;
-                    launch_conv(p, s);
-                }
+                AttnGemmTrace tc{this, N, x.C, dt};
+                launch_attention_gemm(q.p, k.p, v.p, a.p, sc, vt, dt, B, x.H, x.W, x.C, s, (g_trace && primary) ? &trace_attn_gemm : nullptr, &tc);
             }
         } else if (!pl.dry) {
             if (g_trace && primary) {
@@ -2532,6 +2536,29 @@ int use_op_attention(const void* q, const void* k, const void* v, void* out, int
     if ((size_t)(C + N) * 4 + 16 > OP_LDS_DEFAULT)
         return fail(USE_E_INVALID, "use_op_attention: (C + N) * 4 = %zu bytes of LDS per row, more than a launch gets", (size_t)(C + N) * 4);
     launch_attention(q, k, v, out, dtype, B, N, C, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return USE_OK;
+}
+// The GEMM form of the same core (launch_attention_gemm, the engine's path above 512 tokens) in a caller-provided workspace: the scores /
+// probabilities [B][N][N], then v^T [B][C][N], both in `dtype`; the second starts 256-byte aligned
+static size_t attn_gemm_vt_offset(int dtype, int B, int N) { return ((size_t)B * N * N * dtype_size(dtype) + 255) / 256 * 256; }
+static bool attn_gemm_shape_ok(int dtype, int B, int N, int C) {
+    return op_dtype_ok(dtype) && B >= 1 && B <= 65535 && N >= 1 && C >= 1 && (long long)B * N <= 0x7fffffffLL && attention_gemm_eligible(dtype, N, C);
+}
+size_t use_op_attention_gemm_workspace(int dtype, int B, int N, int C) {
+    if (!attn_gemm_shape_ok(dtype, B, N, C)) return 0;
+    return attn_gemm_vt_offset(dtype, B, N) + (size_t)B * C * N * dtype_size(dtype);
+}
+int use_op_attention_gemm(const void* q, const void* k, const void* v, void* out, void* work, size_t work_bytes, int dtype, int B, int H, int W,
+                          int C, use_stream_t stream) {
+    if (!q || !k || !v || !out || !work || H < 1 || W < 1 || (long long)H * W > 0x7fffffffLL) return fail(USE_E_INVALID, "use_op_attention_gemm: bad argument");
+    if (!op_dtype_ok(dtype)) return fail(USE_E_INVALID, "use_op_attention_gemm: bad dtype %d", dtype);
+    const int N = H * W;
+    if (!attn_gemm_shape_ok(dtype, B, N, C))
+        return fail(USE_E_INVALID, "use_op_attention_gemm: the GEMM form runs N = H W > 512 tokens with N %% 128 == 0 and C %% 128 == 0 (B %d, N %d, C %d)", B, N, C);
+    if (work_bytes < use_op_attention_gemm_workspace(dtype, B, N, C)) return fail(USE_E_INVALID, "use_op_attention_gemm: workspace too small");
+    if ((uintptr_t)work % 16) return fail(USE_E_INVALID, "use_op_attention_gemm: the workspace must be 16-byte aligned");
+    launch_attention_gemm(q, k, v, out, work, (char*)work + attn_gemm_vt_offset(dtype, B, N), dtype, B, H, W, C, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return USE_OK;
 }

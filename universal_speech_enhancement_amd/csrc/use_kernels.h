@@ -220,9 +220,21 @@ struct AttnArgs {
 bool attn_fused_eligible(int dtype, int N, int C);
 void launch_attn_fused(const AttnArgs& a, int dtype, int B, hipStream_t s);
 
-// helpers of the long-sequence attention path (two implicit GEMMs on conv_kernel, see Fwd::attention)
+// helpers of the long-sequence attention path (launch_attention_gemm below)
 void launch_softmax_rows(void* x, int dtype, long rows, int cols, hipStream_t s);            // in place, over the last axis
 void launch_transpose_nc(const void* in, void* out, int dtype, int B, int N, int C, hipStream_t s);   // [B][N][C] -> [B][C][N]
+// The attention core of a long token sequence (N = H * W > 512: the 64x80 bottleneck of the refine generator) as two implicit GEMMs per
+// item through launch_conv, in 2 + 2 B launches: vt = v^T; per item scores = conv1x1(q; weights = the item's keys [N][C], out_scale C^-0.5)
+// -> sc; softmax over the B N rows of sc in place; per item out = conv1x1(sc; weights = the item's vt [C][N]).  q / k / v / out [B][N][C],
+// sc [B][N][N] and vt [B][C][N] caller-owned, all in `dtype`: scores and probabilities are stored in the activation type between the
+// launches.  The kernel of each GEMM is conv_choose's answer for it (fp32 storage: conv_sk while N <= 4096 and K <= 1024, else
+// conv_kernel; 16-bit storage: conv_kernel).  note (optional): called in front of every launch with its stage, the ConvArgs of a GEMM
+// (else null) and what the launch reads / writes - the engine's launch trace.
+bool attention_gemm_eligible(int dtype, int N, int C);
+enum { ATTN_GEMM_TRANSPOSE, ATTN_GEMM_SCORES, ATTN_GEMM_SOFTMAX, ATTN_GEMM_PV };
+typedef void (*AttnGemmNote)(void* ctx, int stage, const ConvArgs* gemm, const void* in, const void* out);
+void launch_attention_gemm(const void* q, const void* k, const void* v, void* out, void* sc, void* vt, int dtype, int B, int H, int W, int C,
+                           hipStream_t s, AttnGemmNote note = nullptr, void* ctx = nullptr);
 
 // net = conv1x1_{4->2}(pyr / t[b]) (t == null: no division); out = sign * net  (complex64 out; sign -1: the score)
 void launch_score_out(const float* pyr, int pc, const float* t, int t_stride, const float* w, const float* bias,

@@ -1983,8 +1983,11 @@ void launch_attention(const void* q, const void* k, const void* v, void* out, in
 }
 
 // Long token sequences (the 64x80 bottleneck of the LSGAN refine generator: N = 5120) run the attention core as two
-// implicit GEMMs on conv_kernel -- scores = conv1x1(q; weights = k), out = conv1x1(softmax(scores); weights = v^T), the
-// [N][C] key tensor already being the packed [Cout][1][Cin] weight layout -- with these two helpers in between.
+// implicit GEMMs through launch_conv -- scores = conv1x1(q; weights = k), out = conv1x1(softmax(scores); weights = v^T), the
+// [N][C] key tensor already being the packed [Cout][1][Cin] weight layout -- with these two helpers in between
+// (launch_attention_gemm below).  The GEMMs run on whatever conv_choose answers: conv_kernel in 16-bit storage (the maps are
+// above conv_sk's 320 pixels); in fp32 storage conv_sk takes every map of at most 4096 pixels with K <= 1024 - the scores of
+// N <= 4096 tokens (K = C) and P.V up to N = 1024 (K = N) - and conv_kernel the rest.
 template <typename T>
 __global__ __launch_bounds__(256) void softmax_rows_kernel(T* __restrict__ x, int cols) {
     __shared__ float red[4];
@@ -2027,6 +2030,42 @@ void launch_transpose_nc(const void* in, void* out, int dtype, int B, int N, int
     if (dtype == DT_F32) hipLaunchKernelGGL((transpose_nc_kernel<float>), grid, dim3(256), 0, s, (const float*)in, (float*)out, N, C);
     else if (dtype == DT_F16) hipLaunchKernelGGL((transpose_nc_kernel<_Float16>), grid, dim3(256), 0, s, (const _Float16*)in, (_Float16*)out, N, C);
     else                 hipLaunchKernelGGL((transpose_nc_kernel<__bf16>), grid, dim3(256), 0, s, (const __bf16*)in, (__bf16*)out, N, C);
+}
+// (N and C in whole 128-row weight tiles, K = C and K = N in whole chunks of conv_kernel)
+bool attention_gemm_eligible(int dtype, int N, int C) {
+    const int ck = dtype == DT_F32 ? 32 : 64;
+    return N > 512 && N % 128 == 0 && C % 128 == 0 && N % ck == 0;
+}
+void launch_attention_gemm(const void* q, const void* k, const void* v, void* out, void* sc_, void* vt_, int dtype, int B, int H, int W, int C,
+                           hipStream_t s, AttnGemmNote note, void* ctx) {
+    // The key tensor [N][C] already is a packed 1x1 weight [Cout = N][1][Cin = C]; v^T plays that part for P.V
+    const int N = H * W;
+    const size_t es = dtype_size(dtype);
+    char* sc = (char*)sc_; char* vt = (char*)vt_;                   // scores -> probabilities [B][N][N]; [B][C][N]
+    if (note) note(ctx, ATTN_GEMM_TRANSPOSE, nullptr, v, vt);
+    launch_transpose_nc(v, vt, dtype, B, N, C, s);
+    for (int b = 0; b < B; ++b) {
+        ConvArgs p{};
+        p.src0 = (const char*)q + (size_t)b * N * C * es; p.C0 = C; p.in_dtype = dtype;
+        p.w = (const char*)k + (size_t)b * N * C * es; p.cout_pad = N;
+        p.out_scale = 1.0f / std::sqrt((float)C);                   // int(C) ** -0.5 (layerspp.py:84)
+        p.out = sc + (size_t)b * N * N * es; p.out_dtype = dtype;
+        p.B = 1; p.H = H; p.W = W; p.Cout = N; p.ntaps = 1;
+        if (note) note(ctx, ATTN_GEMM_SCORES, &p, p.src0, p.out);
+        launch_conv(p, s);
+    }
+    if (note) note(ctx, ATTN_GEMM_SOFTMAX, nullptr, sc, sc);
+    launch_softmax_rows(sc, dtype, (long)B * N, N, s);
+    for (int b = 0; b < B; ++b) {
+        ConvArgs p{};
+        p.src0 = sc + (size_t)b * N * N * es; p.C0 = N; p.in_dtype = dtype;
+        p.w = vt + (size_t)b * C * N * es; p.cout_pad = C;
+        p.out_scale = 1.f;
+        p.out = (char*)out + (size_t)b * N * C * es; p.out_dtype = dtype;
+        p.B = 1; p.H = H; p.W = W; p.Cout = C; p.ntaps = 1;
+        if (note) note(ctx, ATTN_GEMM_PV, &p, p.src0, p.out);
+        launch_conv(p, s);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------
