@@ -616,6 +616,47 @@ typedef struct use_trace_entry {
 int use_trace_count(use_handle* h);
 int use_trace_entry_get(use_handle* h, int index, use_trace_entry* out);
 
+/* Sampler step trace (test infrastructure; use_set_option("sampler_trace", 1), off by default, not a tuning knob: it does not mark plans
+ * stale).  While it is on, a call of use_sample / use_sample_cond / use_sample_cond2 / use_sample_items records one entry per launch
+ * the predictor-corrector loop issues, in launch order, a network evaluation counting as one launch.  The loop overwrites its state X,
+ * the score and the Langevin step in place, so the call also keeps snapshots: device-to-device copies on the loop's own stream into a
+ * buffer that belongs to the plan - of X after the prior and after every corrector and predictor launch, of the score after every
+ * evaluation, of the Langevin step ([items] floats) after every LANGEVIN_STEP, of Xmean at the end.  The copies are captured into the
+ * graph segments and replayed with them; the entries of a captured loop are kept with its graphs and returned for every replay.  No
+ * launch changes and no bit of the result does.  The buffer is allocated at the first traced call of a sampler configuration and filled
+ * with NaN before every traced call (an untaken snapshot is not finite); one that
+ * needs more than 256 MB is refused (USE_E_INVALID, the size named, nothing launched): the trace is for small shapes.  The option may
+ * change between calls: graphs captured under the other setting are dropped, a call with the option off records nothing, allocates
+ * nothing, copies nothing and leaves use_sampler_trace_count at 0.  use_sample_ode is not traced.
+ *
+ * Every pointer below is a snapshot (complex64 [B][F][T'] unless said otherwise), valid after a synchronise until the next sampler
+ * call, use_set_sampler or use_plan; a field a kind does not use is null / 0 / -1.  i: reverse step, k: corrector index (-1: the prior,
+ * and the predictor with its evaluation), d: the noise draw the launch consumed (-1: none), t = timesteps[i] (1 for the prior).  items,
+ * n_per_item: the addressing of the element-wise updates (1, B F T' or B, F T'); per_item: 1 in use_sample_items.
+ *
+ * kind                      reads                               writes      scalars (float32, exactly as passed to the launch)
+ * USE_STRACE_PRIOR          noise (draw 0; null: device RNG)    x_out       std1
+ * USE_STRACE_SCORE          x_in                                score
+ * USE_STRACE_LANGEVIN_NORMS score, noise                        -           blocks_per_b (workgroups per item of the reduction)
+ * USE_STRACE_LANGEVIN_STEP  (the norms)                         step [items] float32     blocks_per_b
+ * USE_STRACE_CORRECTOR      x_in, score, noise, step (Langevin) x_out       step_host (ALD; Langevin: 0 and step set)
+ * USE_STRACE_PREDICTOR      x_in, score, noise                  x_out, x_mean (last step only)   c_drift, c_score, c_noise
+ * USE_STRACE_COPY_MEAN      x_in                                x_mean      (USE_PRED_NONE, last step: Xmean is a copy of X)
+ * use_sampler_trace_count: entries of the current plan's last sampler call (0: none, or the trace was off), < 0: error. */
+enum { USE_STRACE_PRIOR = 1, USE_STRACE_SCORE, USE_STRACE_LANGEVIN_NORMS, USE_STRACE_LANGEVIN_STEP, USE_STRACE_CORRECTOR,
+       USE_STRACE_PREDICTOR, USE_STRACE_COPY_MEAN };
+typedef struct use_sampler_trace_entry {
+    int kind;
+    int i, k, d;
+    float t;
+    float std1, c_drift, c_score, c_noise, step_host;
+    int items; int64_t n_per_item; int blocks_per_b, per_item;
+    const void *x_in, *score, *step, *x_out, *x_mean;
+    const void* noise;                   /* injected noise: the draw this launch read (graph replay: inside the library's staging copy) */
+} use_sampler_trace_entry;
+int use_sampler_trace_count(use_handle* h);
+int use_sampler_trace_get(use_handle* h, int index, use_sampler_trace_entry* out);
+
 #ifdef __cplusplus
 }
 #endif

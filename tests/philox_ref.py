@@ -140,17 +140,21 @@ def predictor(t, N, x, y, s, z, mut=None):
     return out, mean, (bo_r, bo_i), (bm_r, bm_i)
 
 
-def langevin_eps(g, z, snr, mut=None):
+def langevin_eps(g, z, snr, mut=None, blocks=SDE_BLOCKS, per_item=False):
     """eps = 2 (snr mean_b ||z_b|| / mean_b ||g_b||)^2 (correctors.py:55-57) on [B, ...] complex arrays -> (eps, relative error bound in
-    units of 2^-24)."""
+    units of 2^-24).  blocks: the workgroups per item of langevin_norms_kernel (SDE_BLOCKS in use_sde_corrector, the plan's lang_blocks in
+    the sampler loop).  per_item (use_sample_items): eps_b = 2 (snr ||z_b|| / ||g_b||)^2 as an array [B] - the mean of one norm is that
+    norm, and the count of roundings is the same."""
     B = g.shape[0]
     g2, z2 = g.reshape(B, -1).astype(np.complex128), z.reshape(B, -1).astype(np.complex128)
     if mut == "norm_of_mean":
         gn, zn = np.linalg.norm(g2.mean(0)), np.linalg.norm(z2.mean(0))
+    elif per_item:
+        gn, zn = np.linalg.norm(g2, axis=1), np.linalg.norm(z2, axis=1)
     else:
         gn, zn = np.linalg.norm(g2, axis=1).mean(), np.linalg.norm(z2, axis=1).mean()
     snr = float(np.float32(snr))
-    k = -(-g2.shape[1] // (SDE_BLOCKS * 256))               # serial terms per thread
+    k = -(-g2.shape[1] // (blocks * 256))                   # serial terms per thread
     return 2.0 * (snr * zn / gn) ** 2, 2.0 * (k + 17) + 1.0
 
 

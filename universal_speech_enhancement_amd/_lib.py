@@ -69,6 +69,18 @@ class UseTraceEntry(C.Structure):
                 ("params", C.c_char_p * len(TRACE_PARAMS))]
 
 
+SAMPLER_TRACE_KINDS = {1: "prior", 2: "score", 3: "langevin_norms", 4: "langevin_step", 5: "corrector", 6: "predictor",
+                       7: "copy_mean"}                                                                     # USE_STRACE_*
+
+
+class UseSamplerTraceEntry(C.Structure):
+    _fields_ = [("kind", C.c_int), ("i", C.c_int), ("k", C.c_int), ("d", C.c_int), ("t", C.c_float),
+                ("std1", C.c_float), ("c_drift", C.c_float), ("c_score", C.c_float), ("c_noise", C.c_float), ("step_host", C.c_float),
+                ("items", C.c_int), ("n_per_item", C.c_int64), ("blocks_per_b", C.c_int), ("per_item", C.c_int),
+                ("x_in", C.c_void_p), ("score", C.c_void_p), ("step", C.c_void_p), ("x_out", C.c_void_p), ("x_mean", C.c_void_p),
+                ("noise", C.c_void_p)]
+
+
 class UseHipError(RuntimeError):
     pass
 
@@ -137,6 +149,8 @@ SYMBOLS = {
     "use_debug_tensor": (_i, [_vp, C.c_char_p, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i)]),
     "use_trace_count": (_i, [_vp]),
     "use_trace_entry_get": (_i, [_vp, _i, C.POINTER(UseTraceEntry)]),
+    "use_sampler_trace_count": (_i, [_vp]),
+    "use_sampler_trace_get": (_i, [_vp, _i, C.POINTER(UseSamplerTraceEntry)]),
     "use_flops_per_score": (C.c_double, [_vp]),
     "use_get_stat": (_i, [_vp, C.c_char_p, C.POINTER(C.c_longlong)]),
     "use_profile_aux": (_i, [_vp, _i, C.c_char_p, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -149,17 +149,28 @@ struct Plan {
     std::vector<use_trace_entry> trace;          // use_set_option("trace", 1): the launches of the last evaluation's primary sub-batch
     size_t trace_head = 0;                       // ... of which this many were recorded ahead of Fwd::run (time embedding, pack_input)
     double flops = 0.0;
+    // sampler step trace (use_set_option("sampler_trace", 1); use_sampler_trace_entry, use_hip.h).  One entry list per graph set ([gi], kept
+    // with the graphs it was recorded at the capture of) and one for eager calls ([4]); strace_cur: the list of the last sampler call
+    std::vector<use_sampler_trace_entry> strace[5];
+    int strace_cur = -1;                         // -1: the last call was not traced
+    int strace_rec = -1;                         // the list run_sampler is recording into (-1: not tracing)
+    bool graphs_traced = false;                  // the setting graph_exec[] were captured under
+    char* strace_buf = nullptr; size_t strace_bytes = 0, strace_off = 0;   // the snapshots: bump-allocated in launch order from offset 0
+    const float2 *strace_x = nullptr, *strace_score = nullptr; const float* strace_step = nullptr;   // the newest snapshot of each
 
     Plan() = default;
     Plan(const Plan&) = delete;
     Plan& operator=(const Plan&) = delete;
-    void drop_graphs() {
+    void drop_sampler_graphs() {
         for (auto& v : graph_exec) { for (auto g : v) if (g) (void)hipGraphExecDestroy(g); v.clear(); }
+    }
+    void drop_graphs() {
+        drop_sampler_graphs();
         if (score_graph) { (void)hipGraphExecDestroy(score_graph); score_graph = nullptr; }
     }
     ~Plan() {
         drop_graphs();
-        for (void* d : {(void*)arena.base, (void*)persist, (void*)temb_table, (void*)silu_table, (void*)ts_dev, (void*)noise_copy})
+        for (void* d : {(void*)arena.base, (void*)persist, (void*)temb_table, (void*)silu_table, (void*)ts_dev, (void*)noise_copy, (void*)strace_buf})
             if (d) (void)hipFree(d);
     }
 };
@@ -477,6 +488,7 @@ static int g_attn_fused = 1;                     // use_set_option("attn_fused",
 static int g_stats_part = 1;                     // use_set_option("stats_part", 0): GroupNorm totals by atomics on the large maps too
 static int g_stagger_level = 2;                  // use_set_option("stagger_level", l): the next sub-batch starts after level l
 static int g_trace = 0;                          // use_set_option("trace", 1): record every launch of an evaluation (use_trace_entry, use_hip.h)
+static int g_sampler_trace = 0;                  // use_set_option("sampler_trace", 1): record every launch of the PC loop and snapshot what it overwrites (use_sampler_trace_entry)
 
 // ---- launch trace: what each launch read and wrote, for the layer-by-layer tests.  Filled from the launch's own arguments ----
 static use_trace_tensor trace_tensor(const void* p, int B, int H, int W, int C, int dtype) {
@@ -985,33 +997,108 @@ static void run_sampler(use_handle* h, const float2* noise, hipStream_t s, int i
     struct PerImage { bool on; PerImage(bool o) : on(o) { if (on) conv_sk_set_per_image(true); } ~PerImage() { if (on) conv_sk_set_per_image(false); } } per_image(per_item);
     auto nz = [&](unsigned d) { return noise ? noise + (size_t)d * n : nullptr; };
     unsigned d = 1 + (unsigned)i0 * (unsigned)(ncorr + (sc.predictor == USE_PRED_NONE ? 0 : 1));   // noise draws consumed so far
-    if (i0 == 0) launch_prior(pl.Y, nz(0), SdeRng{pl.seeds, 0}, ouve_std(h->cfg, 1.0f), pl.X, items, n_per_item, s);
+    // The sampler step trace (use_sampler_trace_entry, use_hip.h): every `if (tr)` below records the launch above it and copies what it
+    // wrote, on this stream; off, the loop issues what it always did.  The segments of one call run (or are captured) in order, so the
+    // list, the bump offset and the newest snapshots carry over from one segment to the next.
+    const bool tr = pl.strace_rec >= 0;
+    auto rec = [&](int kind, int i, int k, int dd, float t) -> use_sampler_trace_entry& {
+        use_sampler_trace_entry e{};
+        e.kind = kind; e.i = i; e.k = k; e.d = dd; e.t = t;
+        e.items = items; e.n_per_item = n_per_item; e.per_item = per_item ? 1 : 0;
+        pl.strace[pl.strace_rec].push_back(e);
+        return pl.strace[pl.strace_rec].back();
+    };
+    auto snap = [&](const void* src, size_t bytes) -> const void* {
+        const size_t step = (bytes + 255) / 256 * 256;
+        if (pl.strace_off + step > pl.strace_bytes) return nullptr;       // (sized by strace_need from the same counts: never a write past the buffer)
+        char* dst = pl.strace_buf + pl.strace_off;
+        pl.strace_off += step;
+        (void)hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s);
+        return dst;
+    };
+    if (tr && i0 == 0) { pl.strace[pl.strace_rec].clear(); pl.strace_off = 0; pl.strace_x = pl.strace_score = nullptr; pl.strace_step = nullptr; }
+    if (i0 == 0) {
+        const float std1 = ouve_std(h->cfg, 1.0f);
+        launch_prior(pl.Y, nz(0), SdeRng{pl.seeds, 0}, std1, pl.X, items, n_per_item, s);
+        if (tr) {
+            use_sampler_trace_entry& e = rec(USE_STRACE_PRIOR, -1, -1, 0, 1.0f);
+            e.std1 = std1; e.noise = nz(0); e.x_out = pl.strace_x = (const float2*)snap(pl.X, (size_t)n * 8);
+        }
+    }
     for (int i = i0; i < i1; ++i) {
         const float t = pl.timesteps[i];
         const float* temb = pl.temb_table + (size_t)i * h->dense_rows;
         for (int k = 0; k < ncorr; ++k) {
             run_score(h, pl.X, pl.Cond, temb, 0, pl.ts_dev + i, 0, pl.score, s, -1.f, h->pcp == 8 ? pl.cond2_buf : nullptr);
+            if (tr) {
+                use_sampler_trace_entry& e = rec(USE_STRACE_SCORE, i, k, -1, t);
+                e.x_in = pl.strace_x; e.score = pl.strace_score = (const float2*)snap(pl.score, (size_t)n * 8);
+            }
             const SdeRng rng{pl.seeds, d};
             if (sc.corrector == USE_CORR_LANGEVIN) {
                 launch_langevin_norms(pl.score, nz(d), rng, per_item, pl.lang_partial, pl.B, n_per_b, pl.lang_blocks, s);
+                if (tr) {
+                    use_sampler_trace_entry& e = rec(USE_STRACE_LANGEVIN_NORMS, i, k, (int)d, t);
+                    e.score = pl.strace_score; e.noise = nz(d); e.blocks_per_b = pl.lang_blocks;
+                }
                 launch_langevin_step(pl.lang_partial, pl.B, per_item, pl.lang_blocks, sc.snr, pl.lang_step, s);
+                if (tr) {
+                    use_sampler_trace_entry& e = rec(USE_STRACE_LANGEVIN_STEP, i, k, -1, t);
+                    e.blocks_per_b = pl.lang_blocks; e.step = pl.strace_step = (const float*)snap(pl.lang_step, (size_t)items * 4);
+                }
                 launch_corrector(pl.X, pl.score, nz(d), rng, pl.lang_step, 0.f, pl.X, nullptr, items, n_per_item, s);
+                if (tr) {
+                    use_sampler_trace_entry& e = rec(USE_STRACE_CORRECTOR, i, k, (int)d, t);
+                    e.x_in = pl.strace_x; e.score = pl.strace_score; e.step = pl.strace_step; e.noise = nz(d);
+                    e.x_out = pl.strace_x = (const float2*)snap(pl.X, (size_t)n * 8);
+                }
             } else {                                               // ALD: correctors.py:79-98
                 const float sd = sc.snr * ouve_std(h->cfg, t);
                 launch_corrector(pl.X, pl.score, nz(d), rng, nullptr, sd * sd * 2.f, pl.X, nullptr, items, n_per_item, s);
+                if (tr) {
+                    use_sampler_trace_entry& e = rec(USE_STRACE_CORRECTOR, i, k, (int)d, t);
+                    e.x_in = pl.strace_x; e.score = pl.strace_score; e.step_host = sd * sd * 2.f; e.noise = nz(d);
+                    e.x_out = pl.strace_x = (const float2*)snap(pl.X, (size_t)n * 8);
+                }
             }
             d++;
         }
         if (sc.predictor == USE_PRED_NONE) {
-            if (i == sc.N - 1) (void)hipMemcpyAsync(pl.Xmean, pl.X, (size_t)n * 8, hipMemcpyDeviceToDevice, s);
+            if (i == sc.N - 1) {
+                (void)hipMemcpyAsync(pl.Xmean, pl.X, (size_t)n * 8, hipMemcpyDeviceToDevice, s);
+                if (tr) {
+                    use_sampler_trace_entry& e = rec(USE_STRACE_COPY_MEAN, i, -1, -1, t);
+                    e.x_in = pl.strace_x; e.x_mean = snap(pl.Xmean, (size_t)n * 8);
+                }
+            }
         } else {
             run_score(h, pl.X, pl.Cond, temb, 0, pl.ts_dev + i, 0, pl.score, s, -1.f, h->pcp == 8 ? pl.cond2_buf : nullptr);
+            if (tr) {
+                use_sampler_trace_entry& e = rec(USE_STRACE_SCORE, i, -1, -1, t);
+                e.x_in = pl.strace_x; e.score = pl.strace_score = (const float2*)snap(pl.score, (size_t)n * 8);
+            }
             float cd, cs, cn; predictor_coeffs(h->cfg, sc.predictor, t, sc.N, cd, cs, cn);
             launch_predictor(pl.X, pl.Y, pl.score, nz(d), SdeRng{pl.seeds, d}, cd, cs, cn, pl.X,
                              i == sc.N - 1 ? pl.Xmean : nullptr, items, n_per_item, s);
+            if (tr) {
+                use_sampler_trace_entry& e = rec(USE_STRACE_PREDICTOR, i, -1, (int)d, t);
+                e.x_in = pl.strace_x; e.score = pl.strace_score; e.noise = nz(d); e.c_drift = cd; e.c_score = cs; e.c_noise = cn;
+                e.x_out = pl.strace_x = (const float2*)snap(pl.X, (size_t)n * 8);
+                if (i == sc.N - 1) e.x_mean = snap(pl.Xmean, (size_t)n * 8);
+            }
             d++;
         }
     }
+}
+
+// bytes of the snapshots run_sampler takes with the step trace on (its snap() calls, each rounded up to 256 bytes)
+static size_t strace_need(const use_handle* h, const Plan& pl) {
+    const use_sampler_config& sc = pl.sc;
+    const size_t n = (size_t)pl.B * h->cfg.n_freq * pl.T, field = (n * 8 + 255) / 256 * 256;
+    const size_t ncorr = sc.corrector == USE_CORR_NONE ? 0 : (size_t)sc.corrector_steps;
+    const size_t evals = (size_t)sc.N * (ncorr + (sc.predictor == USE_PRED_NONE ? 0 : 1));
+    const size_t steps = sc.corrector == USE_CORR_LANGEVIN ? (size_t)sc.N * ncorr : 0;
+    return (1 + evals + evals + 1) * field + steps * (((size_t)pl.B * 4 + 255) / 256 * 256);    // X, score, Xmean; Langevin steps
 }
 
 static void drop_graphs(use_handle* h) {                  // every graph that replays against the current plan
@@ -1071,6 +1158,7 @@ int use_get_stat(use_handle* h, const char* name, long long* value) {
 int use_set_option(const char* name, long long value) {
     if (!name) return fail(USE_E_INVALID, "option name is null");
     if (!strcmp(name, "trace")) { g_trace = value != 0; return USE_OK; }   // records launches, changes none: no plan goes stale
+    if (!strcmp(name, "sampler_trace")) { g_sampler_trace = value != 0; return USE_OK; }   // the same for the PC loop's launches (use_sampler_trace_entry)
     ++g_opt_gen;                                               // plans built under the previous options are not reused
     if (!strcmp(name, "attn_fused")) { g_attn_fused = (int)value; return USE_OK; }
     if (!strcmp(name, "plan_cache")) { g_plan_cache = (int)std::max(0LL, std::min(16LL, value)); return USE_OK; }   // parked plans per handle
@@ -1497,6 +1585,8 @@ int use_set_sampler(use_handle* h, const use_sampler_config* sc) {
     if (pl.sampler_set && !memcmp(&pl.sc, sc, sizeof *sc)) return USE_OK;       // unchanged (e.g. a parked plan taken back): tables and graphs stay
     HIPCHK(hipDeviceSynchronize());
     drop_graphs(h);
+    for (auto& v : pl.strace) v.clear();                        // the step trace of the previous configuration goes with its graphs
+    pl.strace_cur = -1;
     pl.sc = *sc;
     linspace_f32(1.0f, sc->t_eps, sc->N, pl.timesteps);         // sampling/__init__.py:63 (sde.T == 1)
     if (pl.temb_table) { HIPCHK(hipFree(pl.temb_table)); pl.temb_table = nullptr; }
@@ -1605,14 +1695,36 @@ static int sample_impl(use_handle* h, const void* y, const void* cond, const voi
     Plan& pl = *h->plan;
     hipStream_t s = (hipStream_t)stream;
     const size_t n = (size_t)pl.B * h->cfg.n_freq * pl.T;
+    // The sampler step trace.  Off: nothing is recorded, and the count reads 0.  Graphs captured under the other setting hold (or
+    // lack) the snapshot copies and are dropped; the snapshot buffer is made at the first traced call of a configuration.
+    const bool traced = g_sampler_trace != 0;
+    pl.strace_cur = pl.strace_rec = -1;
+    struct RecOff { Plan& p; ~RecOff() { p.strace_rec = -1; } } rec_off{pl};
+    if (traced != pl.graphs_traced) { HIPCHK(hipDeviceSynchronize()); pl.drop_sampler_graphs(); pl.graphs_traced = traced; }
+    if (traced) {
+        const size_t need = strace_need(h, pl);
+        if (need > ((size_t)256 << 20))
+            return fail(USE_E_INVALID, "sampler_trace: the snapshots of this sampler configuration take %.1f MB, more than the 256 MB the trace allows (it is for small shapes)", need / 1048576.0);
+        if (need != pl.strace_bytes) {
+            HIPCHK(hipDeviceSynchronize());
+            pl.drop_sampler_graphs();                                      // they hold addresses inside the old buffer
+            if (pl.strace_buf) HIPCHK(hipFree(pl.strace_buf));
+            pl.strace_buf = nullptr; pl.strace_bytes = 0;
+            if (hipMalloc((void**)&pl.strace_buf, need) != hipSuccess) return fail(USE_E_NOMEM, "cannot allocate %.1f MB of sampler trace snapshots", need / 1e6);
+            pl.strace_bytes = need;
+        }
+        HIPCHK(hipMemsetAsync(pl.strace_buf, 0xFF, pl.strace_bytes, s));   // NaN: a snapshot that is not taken cannot pass for one of an earlier call
+    }
     rc = load_sampler_inputs(h, y, cond, cond2, s); if (rc) return rc;
     // both forms keep their seeds in pl.seeds, and so do both forms' graphs: each call uploads its own (per item without seeds: all its noise
     // is injected, and its kernels read none)
     if (per_item) { if (seeds_host) upload_item_seeds(pl.seeds, seeds_host, pl.B, s); }
     else hipLaunchKernelGGL(set_rng_kernel, dim3(1), dim3(1), 0, s, pl.seeds, (unsigned long long)seed);
     if (!pl.sc.use_graph) {
+        if (traced) pl.strace_rec = 4;
         run_sampler(h, (const float2*)noise, s, 0, pl.sc.N, per_item);
         rc = eval_status(h); if (rc) return rc;
+        if (traced) pl.strace_cur = 4;
     } else {
         const int gi = (noise ? 1 : 0) + (per_item ? 2 : 0);
         const float2* nz = nullptr;
@@ -1639,6 +1751,7 @@ static int sample_impl(use_handle* h, const void* y, const void* cond, const voi
             rc = ensure_cap_stream(h); if (rc) return rc;
             const int ncorr = pl.sc.corrector == USE_CORR_NONE ? 0 : pl.sc.corrector_steps;
             const int per_seg = std::max(1, 64 / (ncorr + 1));
+            if (traced) pl.strace_rec = gi;                                // recorded once, at the capture: the replays refill the snapshots
             for (int i0 = 0; i0 < pl.sc.N; i0 += per_seg) {
                 hipGraphExec_t ge = nullptr;
                 rc = capture_graph(h, "the sampling loop",
@@ -1647,7 +1760,9 @@ static int sample_impl(use_handle* h, const void* y, const void* cond, const voi
                 pl.graph_exec[gi].push_back(ge);
             }
         }
+        pl.strace_rec = -1;
         for (auto ge : pl.graph_exec[gi]) HIPCHK(hipGraphLaunch(ge, s));
+        if (traced) pl.strace_cur = gi;
     }
     HIPCHK(hipMemcpyAsync(out, pl.Xmean, n * 8, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipGetLastError());
@@ -2736,6 +2851,17 @@ int use_trace_entry_get(use_handle* h, int index, use_trace_entry* out) {
     if (!h || !out) return fail(USE_E_INVALID, "null argument");
     if (!h->plan || index < 0 || index >= (int)h->plan->trace.size()) return fail(USE_E_INVALID, "no trace entry %d", index);
     *out = h->plan->trace[(size_t)index];
+    return USE_OK;
+}
+
+int use_sampler_trace_count(use_handle* h) {
+    if (!h) return fail(USE_E_INVALID, "null handle");
+    return h->plan && h->plan->strace_cur >= 0 ? (int)h->plan->strace[h->plan->strace_cur].size() : 0;
+}
+int use_sampler_trace_get(use_handle* h, int index, use_sampler_trace_entry* out) {
+    if (!h || !out) return fail(USE_E_INVALID, "null argument");
+    if (index < 0 || index >= use_sampler_trace_count(h)) return fail(USE_E_INVALID, "no sampler trace entry %d", index);
+    *out = h->plan->strace[h->plan->strace_cur][(size_t)index];
     return USE_OK;
 }
 

@@ -479,6 +479,41 @@ class HipScoreEngine:
             out.append(d)
         return out
 
+    def sampler_trace(self) -> list:
+        """The launches of the last ``sample`` call's predictor-corrector loop (``use_set_option("sampler_trace", 1)``;
+        ``use_sampler_trace_entry`` in use_hip.h), one dict per launch: ``kind`` as a string, the integer and float32 fields under their C
+        names (floats as ``np.float32``), and the snapshots ``x_in`` / ``score`` / ``x_out`` / ``x_mean`` as complex64 CPU tensors
+        [B,1,F,T'] and ``step`` as a float32 one [items] (None where the kind has none; one tensor per snapshot, shared by the entries that
+        name it).  ``noise``: the device pointer of the injected draw, or None.  Synchronises the device."""
+        torch.cuda.synchronize(self.device)
+        B, T = self.plan_shape
+        cache = {}
+
+        def snap(ptr, step=False, items=1):
+            if not ptr:
+                return None
+            if ptr not in cache:
+                if step:
+                    cache[ptr] = torch.from_numpy(self.read_device(ptr, items, "<f4").copy())
+                else:
+                    a = self.read_device(ptr, 2 * B * self.n_freq * T, "<f4").copy()
+                    cache[ptr] = torch.view_as_complex(torch.from_numpy(a).view(B, 1, self.n_freq, T, 2))
+            return cache[ptr]
+        out = []
+        for i in range(check(self.L.use_sampler_trace_count(self.h), "use_sampler_trace_count")):
+            e = _lib.UseSamplerTraceEntry()
+            check(self.L.use_sampler_trace_get(self.h, i, C.byref(e)), "use_sampler_trace_get")
+            d = {"index": i, "kind": _lib.SAMPLER_TRACE_KINDS[e.kind], "noise": e.noise}
+            for k in ("i", "k", "d", "items", "n_per_item", "blocks_per_b", "per_item"):
+                d[k] = int(getattr(e, k))
+            for k in ("t", "std1", "c_drift", "c_score", "c_noise", "step_host"):
+                d[k] = np.float32(getattr(e, k))
+            for k in ("x_in", "score", "x_out", "x_mean"):
+                d[k] = snap(getattr(e, k))
+            d["step"] = snap(e.step, True, e.items)
+            out.append(d)
+        return out
+
     def read_device(self, ptr: int, n: int, typestr: str) -> "np.ndarray":
         """Host copy of ``n`` elements of library-owned device memory (``typestr``: "<f4", "<u2", "<i8"): the tensors a trace entry names."""
         class _Iface:
