@@ -546,6 +546,25 @@ int use_wav_info(const char* path, int64_t* frames, int* channels, int* sample_r
 int64_t use_resampled_length(int64_t frames, int sample_rate, int target_rate);
 void use_free(void* p);
 
+/* The front of the loader on the device (csrc/use_resample.hip), handle-free: what use_load_utterance does to the decoded first channel of a
+ * file, in fp64 - the host still opens and decodes the file (use_wav_read).
+ * use_resample_fft_dev: the device counterpart of use_resample_fft, x_dev [n] -> y_dev [num], both fp64 DEVICE; num == n is a copy.  The
+ *   transforms are power-of-two FFTs (Stockham passes through LDS), and Bluestein's form over them for any other length; twiddles and chirps
+ *   are evaluated per element from exactly reduced arguments.
+ * use_load_items_dev: B signals, x_dev[b] (HOST array of fp64 DEVICE pointers) of n_host[b] samples -> resampled to num_host[b] samples
+ *   (num == n: as it is) -> with normalize: mx = max |v| by `fabs(v) > mx`, v / mx * 0.8 with two roundings (a silent item gives NaN, as the
+ *   host loader does) -> float32 -> wav[b][0 ... num), exact zeros from there to stride.  wav: float32 DEVICE [B][stride].  At num == n a row
+ *   has the bits use_load_utterance gives it.  The items run one after another on `s`; work_bytes covers the largest item.
+ * No atomics, and every addition has a place fixed by (n, num) alone: an item's output has the same bits in every run, at every row of every
+ * batch, with any companions.  work: use_resample_workspace(n, num) bytes of device scratch for one item, 16-byte aligned (0: n or num < 1 or
+ * above 2^24; a host function, no device needed).  Launches on `s` only: no synchronisation, no allocation.
+ * USE_E_INVALID (reason in use_last_error(), nothing launched): a null or misaligned pointer, B < 1, n or num < 1, max(n, num) > 2^24,
+ * work_bytes too small, stride < num of any item. */
+size_t use_resample_workspace(int64_t n, int64_t num);
+int use_resample_fft_dev(const double* x_dev, int64_t n, int64_t num, double* y_dev, void* work, size_t work_bytes, use_stream_t s);
+int use_load_items_dev(const double* const* x_dev /* [B] device pointers, held on the host */, const int64_t* n_host, const int64_t* num_host,
+                       int B, int normalize, float* wav, int64_t stride, void* work, size_t work_bytes, use_stream_t s);
+
 /* timesteps of the sampler, torch.linspace(1, t_eps, N) float32 semantics (sampling/__init__.py:63); host only */
 int use_timesteps(int N, float t_eps, float* out);
 int use_debug_tensor(use_handle* h, const char* name, void** dev_ptr, int* dims4, int* dtype);

@@ -191,6 +191,9 @@ SYMBOLS = {
     "use_wav_info": (_i, [C.c_char_p, C.POINTER(_i64), C.POINTER(_i), C.POINTER(_i)]),
     "use_resampled_length": (_i64, [_i64, _i, _i]),
     "use_free": (None, [_vp]),
+    "use_resample_workspace": (C.c_size_t, [_i64, _i64]),
+    "use_resample_fft_dev": (_i, [_vp, _i64, _i64, _vp, _vp, C.c_size_t, _vp]),
+    "use_load_items_dev": (_i, [C.POINTER(_vp), C.POINTER(_i64), C.POINTER(_i64), _i, _i, _vp, _i64, _vp, C.c_size_t, _vp]),
 }
 
 

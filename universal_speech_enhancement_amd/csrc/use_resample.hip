@@ -1,0 +1,423 @@
+// The front of the inference loader on the device: what use_load_utterance (use_io.cpp) does to the decoded first channel of a file -
+// FFT resampling (scipy.signal.resample's rule), peak normalisation to 0.8, the cast to float32 - and the zero-padded collation of
+// LoadWavData.predict_batches, in fp64 throughout.  The host still opens and decodes the file (use_wav_read).
+//
+//   resampling   rfft of length n -> bins 0 ... min(n, num) / 2, the shared Nyquist bin of an even shorter grid times 2 (shortening) or
+//                0.5 (lengthening) -> Hermitian extension to length num (the imaginary parts of DC and of an even grid's Nyquist bin are
+//                dropped) -> inverse transform of length num -> times (1 / num) * (num / n).  num == n is a copy.
+//   a transform  of a power-of-two length is the FFT below; of any other length N it is Bluestein's chirp-z form over FFTs of
+//                M = pow2 >= 2 N - 1: a = x * chirp zero-padded, b = conj(chirp) wrapped, ifft(fft(a) * fft(b)) * chirp / M, with
+//                chirp[k] = exp(sign * i * pi * (k^2 mod 2N) / N), the square reduced in 64-bit integers as the host does.
+//   the FFT      Stockham autosort passes of radix R = 2^r <= 512, out of place between two buffers, so that no bit-reversal pass exists.
+//                A workgroup owns C = 2048 / R neighbouring columns j: it reads the R x C tile x[j + r * M / R] (runs of C contiguous
+//                points), applies the pass twiddle W_{Ns R}^{r (j mod Ns)} (Ns = the product of the radices before), transforms the C
+//                columns in LDS by radix-2 stages over a table of W_R^t (2048 points = 32 KiB, the table at most 16 KiB), and writes
+//                y[(j / Ns) Ns R + (j mod Ns) + r Ns] (runs of C, or the whole contiguous tile in the first pass).
+//                M <= 2^11: one pass, one workgroup.  M <= 2^18: two passes.  M <= 2^27: three (fft_plan: the radices as equal as possible).
+//   twiddles     every twiddle and chirp is sincospi of an exactly reduced argument (an integer times a power of two, or an integer
+//                below 2N over N); none comes from a recurrence.
+//   peak, scale  the hand-off's pattern (use_handoff.hip): one partial maximum per LOAD_SLICE samples by a plain store, re-reduced by
+//                every workgroup of the second kernel, which forms v / mx * 0.8 with two roundings, casts, and zeroes the padding.
+// No atomics; every addition has a place fixed by (n, num) alone, so an item's output has the same bits in every run, at every row of
+// every batch, with any companions: the items of a batch run one after another on the stream and share nothing but the workspace.
+//
+// The bodies of the kernels are __host__ __device__ functions of the thread index (one per phase between two barriers), so that a
+// host program can run the same arithmetic without a device.
+#include <cstdarg>
+#include <cstdio>
+
+#include "../../include/use_hip.h"
+#include "use_kernels.h"
+
+int use_set_error(int code, const char* msg);   // use_engine.cpp
+
+namespace use {
+
+namespace {
+
+#define USE_HD __host__ __device__ __forceinline__
+
+constexpr int FFT_THREADS = 256;
+constexpr int FFT_LDS_LOG2 = 11, FFT_LDS = 1 << FFT_LDS_LOG2;   // points a workgroup transforms in LDS
+constexpr int FFT_RADIX_LOG2 = 9;                               // largest radix of a pass of a transform longer than FFT_LDS
+constexpr int FFT_MAX_LOG2 = 26;                                // longest transform (M)
+constexpr int64_t RESAMPLE_MAX = (int64_t)1 << 24;              // max(n, num): Bluestein's M is at most 2^25
+constexpr int LOAD_SLICE = 4096;                                // samples per workgroup of the peak and scale kernels
+static_assert(FFT_MAX_LOG2 <= 3 * FFT_RADIX_LOG2 && 2 * RESAMPLE_MAX <= (int64_t)1 << FFT_MAX_LOG2, "fft_plan: at most three passes");
+
+USE_HD double2 cmul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
+
+// exp(sign * i * pi * t), t >= 0
+USE_HD double2 expipi(double t, int sign) {
+    double s, c;
+#ifdef __HIP_DEVICE_COMPILE__
+    sincospi(t, &s, &c);
+#else
+    s = sin(M_PI * t); c = cos(M_PI * t);
+#endif
+    return make_double2(c, sign < 0 ? -s : s);
+}
+
+// exp(sign * i * pi * k^2 / N) with k^2 reduced mod 2N exactly (k < 2^24: the square fits 64 bits)
+USE_HD double2 chirp(int64_t k, int64_t N, int sign) {
+    const uint64_t k2 = ((uint64_t)k * (uint64_t)k) % (2 * (uint64_t)N);
+    return expipi((double)k2 / (double)N, sign);
+}
+
+// ---- one Stockham pass ----
+struct FftPass { int log2N, log2R, log2Ns, log2C, sign; };
+
+USE_HD int bitrev(int r, int bits) {
+    int o = 0;
+    for (int i = 0; i < bits; ++i) o |= ((r >> i) & 1) << (bits - 1 - i);
+    return o;
+}
+
+// W_R^t, t < R / 2
+USE_HD void fft_table_phase(int tid, double2* w, const FftPass g) {
+    for (int t = tid; t < (1 << g.log2R) / 2; t += FFT_THREADS) w[t] = expipi(ldexp((double)t, 1 - g.log2R), g.sign);
+}
+
+USE_HD void fft_load_phase(int tid, const double2* in, double2* a, const FftPass g, int64_t blk) {
+    const int C = 1 << g.log2C, E = 1 << (g.log2R + g.log2C);
+    const int64_t stride = (int64_t)1 << (g.log2N - g.log2R), j0 = blk << g.log2C;
+    for (int e = tid; e < E; e += FFT_THREADS) {
+        const int c = e & (C - 1), r = e >> g.log2C;
+        const int64_t j = j0 + c;
+        double2 v = in[j + r * stride];
+        if (g.log2Ns > 0) {                                       // r * k < Ns * R <= 2^26: exact in a double, and so is the scaling
+            const int64_t k = j & (((int64_t)1 << g.log2Ns) - 1);
+            v = cmul(v, expipi(ldexp((double)(r * k), 1 - g.log2Ns - g.log2R), g.sign));
+        }
+        a[(bitrev(r, g.log2R) << g.log2C) + c] = v;
+    }
+}
+
+// stage ls (1 ... log2R) of the decimation-in-time butterflies over the C columns
+USE_HD void fft_stage_phase(int tid, double2* a, const double2* w, const FftPass g, int ls) {
+    const int C = 1 << g.log2C, E2 = 1 << (g.log2R + g.log2C - 1), half = 1 << (ls - 1);
+    for (int t = tid; t < E2; t += FFT_THREADS) {
+        const int c = t & (C - 1), b = t >> g.log2C, pos = b & (half - 1);
+        const int i = (((b >> (ls - 1)) << ls) + pos) << g.log2C, i2 = i + (half << g.log2C);
+        const double2 u = a[i + c], v = cmul(a[i2 + c], w[pos << (g.log2R - ls)]);
+        a[i + c] = make_double2(u.x + v.x, u.y + v.y);
+        a[i2 + c] = make_double2(u.x - v.x, u.y - v.y);
+    }
+}
+
+USE_HD void fft_store_phase(int tid, const double2* a, double2* out, const FftPass g, int64_t blk) {
+    const int C = 1 << g.log2C, R = 1 << g.log2R, E = 1 << (g.log2R + g.log2C);
+    const int64_t j0 = blk << g.log2C, maskNs = ((int64_t)1 << g.log2Ns) - 1;
+    for (int e = tid; e < E; e += FFT_THREADS) {
+        int c, r;
+        if (g.log2Ns == 0) { r = e & (R - 1); c = e >> g.log2R; }  // first pass: the tile's outputs j R + r are one contiguous run
+        else { c = e & (C - 1); r = e >> g.log2C; }
+        const int64_t j = j0 + c;
+        out[((j >> g.log2Ns) << (g.log2Ns + g.log2R)) + (j & maskNs) + ((int64_t)r << g.log2Ns)] = a[(r << g.log2C) + c];
+    }
+}
+
+__global__ __launch_bounds__(FFT_THREADS) void fft_pass_kernel(const double2* __restrict__ in, double2* __restrict__ out, const FftPass g) {
+    __shared__ double2 a[FFT_LDS];
+    __shared__ double2 w[FFT_LDS / 2];
+    const int tid = threadIdx.x;
+    fft_table_phase(tid, w, g);
+    fft_load_phase(tid, in, a, g, blockIdx.x);
+    __syncthreads();
+    for (int ls = 1; ls <= g.log2R; ++ls) {
+        fft_stage_phase(tid, a, w, g, ls);
+        __syncthreads();
+    }
+    fft_store_phase(tid, a, out, g, blockIdx.x);
+}
+
+// the radices of the passes of a 2^m-point transform (m <= 27), first pass first; -> the number of passes (0 for m == 0)
+int fft_plan(int m, int log2R[3]) {
+    if (m <= 0) return 0;
+    const int p = m <= FFT_LDS_LOG2 ? 1 : (m + FFT_RADIX_LOG2 - 1) / FFT_RADIX_LOG2;
+    for (int i = 0; i < p; ++i) log2R[i] = m / p + (i < m % p ? 1 : 0);
+    return p;
+}
+
+// the geometry of pass i: its tile is C = min(FFT_LDS / R, M / R) columns wide
+FftPass fft_pass(int m, const int log2R[3], int i, int sign) {
+    FftPass g;
+    g.log2N = m; g.log2R = log2R[i]; g.sign = sign;
+    g.log2Ns = 0;
+    for (int q = 0; q < i; ++q) g.log2Ns += log2R[q];
+    g.log2C = FFT_LDS_LOG2 - g.log2R < m - g.log2R ? FFT_LDS_LOG2 - g.log2R : m - g.log2R;
+    return g;
+}
+
+// smallest power of two >= v, as its exponent
+int ceil_log2(int64_t v) { int m = 0; while (((int64_t)1 << m) < v) ++m; return m; }
+
+// the FFT length a transform of length N runs at: N itself when it is a power of two, else Bluestein's M = pow2 >= 2 N - 1
+int64_t transform_size(int64_t N) { return (N & (N - 1)) == 0 ? N : (int64_t)1 << ceil_log2(2 * N - 1); }
+
+// ---- the source of a transform, the chirp products, the result ----
+struct Src { const double* x; const double2* X; int64_t n, num; };
+
+template <int KIND>
+USE_HD double2 src_value(const Src s, int64_t i) {
+    if (KIND == 0) return make_double2(s.x[i], 0.0);             // the real signal
+    // the Hermitian extension to length num of the kept bins X[0 ... min(n, num) / 2] (resample_fft, use_io.cpp)
+    const int64_t nh = s.num / 2 + 1, N = s.num < s.n ? s.num : s.n, k = i < nh ? i : s.num - i;
+    double2 y = make_double2(0.0, 0.0);
+    if (k < N / 2 + 1) y = s.X[k];
+    if (N % 2 == 0 && k == N / 2) { const double f = s.num < s.n ? 2.0 : 0.5; y.x *= f; y.y *= f; }
+    if (i == 0 || 2 * i == s.num) return make_double2(y.x, 0.0);
+    return i < nh ? y : make_double2(y.x, -y.y);
+}
+
+// A[i] = src[i] (* chirp[i]) for i < N, 0 up to M; B[i] = conj(chirp[d]) at i = d and i = M - d, d < N, 0 between (B == NULL: no Bluestein)
+template <int KIND>
+USE_HD void prep_element(int64_t i, const Src s, double2* A, double2* B, int64_t N, int64_t M, int sign) {
+    double2 v = make_double2(0.0, 0.0);
+    if (i < N) {
+        v = src_value<KIND>(s, i);
+        if (B) v = cmul(v, chirp(i, N, sign));
+    }
+    A[i] = v;
+    if (B) {
+        const int64_t d = i < N ? i : M - i < N ? M - i : -1;
+        B[i] = d >= 0 ? chirp(d, N, -sign) : make_double2(0.0, 0.0);
+    }
+}
+
+// OUT 0: X[k] = result (complex, the kept bins); OUT 1: y[k] = Re(result) * sc
+template <int OUT>
+USE_HD void post_element(int64_t k, const double2* R, int blue, int64_t N, int64_t M, int sign, double2* X, double* y, double sc) {
+    double2 v = R[k];
+    if (blue) {
+        const double inv = 1.0 / (double)M;
+        v = cmul(make_double2(v.x * inv, v.y * inv), chirp(k, N, sign));
+    }
+    if (OUT == 0) X[k] = v;
+    else y[k] = v.x * sc;
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void prep_kernel(const Src s, double2* __restrict__ A, double2* __restrict__ B, int64_t N, int64_t M, int sign) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < M) prep_element<KIND>(i, s, A, B, N, M, sign);
+}
+
+__global__ __launch_bounds__(256) void mul_kernel(double2* __restrict__ A, const double2* __restrict__ B, int64_t M) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < M) A[i] = cmul(A[i], B[i]);
+}
+
+template <int OUT>
+__global__ __launch_bounds__(256) void post_kernel(const double2* __restrict__ R, int blue, int64_t N, int64_t M, int sign, int64_t count,
+                                                   double2* __restrict__ X, double* __restrict__ y, double sc) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k < count) post_element<OUT>(k, R, blue, N, M, sign, X, y, sc);
+}
+
+// ---- peak normalisation, cast, collation ----
+// maximum of 256 non-negative doubles (never NaN); every thread gets the result
+__device__ __forceinline__ double block_max(double v, double* sh) {
+    for (int off = 32; off > 0; off >>= 1) {
+        const double o = __shfl_down(v, off, 64);
+        v = o > v ? o : v;
+    }
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double m = sh[0];
+    for (int w = 1; w < 4; ++w) m = sh[w] > m ? sh[w] : m;
+    return m;
+}
+
+// grid ceil(L / LOAD_SLICE): part[blockIdx.x] = max |v| of the slice, by `fabs(v) > mx` (a NaN never becomes the peak)
+__global__ __launch_bounds__(256) void load_peak_kernel(const double* __restrict__ v, int64_t L, double* __restrict__ part) {
+    __shared__ double sh[4];
+    const int64_t lo = (int64_t)blockIdx.x * LOAD_SLICE, hi = min(L, lo + LOAD_SLICE);
+    double mx = 0.0;
+    for (int64_t i = lo + threadIdx.x; i < hi; i += 256) { const double a = fabs(v[i]); mx = a > mx ? a : mx; }
+    mx = block_max(mx, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = mx;
+}
+
+// grid ceil(stride / LOAD_SLICE): row[i] = (float)(v[i] / mx * 0.8) (NORM) or (float)v[i] for i < L, 0 for L <= i < stride
+template <int NORM>
+__global__ __launch_bounds__(256) void load_scale_kernel(const double* __restrict__ v, int64_t L, const double* __restrict__ part, int np,
+                                                         float* __restrict__ row, int64_t stride) {
+    __shared__ double sh[4];
+    const int64_t lo = (int64_t)blockIdx.x * LOAD_SLICE, hi = min(stride, lo + LOAD_SLICE);
+    double mx = 0.0;
+    if (NORM && lo < L) {
+        for (int j = threadIdx.x; j < np; j += 256) mx = part[j] > mx ? part[j] : mx;
+        mx = block_max(mx, sh);
+    }
+    for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
+        float o = 0.f;
+        if (i < L) {
+            double x = v[i];
+            if (NORM) x = __dmul_rn(__ddiv_rn(x, mx), 0.8);       // v / mx * 0.8: two roundings; mx = 0 gives NaN, as the loader does
+            o = (float)x;
+        }
+        row[i] = o;
+    }
+}
+
+int failf(int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
+    return use_set_error(code, buf);
+}
+
+// ---- host: workspace layout and launches ----
+// byte offsets in an item's workspace: the partial maxima, the resampled signal (use_load_items_dev), the kept bins, three FFT buffers
+struct ItemWork { size_t part, y, spec, buf, bytes; int64_t M; };
+size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
+bool item_ok(int64_t n, int64_t num) { return n >= 1 && num >= 1 && n <= RESAMPLE_MAX && num <= RESAMPLE_MAX; }
+ItemWork item_layout(int64_t n, int64_t num) {
+    ItemWork w;
+    // the buffers are sized for Bluestein's M whether or not a length is a power of two: the size never shrinks as n grows
+    const int64_t Mn = (int64_t)1 << ceil_log2(2 * n - 1), Mnum = (int64_t)1 << ceil_log2(2 * num - 1), keep = (n < num ? n : num) / 2 + 1;
+    w.M = n == num ? 0 : Mn > Mnum ? Mn : Mnum;
+    w.part = 0;
+    w.y = align16((size_t)((num + LOAD_SLICE - 1) / LOAD_SLICE) * sizeof(double));
+    w.spec = w.y + align16((size_t)num * sizeof(double));
+    w.buf = w.spec + (n == num ? 0 : align16((size_t)keep * sizeof(double2)));
+    w.bytes = w.buf + 3 * (size_t)w.M * sizeof(double2);
+    return w;
+}
+
+int blocks256(int64_t count) { return (int)((count + 255) / 256); }
+
+// a 2^m-point FFT from `cur`, ping-pong with `other`; -> the buffer that holds the result
+double2* fft_launch(double2* cur, double2* other, int m, int sign, hipStream_t st) {
+    int log2R[3];
+    const int p = fft_plan(m, log2R);
+    for (int i = 0; i < p; ++i) {
+        const FftPass g = fft_pass(m, log2R, i, sign);
+        hipLaunchKernelGGL(fft_pass_kernel, dim3(1u << (m - g.log2R - g.log2C)), dim3(FFT_THREADS), 0, st, cur, other, g);
+        double2* t = cur; cur = other; other = t;
+    }
+    return cur;
+}
+
+// the DFT of length N of src (KIND) with `sign`; OUT 0: `count` bins to X, OUT 1: the N real parts times sc to y
+template <int KIND, int OUT>
+void dft_launch(const Src src, int64_t N, int sign, int64_t count, double2* X, double* y, double sc, double2* b0, double2* b1, double2* b2,
+                hipStream_t st) {
+    const int64_t M = transform_size(N);
+    const int blue = M != N, m = ceil_log2(M);
+    hipLaunchKernelGGL(prep_kernel<KIND>, dim3(blocks256(M)), dim3(256), 0, st, src, b0, blue ? b1 : (double2*)nullptr, N, M, sign);
+    double2* R;
+    if (blue) {
+        double2* B = fft_launch(b1, b2, m, -1, st);
+        double2* spare = B == b1 ? b2 : b1;
+        double2* A = fft_launch(b0, spare, m, -1, st);
+        spare = A == b0 ? spare : b0;
+        hipLaunchKernelGGL(mul_kernel, dim3(blocks256(M)), dim3(256), 0, st, A, B, M);
+        R = fft_launch(A, spare, m, +1, st);
+    } else {
+        R = fft_launch(b0, b1, m, sign, st);
+    }
+    hipLaunchKernelGGL(post_kernel<OUT>, dim3(blocks256(count)), dim3(256), 0, st, R, blue, N, M, sign, count, X, y, sc);
+}
+
+// scipy.signal.resample(x, num) for n != num
+void resample_launch(const double* x, int64_t n, int64_t num, double* y, char* work, const ItemWork w, hipStream_t st) {
+    double2* X = reinterpret_cast<double2*>(work + w.spec);
+    double2* b0 = reinterpret_cast<double2*>(work + w.buf);
+    double2 *b1 = b0 + w.M, *b2 = b1 + w.M;
+    const int64_t keep = (n < num ? n : num) / 2 + 1;
+    Src s; s.x = x; s.X = X; s.n = n; s.num = num;
+    dft_launch<0, 0>(s, n, -1, keep, X, nullptr, 0.0, b0, b1, b2, st);
+    const double sc = (1.0 / (double)num) * ((double)num / (double)n);
+    dft_launch<1, 1>(s, num, +1, num, nullptr, y, sc, b0, b1, b2, st);
+}
+
+}  // namespace
+
+}  // namespace use
+
+using namespace use;
+
+size_t use_resample_workspace(int64_t n, int64_t num) {
+    if (!item_ok(n, num)) return 0;
+    return item_layout(n, num).bytes;
+}
+
+int use_resample_fft_dev(const double* x_dev, int64_t n, int64_t num, double* y_dev, void* work, size_t work_bytes, use_stream_t s) {
+    if (n < 1 || num < 1) return failf(USE_E_INVALID, "use_resample_fft_dev: n=%lld and num=%lld must be positive", (long long)n, (long long)num);
+    if (!item_ok(n, num))
+        return failf(USE_E_INVALID, "use_resample_fft_dev: max(n, num)=%lld exceeds 2^24", (long long)(n > num ? n : num));
+    if (!x_dev) return failf(USE_E_INVALID, "use_resample_fft_dev: x_dev is null");
+    if (!y_dev) return failf(USE_E_INVALID, "use_resample_fft_dev: y_dev is null");
+    if (!work) return failf(USE_E_INVALID, "use_resample_fft_dev: work is null");
+    const ItemWork w = item_layout(n, num);
+    if (work_bytes < w.bytes)
+        return failf(USE_E_INVALID, "use_resample_fft_dev: work_bytes=%zu is smaller than use_resample_workspace(%lld, %lld) = %zu", work_bytes,
+                     (long long)n, (long long)num, w.bytes);
+    if ((uintptr_t)work & 15) return failf(USE_E_INVALID, "use_resample_fft_dev: work must be 16-byte aligned");
+    if (((uintptr_t)x_dev | (uintptr_t)y_dev) & 7) return failf(USE_E_INVALID, "use_resample_fft_dev: x_dev and y_dev must be 8-byte aligned");
+    hipStream_t st = (hipStream_t)s;
+    if (n == num) {
+        if (x_dev != y_dev && hipMemcpyAsync(y_dev, x_dev, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess)
+            return failf(USE_E_HIP, "use_resample_fft_dev: copy failed: %s", hipGetErrorString(hipGetLastError()));
+        return USE_OK;
+    }
+    resample_launch(x_dev, n, num, y_dev, static_cast<char*>(work), w, st);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return failf(USE_E_HIP, "use_resample_fft_dev: launch failed: %s", hipGetErrorString(e));
+    return USE_OK;
+}
+
+int use_load_items_dev(const double* const* x_dev, const int64_t* n_host, const int64_t* num_host, int B, int normalize, float* wav,
+                       int64_t stride, void* work, size_t work_bytes, use_stream_t s) {
+    if (B < 1) return failf(USE_E_INVALID, "use_load_items_dev: B=%d must be positive", B);
+    if (!x_dev) return failf(USE_E_INVALID, "use_load_items_dev: x_dev is null");
+    if (!n_host) return failf(USE_E_INVALID, "use_load_items_dev: n_host is null");
+    if (!num_host) return failf(USE_E_INVALID, "use_load_items_dev: num_host is null");
+    if (!wav) return failf(USE_E_INVALID, "use_load_items_dev: wav is null");
+    if (!work) return failf(USE_E_INVALID, "use_load_items_dev: work is null");
+    if ((uintptr_t)work & 15) return failf(USE_E_INVALID, "use_load_items_dev: work must be 16-byte aligned");
+    if ((uintptr_t)wav & 3) return failf(USE_E_INVALID, "use_load_items_dev: wav must be 4-byte aligned");
+    if (stride < 1 || (stride + LOAD_SLICE - 1) / LOAD_SLICE > 0x7fffffff)
+        return failf(USE_E_INVALID, "use_load_items_dev: stride=%lld must be positive (and below 2^43)", (long long)stride);
+    for (int b = 0; b < B; ++b) {
+        const int64_t n = n_host[b], num = num_host[b];
+        if (n < 1 || num < 1)
+            return failf(USE_E_INVALID, "use_load_items_dev: n[%d]=%lld and num[%d]=%lld must be positive", b, (long long)n, b, (long long)num);
+        if (!item_ok(n, num))
+            return failf(USE_E_INVALID, "use_load_items_dev: max(n[%d], num[%d])=%lld exceeds 2^24", b, b, (long long)(n > num ? n : num));
+        if (!x_dev[b] || ((uintptr_t)x_dev[b] & 7)) return failf(USE_E_INVALID, "use_load_items_dev: x_dev[%d] is null or not 8-byte aligned", b);
+        if (stride < num)
+            return failf(USE_E_INVALID, "use_load_items_dev: stride=%lld is smaller than num[%d]=%lld", (long long)stride, b, (long long)num);
+        const size_t need = item_layout(n, num).bytes;
+        if (work_bytes < need)
+            return failf(USE_E_INVALID, "use_load_items_dev: work_bytes=%zu is smaller than use_resample_workspace(%lld, %lld) = %zu (item %d)",
+                         work_bytes, (long long)n, (long long)num, need, b);
+    }
+    hipStream_t st = (hipStream_t)s;
+    char* base = static_cast<char*>(work);
+    for (int b = 0; b < B; ++b) {
+        const int64_t n = n_host[b], num = num_host[b];
+        const ItemWork w = item_layout(n, num);
+        const double* v = x_dev[b];
+        if (n != num) {
+            double* y = reinterpret_cast<double*>(base + w.y);
+            resample_launch(x_dev[b], n, num, y, base, w, st);
+            v = y;
+        }
+        double* part = reinterpret_cast<double*>(base + w.part);
+        const int np = (int)((num + LOAD_SLICE - 1) / LOAD_SLICE);
+        float* row = wav + (int64_t)b * stride;
+        const dim3 grid((unsigned)((stride + LOAD_SLICE - 1) / LOAD_SLICE)), block(256);
+        if (normalize) {
+            hipLaunchKernelGGL(load_peak_kernel, dim3(np), block, 0, st, v, num, part);
+            hipLaunchKernelGGL(load_scale_kernel<1>, grid, block, 0, st, v, num, part, np, row, stride);
+        } else {
+            hipLaunchKernelGGL(load_scale_kernel<0>, grid, block, 0, st, v, num, part, np, row, stride);
+        }
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return failf(USE_E_HIP, "use_load_items_dev: launch failed: %s", hipGetErrorString(e));
+    return USE_OK;
+}

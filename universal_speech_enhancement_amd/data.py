@@ -6,7 +6,12 @@ the longest item.  Multi-process runs shard the file list over ranks like the re
 
 ``bucket_by_length`` (no reference counterpart, off by default): the rank's shard - the same file set as without it - is ordered by
 (padded frame count T', relative path) and cut into batches of files of EQUAL T', so that ``sample(own_length=True)`` runs full
-batches of one plan shape; T' comes from the WAV headers (``wav_info`` + ``resampled_length``), no file is decoded for it."""
+batches of one plan shape; T' comes from the WAV headers (``wav_info`` + ``resampled_length``), no file is decoded for it.
+
+``device_load`` (no reference counterpart, off by default): the host only decodes the files; resampling, peak normalisation, the cast
+and the zero-padded collation run on the device (``wavio.load_batch_device``).  The batch dict is the same; a resampled row is the host
+loader's to within the last float32 bit, a row at an unchanged rate is bit-equal.  A file of more than ``device_load_max_samples``
+samples (before or after resampling) takes the host path."""
 from __future__ import annotations
 
 import os
@@ -16,16 +21,17 @@ import numpy as np
 import torch
 
 from .distributed import shard_list
-from .wavio import load_utterance, resampled_length, wav_info
+from .wavio import load_batch_device, load_utterance, resampled_length, wav_info
 
 
 class LoadWavData:
     def __init__(self, data_folder: str, target_folder: str, normalize: bool = True, sampling_rate: int = 24000,
                  batch_size: int = 1, num_workers: int = 0, rank: int = 0, world_size: int = 1, bucket_by_length: bool = False,
-                 **ignored):
+                 device_load: bool = False, device_load_max_samples: int = 2 ** 24, **ignored):
         self.data_folder, self.target_folder = data_folder, target_folder
         self.normalize, self.sampling_rate, self.batch_size = normalize, sampling_rate, batch_size
         self.bucket_by_length = bool(bucket_by_length)
+        self.device_load, self.device_load_max_samples = bool(device_load), int(device_load_max_samples)
         files: List[str] = []
         for root, _, names in os.walk(data_folder):
             files += [os.path.join(root, n) for n in sorted(names) if n.endswith(".wav")]
@@ -64,6 +70,20 @@ class LoadWavData:
         return batches
 
     def predict_batches(self, device="cuda", frame_hop=None) -> Iterator[Dict]:
+        if self.device_load:
+            if torch.device(device).type != "cuda":
+                raise ValueError(f"device_load=True needs a CUDA (ROCm) device, got {device!r}: the device loader has no CPU implementation")
+            return self._device_batches(device, frame_hop)
+        return self._host_batches(device, frame_hop)
+
+    def _device_batches(self, device, frame_hop) -> Iterator[Dict]:
+        for paths in self.batch_files(frame_hop):
+            wav, lens, rates = load_batch_device(paths, self.sampling_rate, self.normalize, device, self.device_load_max_samples)
+            yield {"perturbed": wav, "name": [os.path.basename(p).split(".wav")[0] for p in paths],
+                   "sample_length": torch.from_numpy(lens), "sampling_rate": rates, "audio_path": list(paths),
+                   "data_folder": self.data_folder, "target_folder": self.target_folder}
+
+    def _host_batches(self, device, frame_hop) -> Iterator[Dict]:
         for paths in self.batch_files(frame_hop):
             items = [self._item(p) for p in paths]
             lens = np.array([len(it["perturbed"]) for it in items], dtype=np.int32)

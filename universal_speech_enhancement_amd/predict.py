@@ -23,6 +23,9 @@
                                                   [model.handoff_subtype=FLOAT] hands over unquantised samples; [model.stage1_folder=enhanced/]
                                                   keeps the stage-1 files as well; each checkpoint a Lightning .ckpt or a packed .usehip file)
     Options of every model:
+        [data.device_load=true]                  (the loader's FFT resampling, peak normalisation, cast and collation on the device instead
+                                                  of file by file on the host, which then only decodes; off by default.  A resampled input
+                                                  equals the host loader's to within the last float32 bit, one at an unchanged rate bit for bit)
         [data.clean_folder=clean/]               (score every enhanced file whose clean counterpart exists under clean/ at the same
                                                   relative path: SI-SDR / SI-SIR / SI-SAR / LSD on the device -> enhanced/metrics.csv)
         [data.clean_folder=clean/ data.convergence_losses=true]

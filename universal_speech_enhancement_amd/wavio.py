@@ -1,7 +1,11 @@
 """WAV files and the loader's FFT resampling through the library's host functions (``use_wav_read`` / ``use_wav_write`` /
 ``use_resample_fft`` / ``use_load_utterance``, include/use_hip.h): the reference's ``sf.read`` -> first channel ->
 ``librosa.resample(res_type="fft")`` -> peak normalisation (``src/data/components/loadwav_dataset.py:90-120``) and
-``sf.write`` (``src/models/SGMSE_module.py:80``) without soundfile / librosa / scipy."""
+``sf.write`` (``src/models/SGMSE_module.py:80``) without soundfile / librosa / scipy.
+
+``resample_fft_device`` / ``load_batch_device`` (``use_resample_fft_dev`` / ``use_load_items_dev``, csrc/use_resample.hip): the same
+resampling, peak normalisation, cast and the loader's zero-padded collation on the device; the host only decodes the files.  There is
+no CPU implementation of the two."""
 from __future__ import annotations
 
 import ctypes as C
@@ -9,7 +13,7 @@ import os
 
 import numpy as np
 
-from ._lib import check, lib
+from ._lib import UseHipError, check, lib
 
 PCM16, FLOAT32 = 0, 1
 
@@ -66,3 +70,97 @@ def load_utterance(path: str, sampling_rate: int = 24000, normalize: bool = True
     finally:
         lib().use_free(p)
     return a, sr.value
+
+
+_WORK = {}                                                  # device -> the cached workspace of the device loader (uint8, grown on demand)
+
+
+def _workspace(dev, nbytes: int):
+    import torch
+    w = _WORK.get(dev)
+    if w is None or w.numel() < nbytes:
+        _WORK.pop(dev, None)                                # let the old one go before the larger one is allocated
+        w = _WORK[dev] = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
+    return w
+
+
+def _device_workspace_bytes(n: int, num: int) -> int:
+    nbytes = lib().use_resample_workspace(int(n), int(num))
+    if not nbytes:
+        raise ValueError(f"use_resample_workspace refuses n={n}, num={num} (each must lie in 1 ... 2^24)")
+    return nbytes
+
+
+def resample_fft_device(x, num: int):
+    """``scipy.signal.resample(x, num)`` for a real 1-D signal on the device: ``x`` a float64 CUDA tensor -> float64 CUDA ``[num]``
+    (``use_resample_fft_dev``)."""
+    import torch
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise UseHipError("x must be a CUDA (ROCm) tensor: the device resampler has no CPU implementation")
+    if x.dtype != torch.float64 or x.dim() != 1:
+        raise TypeError(f"x must be a 1-D float64 tensor, got {x.dtype} of shape {tuple(x.shape)}")
+    x = x.contiguous()
+    n, num = x.shape[0], int(num)
+    nbytes = _device_workspace_bytes(n, num)
+    dev = x.device
+    y = torch.empty(num, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        work = _workspace(dev, nbytes)
+        check(lib().use_resample_fft_dev(x.data_ptr(), n, num, y.data_ptr(), work.data_ptr(), work.numel(),
+                                         torch.cuda.current_stream(dev).cuda_stream), "use_resample_fft_dev")
+    return y
+
+
+def load_batch_device(paths, sampling_rate: int = 24000, normalize: bool = True, device="cuda", max_samples: int = 2 ** 24):
+    """The batch ``LoadWavData`` builds from ``paths``, formed on the device: -> (float32 ``[B, Lmax]`` on ``device``, int32 lengths
+    ``[B]`` (host), sample rates).  The host decodes every file (``read_wav``) and uploads the first channel as float64; resampling to
+    ``sampling_rate`` (0 / None: keep) at the length ``resampled_length`` gives, peak normalisation, the cast and the zero padding run
+    in one ``use_load_items_dev`` call.  A file with more than ``max_samples`` samples before or after resampling goes through
+    ``load_utterance`` on the host instead: its row has the host loader's bits."""
+    import torch
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise ValueError(f"load_batch_device needs a CUDA (ROCm) device, got {dev}: the device loader has no CPU implementation")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    target = int(sampling_rate or 0)
+    limit = min(int(max_samples), 2 ** 24)
+    sigs, ns, nums, rates, host_rows = [], [], [], [], {}
+    for b, path in enumerate(paths):
+        a, sr = read_wav(path)
+        n = a.shape[0]
+        if n < 1:
+            raise UseHipError(f"load_batch_device: '{path}' holds no samples")
+        num = resampled_length(n, sr, target)
+        if max(n, num) > limit:
+            host_rows[b] = load_utterance(path, target, normalize)[0]
+            sigs.append(None)
+        else:
+            sigs.append(np.ascontiguousarray(a if a.ndim == 1 else a[:, 0]))      # first channel (loadwav_dataset.py:93-94)
+        ns.append(n)
+        nums.append(num)
+        rates.append(target if target > 0 else sr)
+    B, stride = len(ns), max(nums)
+    lens = np.asarray(nums, dtype=np.int32)
+    with torch.cuda.device(dev):
+        wav = torch.empty(B, stride, dtype=torch.float32, device=dev)
+        xs = [None if s is None else torch.from_numpy(s).to(dev) for s in sigs]
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        b = 0
+        while b < B:                                        # one call per run of rows that the device forms: one call without host rows
+            if b in host_rows:
+                row = torch.from_numpy(host_rows[b])
+                wav[b, : row.shape[0]] = row.to(dev)
+                wav[b, row.shape[0]:] = 0
+                b += 1
+                continue
+            e = b
+            while e < B and e not in host_rows:
+                e += 1
+            k = e - b
+            work = _workspace(dev, max(_device_workspace_bytes(ns[i], nums[i]) for i in range(b, e)))
+            ptrs = (C.c_void_p * k)(*[xs[i].data_ptr() for i in range(b, e)])
+            check(lib().use_load_items_dev(ptrs, (C.c_int64 * k)(*ns[b:e]), (C.c_int64 * k)(*nums[b:e]), k, int(bool(normalize)),
+                                           wav[b].data_ptr(), stride, work.data_ptr(), work.numel(), stream), "use_load_items_dev")
+            b = e
+    return wav, lens, rates
