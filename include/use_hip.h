@@ -565,6 +565,25 @@ int use_resample_fft_dev(const double* x_dev, int64_t n, int64_t num, double* y_
 int use_load_items_dev(const double* const* x_dev /* [B] device pointers, held on the host */, const int64_t* n_host, const int64_t* num_host,
                        int B, int normalize, float* wav, int64_t stride, void* work, size_t work_bytes, use_stream_t s);
 
+/* The way out on the device (csrc/use_resample.hip), handle-free: from the sampler's float32 rows to the samples of files at their own rate.
+ * use_store_items_dev: wav float32 DEVICE [B][stride], item b valid for len_host[b] samples (HOST ints; a row is never read past them: after
+ *   the iSTFT the padding holds anything) -> widened to fp64 -> resampled to num_host[b] samples with the arithmetic of use_resample_fft_dev
+ *   (num == len: no transform) -> rounded to float32, x32 -> USE_WAV_FLOAT32: out is float [B][out_stride] and receives x32;
+ *   USE_WAV_PCM16: out is int16_t [B][out_stride] and receives what use_wav_write stores for x32, nearbyint((double)x32 * 32767) clamped to
+ *   [-32768, 32767], a NaN as 0.  Exact zeros from num[b] to out_stride.  At num == len a float row has the input's bits.
+ * use_wav_write_pcm16 (host): the file use_wav_write(..., USE_WAV_PCM16) writes, from ready-made codes (interleaved, as they are).
+ * No atomics, and every addition has a place fixed by (len, num) alone: an item's output has the same bits in every run, at every row of every
+ * batch, at any stride and out_stride.  The items run one after another on `s`; row offsets are 64-bit.  work: use_store_workspace(len, num)
+ * bytes of device scratch for the largest item, 16-byte aligned (0: len or num < 1 or above 2^24; a host function, no device needed).
+ * Launches on `s` only: no synchronisation, no allocation.
+ * USE_E_INVALID (reason in use_last_error(), nothing launched): a null or misaligned pointer, B < 1, len[b] < 1 or > stride, num[b] < 1 or
+ * > out_stride, max(len, num) > 2^24, an unknown subtype, work_bytes too small. */
+size_t use_store_workspace(int64_t len, int64_t num);
+int use_store_items_dev(const float* wav, int64_t stride, const int* len_host, const int64_t* num_host, int B,
+                        int subtype /* USE_WAV_PCM16 | USE_WAV_FLOAT32 */, void* out, int64_t out_stride, void* work, size_t work_bytes,
+                        use_stream_t s);
+int use_wav_write_pcm16(const char* path, const int16_t* codes, int64_t frames, int channels, int sample_rate);
+
 /* timesteps of the sampler, torch.linspace(1, t_eps, N) float32 semantics (sampling/__init__.py:63); host only */
 int use_timesteps(int N, float t_eps, float* out);
 int use_debug_tensor(use_handle* h, const char* name, void** dev_ptr, int* dims4, int* dtype);

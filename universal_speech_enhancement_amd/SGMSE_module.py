@@ -36,11 +36,18 @@ def _with_path_seeds(sampler_kwargs: dict, batch: dict) -> dict:
     return kw
 
 
-def _write_items(batch: dict, wavs, folder, subtype: str):
+def _write_items(batch: dict, wavs, folder, subtype: str, restore: bool = True):
     """Item i of ``wavs``, trimmed to ``sample_length[i]``, to ``audio_path[i].replace(data_folder, folder)`` (reference
-    SGMSE_module.py:72-80); a batch without ``audio_path`` writes nothing."""
+    SGMSE_module.py:72-80); a batch without ``audio_path`` writes nothing.
+
+    A batch that carries ``source_rate`` and ``source_length`` (``LoadWavData(restore_rate=True)``) is written at its sources' own
+    rates instead, unless ``restore`` is off: item i, resampled from its ``sample_length[i]`` samples to exactly ``source_length[i]``
+    frames, at ``source_rate[i]`` - the whole batch in one device call and one copy (``wavio.store_batch_device``; a CPU batch through
+    ``wavio.store_items_host``).  A file whose rate is the model's has the bytes it has without the keys."""
     if "audio_path" not in batch:
         return
+    if restore and "source_rate" in batch and "source_length" in batch:
+        return _write_items_restored(batch, wavs, folder, subtype)
     for i, wav in enumerate(wavs):
         noisy_path = batch["audio_path"][i]
         sample_length = int(batch["sample_length"][i])
@@ -48,6 +55,24 @@ def _write_items(batch: dict, wavs, folder, subtype: str):
         path = noisy_path.replace(batch["data_folder"], folder)
         os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
         _write_wav(path, wav.detach().cpu().numpy().astype(np.float32)[:sample_length], sample_rate, subtype)
+
+
+def _write_items_restored(batch: dict, wavs, folder, subtype: str):
+    from . import wavio
+    if subtype not in ("PCM_16", "FLOAT"):
+        raise ValueError(f"unsupported WAV subtype {subtype!r} (PCM_16 or FLOAT)")
+    code = wavio.PCM16 if subtype == "PCM_16" else wavio.FLOAT32
+    wavs = torch.as_tensor(wavs).detach().float()
+    lens = [int(n) for n in batch["sample_length"]]
+    nums = [int(n) for n in batch["source_length"]]
+    rows = (wavio.store_batch_device if wavs.is_cuda else wavio.store_items_host)(wavs, lens, nums, code)
+    for i, num in enumerate(nums):
+        path = batch["audio_path"][i].replace(batch["data_folder"], folder)
+        os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+        if code == wavio.PCM16:
+            wavio.write_wav_pcm16(path, rows[i, :num], int(batch["source_rate"][i]))
+        else:
+            wavio.write_wav(path, rows[i, :num], int(batch["source_rate"][i]), wavio.FLOAT32)
 
 
 try:                                                     # reference: class SGMSEModule(LightningModule), SGMSE_module.py:10

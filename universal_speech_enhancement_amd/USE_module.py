@@ -70,7 +70,8 @@ class USEModule(_Base):
         enhanced = batch["enhanced"]
         lengths = batch.get("sample_length")
         if self.stage1_folder:
-            _write_items(batch, enhanced, self.stage1_folder, self.handoff_subtype)
+            # at the model's rate whatever data.restore_rate says: these are the files the second run's loader reads
+            _write_items(batch, enhanced, self.stage1_folder, self.handoff_subtype, restore=False)
         wav, peaks = wav_handoff(enhanced, lengths, self.handoff_subtype, self.normalize)
         stage2 = {"perturbed": wav}
         if lengths is not None:

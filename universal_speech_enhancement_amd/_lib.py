@@ -194,6 +194,9 @@ SYMBOLS = {
     "use_resample_workspace": (C.c_size_t, [_i64, _i64]),
     "use_resample_fft_dev": (_i, [_vp, _i64, _i64, _vp, _vp, C.c_size_t, _vp]),
     "use_load_items_dev": (_i, [C.POINTER(_vp), C.POINTER(_i64), C.POINTER(_i64), _i, _i, _vp, _i64, _vp, C.c_size_t, _vp]),
+    "use_store_workspace": (C.c_size_t, [_i64, _i64]),
+    "use_store_items_dev": (_i, [_vp, _i64, C.POINTER(_i), C.POINTER(_i64), _i, _i, _vp, _i64, _vp, C.c_size_t, _vp]),
+    "use_wav_write_pcm16": (_i, [C.c_char_p, _vp, _i64, _i, _i]),
 }
 
 

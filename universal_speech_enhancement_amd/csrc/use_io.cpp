@@ -11,6 +11,7 @@
 //   use_wav_write                      <- sf.write(path, enhanced, sampling_rate)                  src/models/SGMSE_module.py:80
 //        soundfile's default WAV subtype is PCM_16 whatever the array dtype: round(x * 32767) (libsndfile's normalised float ->
 //        short conversion); values beyond full scale are clipped here (libsndfile wraps them unless clipping is switched on).
+//   use_wav_write_pcm16                the same file from codes quantised elsewhere (use_store_items_dev forms them on the device).
 //
 // The transforms are double-precision Bluestein FFTs (any length: utterance lengths are arbitrary) over a radix-2 kernel.
 #include <math.h>
@@ -111,6 +112,29 @@ void resample_fft(const double* x, int64_t Nx, int64_t num, double* y) {
 uint32_t rd32(const unsigned char* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
 uint16_t rd16(const unsigned char* p) { return (uint16_t)(p[0] | p[1] << 8); }
 
+uint64_t wav_data_len(int64_t frames, int channels, int subtype) {
+    return (uint64_t)frames * (uint64_t)channels * (uint64_t)(subtype == USE_WAV_PCM16 ? 2 : 4);
+}
+
+// the 44-byte header and `data`, the samples as the file holds them (16-bit codes or float32, interleaved)
+int wav_write_file(const char* path, int subtype, int64_t frames, int channels, int sample_rate, const void* data) {
+    const int bps = subtype == USE_WAV_PCM16 ? 2 : 4;
+    const uint64_t data_len = wav_data_len(frames, channels, subtype);
+    FILE* f = fopen(path, "wb");
+    if (!f) return failf(USE_E_INVALID, "cannot create '%s'", path);
+    unsigned char h[44];
+    auto w32 = [](unsigned char* p, uint32_t v) { p[0] = v & 255; p[1] = v >> 8 & 255; p[2] = v >> 16 & 255; p[3] = v >> 24 & 255; };
+    auto w16 = [](unsigned char* p, uint16_t v) { p[0] = v & 255; p[1] = v >> 8 & 255; };
+    memcpy(h, "RIFF", 4); w32(h + 4, (uint32_t)(36 + data_len)); memcpy(h + 8, "WAVEfmt ", 8); w32(h + 16, 16);
+    w16(h + 20, subtype == USE_WAV_PCM16 ? 1 : 3); w16(h + 22, (uint16_t)channels); w32(h + 24, (uint32_t)sample_rate);
+    w32(h + 28, (uint32_t)sample_rate * (uint32_t)channels * (uint32_t)bps); w16(h + 32, (uint16_t)(channels * bps)); w16(h + 34, (uint16_t)(bps * 8));
+    memcpy(h + 36, "data", 4); w32(h + 40, (uint32_t)data_len);
+    bool ok = fwrite(h, 1, 44, f) == 44;
+    ok = ok && fwrite(data, 1, (size_t)data_len, f) == (size_t)data_len;
+    ok = (fclose(f) == 0) && ok;
+    return ok ? USE_OK : failf(USE_E_INVALID, "write to '%s' failed", path);
+}
+
 }  // namespace
 
 extern "C" {
@@ -173,33 +197,24 @@ int use_wav_read(const char* path, double** samples, int64_t* frames, int* chann
 int use_wav_write(const char* path, const float* samples, int64_t frames, int channels, int sample_rate, int subtype) {
     if (!path || (!samples && frames > 0) || frames < 0 || channels < 1 || sample_rate < 1 || (subtype != USE_WAV_PCM16 && subtype != USE_WAV_FLOAT32))
         return use_set_error(USE_E_INVALID, "use_wav_write: bad argument");
-    const int bps = subtype == USE_WAV_PCM16 ? 2 : 4;
-    const uint64_t data_len = (uint64_t)frames * (uint64_t)channels * (uint64_t)bps;
-    if (data_len > 0xFFFFFF00ull) return use_set_error(USE_E_INVALID, "use_wav_write: more than 4 GiB of samples");
-    FILE* f = fopen(path, "wb");
-    if (!f) return failf(USE_E_INVALID, "cannot create '%s'", path);
-    unsigned char h[44];
-    auto w32 = [](unsigned char* p, uint32_t v) { p[0] = v & 255; p[1] = v >> 8 & 255; p[2] = v >> 16 & 255; p[3] = v >> 24 & 255; };
-    auto w16 = [](unsigned char* p, uint16_t v) { p[0] = v & 255; p[1] = v >> 8 & 255; };
-    memcpy(h, "RIFF", 4); w32(h + 4, (uint32_t)(36 + data_len)); memcpy(h + 8, "WAVEfmt ", 8); w32(h + 16, 16);
-    w16(h + 20, subtype == USE_WAV_PCM16 ? 1 : 3); w16(h + 22, (uint16_t)channels); w32(h + 24, (uint32_t)sample_rate);
-    w32(h + 28, (uint32_t)sample_rate * (uint32_t)channels * (uint32_t)bps); w16(h + 32, (uint16_t)(channels * bps)); w16(h + 34, (uint16_t)(bps * 8));
-    memcpy(h + 36, "data", 4); w32(h + 40, (uint32_t)data_len);
-    bool ok = fwrite(h, 1, 44, f) == 44;
+    if (wav_data_len(frames, channels, subtype) > 0xFFFFFF00ull) return use_set_error(USE_E_INVALID, "use_wav_write: more than 4 GiB of samples");
     const size_t n = (size_t)frames * (size_t)channels;
-    if (subtype == USE_WAV_FLOAT32) {
-        ok = ok && fwrite(samples, 4, n, f) == n;                     // little-endian host (gfx950 hosts are x86-64)
-    } else {
-        std::vector<int16_t> q(n);
-        for (size_t i = 0; i < n; ++i) {
-            double v = nearbyint((double)samples[i] * 32767.0);
-            if (!(v == v)) v = 0.0;
-            q[i] = (int16_t)(v > 32767.0 ? 32767.0 : v < -32768.0 ? -32768.0 : v);
-        }
-        ok = ok && fwrite(q.data(), 2, n, f) == n;
+    if (subtype == USE_WAV_FLOAT32) return wav_write_file(path, subtype, frames, channels, sample_rate, samples);   // little-endian host (gfx950 hosts are x86-64)
+    std::vector<int16_t> q(n);
+    for (size_t i = 0; i < n; ++i) {
+        double v = nearbyint((double)samples[i] * 32767.0);
+        if (!(v == v)) v = 0.0;
+        q[i] = (int16_t)(v > 32767.0 ? 32767.0 : v < -32768.0 ? -32768.0 : v);
     }
-    ok = (fclose(f) == 0) && ok;
-    return ok ? USE_OK : failf(USE_E_INVALID, "write to '%s' failed", path);
+    return wav_write_file(path, subtype, frames, channels, sample_rate, q.data());
+}
+
+int use_wav_write_pcm16(const char* path, const int16_t* codes, int64_t frames, int channels, int sample_rate) {
+    if (!path || (!codes && frames > 0) || frames < 0 || channels < 1 || sample_rate < 1)
+        return use_set_error(USE_E_INVALID, "use_wav_write_pcm16: bad argument");
+    if (wav_data_len(frames, channels, USE_WAV_PCM16) > 0xFFFFFF00ull)
+        return use_set_error(USE_E_INVALID, "use_wav_write_pcm16: more than 4 GiB of samples");
+    return wav_write_file(path, USE_WAV_PCM16, frames, channels, sample_rate, codes);
 }
 
 int use_resample_fft(const double* x, int64_t n, int64_t num, double* y) {

@@ -21,6 +21,10 @@
 // No atomics; every addition has a place fixed by (n, num) alone, so an item's output has the same bits in every run, at every row of
 // every batch, with any companions: the items of a batch run one after another on the stream and share nothing but the workspace.
 //
+// The way out (use_store_items_dev) runs the same resampler from the model's rate back to a file's own: an item's float32 row, read up
+// to its length only, is widened to fp64, resampled to the file's frame count, rounded to float32 and stored as it is or as the 16-bit
+// code use_wav_write would store, with zeros up to the row's end.  At an unchanged length no transform runs and the row's bits pass.
+//
 // The bodies of the kernels are __host__ __device__ functions of the thread index (one per phase between two barriers), so that a
 // host program can run the same arithmetic without a device.
 #include <cstdarg>
@@ -262,6 +266,37 @@ __global__ __launch_bounds__(256) void load_scale_kernel(const double* __restric
     }
 }
 
+// ---- the way out: float32 rows -> file samples (use_store_items_dev) ----
+// x[i] = (double)row[i] for i < L: the only read of a row, and none of it past the item's length
+__global__ __launch_bounds__(256) void store_widen_kernel(const float* __restrict__ row, int64_t L, double* __restrict__ x) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < L) x[i] = (double)row[i];
+}
+
+// the 16-bit code use_wav_write stores for a float32 sample (use_io.cpp): the product is exact (24 + 15 bits), rint rounds to nearest even
+// as the host's nearbyint does, a NaN becomes 0
+__device__ __forceinline__ int16_t pcm16_code(float x32) {
+    double v = rint((double)x32 * 32767.0);
+    if (!(v == v)) v = 0.0;
+    return (int16_t)(v > 32767.0 ? 32767.0 : v < -32768.0 ? -32768.0 : v);
+}
+
+// grid ceil(out_stride / LOAD_SLICE): row[i] = x32 = (float)v[i] (DST float) or its 16-bit code (DST int16_t) for i < num, 0 for
+// num <= i < out_stride.  SRC double: the resampled signal; SRC float: the item's own row (num == len), whose bits pass unchanged
+template <typename SRC, typename DST>
+__global__ __launch_bounds__(256) void store_kernel(const SRC* __restrict__ v, int64_t num, DST* __restrict__ row, int64_t out_stride) {
+    const int64_t lo = (int64_t)blockIdx.x * LOAD_SLICE, hi = min(out_stride, lo + LOAD_SLICE);
+    for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
+        DST o = 0;
+        if (i < num) {
+            const float x32 = (float)v[i];
+            if constexpr (sizeof(DST) == 2) o = pcm16_code(x32);
+            else o = x32;
+        }
+        row[i] = o;
+    }
+}
+
 int failf(int code, const char* fmt, ...) {
     char buf[512];
     va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
@@ -331,6 +366,25 @@ void resample_launch(const double* x, int64_t n, int64_t num, double* y, char* w
     dft_launch<0, 0>(s, n, -1, keep, X, nullptr, 0.0, b0, b1, b2, st);
     const double sc = (1.0 / (double)num) * ((double)num / (double)n);
     dft_launch<1, 1>(s, num, +1, num, nullptr, y, sc, b0, b1, b2, st);
+}
+
+// an item's workspace on the way out: item_layout's, then the row widened to fp64
+size_t store_bytes(int64_t len, int64_t num) { return item_layout(len, num).bytes + align16((size_t)len * sizeof(double)); }
+
+// one item of use_store_items_dev: row[0 ... len) -> dst[0 ... out_stride)
+template <typename DST>
+void store_launch(const float* row, int64_t len, int64_t num, DST* dst, int64_t out_stride, char* work, hipStream_t st) {
+    const dim3 grid((unsigned)((out_stride + LOAD_SLICE - 1) / LOAD_SLICE)), block(256);
+    if (len == num) {
+        hipLaunchKernelGGL((store_kernel<float, DST>), grid, block, 0, st, row, num, dst, out_stride);
+        return;
+    }
+    const ItemWork w = item_layout(len, num);
+    double* x = reinterpret_cast<double*>(work + w.bytes);
+    double* y = reinterpret_cast<double*>(work + w.y);
+    hipLaunchKernelGGL(store_widen_kernel, dim3(blocks256(len)), block, 0, st, row, len, x);
+    resample_launch(x, len, num, y, work, w, st);
+    hipLaunchKernelGGL((store_kernel<double, DST>), grid, block, 0, st, (const double*)y, num, dst, out_stride);
 }
 
 }  // namespace
@@ -419,5 +473,53 @@ int use_load_items_dev(const double* const* x_dev, const int64_t* n_host, const 
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return failf(USE_E_HIP, "use_load_items_dev: launch failed: %s", hipGetErrorString(e));
+    return USE_OK;
+}
+
+size_t use_store_workspace(int64_t len, int64_t num) {
+    if (!item_ok(len, num)) return 0;
+    return store_bytes(len, num);
+}
+
+int use_store_items_dev(const float* wav, int64_t stride, const int* len_host, const int64_t* num_host, int B, int subtype, void* out,
+                        int64_t out_stride, void* work, size_t work_bytes, use_stream_t s) {
+    if (B < 1) return failf(USE_E_INVALID, "use_store_items_dev: B=%d must be positive", B);
+    if (subtype != USE_WAV_PCM16 && subtype != USE_WAV_FLOAT32) return failf(USE_E_INVALID, "use_store_items_dev: unknown subtype %d", subtype);
+    if (!wav) return failf(USE_E_INVALID, "use_store_items_dev: wav is null");
+    if (!len_host) return failf(USE_E_INVALID, "use_store_items_dev: len_host is null");
+    if (!num_host) return failf(USE_E_INVALID, "use_store_items_dev: num_host is null");
+    if (!out) return failf(USE_E_INVALID, "use_store_items_dev: out is null");
+    if (!work) return failf(USE_E_INVALID, "use_store_items_dev: work is null");
+    if ((uintptr_t)wav & 3) return failf(USE_E_INVALID, "use_store_items_dev: wav must be 4-byte aligned");
+    const int bps = subtype == USE_WAV_PCM16 ? 2 : 4;
+    if ((uintptr_t)out & (uintptr_t)(bps - 1)) return failf(USE_E_INVALID, "use_store_items_dev: out must be %d-byte aligned", bps);
+    if ((uintptr_t)work & 15) return failf(USE_E_INVALID, "use_store_items_dev: work must be 16-byte aligned");
+    if (stride < 1) return failf(USE_E_INVALID, "use_store_items_dev: stride=%lld must be positive", (long long)stride);
+    if (out_stride < 1 || (out_stride + LOAD_SLICE - 1) / LOAD_SLICE > 0x7fffffff)
+        return failf(USE_E_INVALID, "use_store_items_dev: out_stride=%lld must be positive (and below 2^43)", (long long)out_stride);
+    for (int b = 0; b < B; ++b) {
+        const int64_t len = len_host[b], num = num_host[b];
+        if (len < 1 || num < 1)
+            return failf(USE_E_INVALID, "use_store_items_dev: len[%d]=%lld and num[%d]=%lld must be positive", b, (long long)len, b, (long long)num);
+        if (len > stride)
+            return failf(USE_E_INVALID, "use_store_items_dev: len[%d]=%lld is larger than stride=%lld", b, (long long)len, (long long)stride);
+        if (num > out_stride)
+            return failf(USE_E_INVALID, "use_store_items_dev: num[%d]=%lld is larger than out_stride=%lld", b, (long long)num, (long long)out_stride);
+        if (!item_ok(len, num))
+            return failf(USE_E_INVALID, "use_store_items_dev: max(len[%d], num[%d])=%lld exceeds 2^24", b, b, (long long)(len > num ? len : num));
+        const size_t need = store_bytes(len, num);
+        if (work_bytes < need)
+            return failf(USE_E_INVALID, "use_store_items_dev: work_bytes=%zu is smaller than use_store_workspace(%lld, %lld) = %zu (item %d)",
+                         work_bytes, (long long)len, (long long)num, need, b);
+    }
+    hipStream_t st = (hipStream_t)s;
+    char* base = static_cast<char*>(work);
+    for (int b = 0; b < B; ++b) {
+        const float* row = wav + (int64_t)b * stride;
+        if (subtype == USE_WAV_PCM16) store_launch(row, len_host[b], num_host[b], static_cast<int16_t*>(out) + (int64_t)b * out_stride, out_stride, base, st);
+        else store_launch(row, len_host[b], num_host[b], static_cast<float*>(out) + (int64_t)b * out_stride, out_stride, base, st);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return failf(USE_E_HIP, "use_store_items_dev: launch failed: %s", hipGetErrorString(e));
     return USE_OK;
 }

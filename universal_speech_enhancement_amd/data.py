@@ -11,7 +11,11 @@ batches of one plan shape; T' comes from the WAV headers (``wav_info`` + ``resam
 ``device_load`` (no reference counterpart, off by default): the host only decodes the files; resampling, peak normalisation, the cast
 and the zero-padded collation run on the device (``wavio.load_batch_device``).  The batch dict is the same; a resampled row is the host
 loader's to within the last float32 bit, a row at an unchanged rate is bit-equal.  A file of more than ``device_load_max_samples``
-samples (before or after resampling) takes the host path."""
+samples (before or after resampling) takes the host path.
+
+``restore_rate`` (no reference counterpart, off by default): every batch also carries ``source_rate`` and ``source_length``, the
+rate and frame count of each file as ``wav_info`` reports them, and the writers of the models (``SGMSE_module._write_items``) then
+write every output at its source's rate with exactly its frame count.  Off: the batch dict is what it always was."""
 from __future__ import annotations
 
 import os
@@ -27,11 +31,12 @@ from .wavio import load_batch_device, load_utterance, resampled_length, wav_info
 class LoadWavData:
     def __init__(self, data_folder: str, target_folder: str, normalize: bool = True, sampling_rate: int = 24000,
                  batch_size: int = 1, num_workers: int = 0, rank: int = 0, world_size: int = 1, bucket_by_length: bool = False,
-                 device_load: bool = False, device_load_max_samples: int = 2 ** 24, **ignored):
+                 device_load: bool = False, device_load_max_samples: int = 2 ** 24, restore_rate: bool = False, **ignored):
         self.data_folder, self.target_folder = data_folder, target_folder
         self.normalize, self.sampling_rate, self.batch_size = normalize, sampling_rate, batch_size
         self.bucket_by_length = bool(bucket_by_length)
         self.device_load, self.device_load_max_samples = bool(device_load), int(device_load_max_samples)
+        self.restore_rate = bool(restore_rate)
         files: List[str] = []
         for root, _, names in os.walk(data_folder):
             files += [os.path.join(root, n) for n in sorted(names) if n.endswith(".wav")]
@@ -73,8 +78,19 @@ class LoadWavData:
         if self.device_load:
             if torch.device(device).type != "cuda":
                 raise ValueError(f"device_load=True needs a CUDA (ROCm) device, got {device!r}: the device loader has no CPU implementation")
-            return self._device_batches(device, frame_hop)
-        return self._host_batches(device, frame_hop)
+            batches = self._device_batches(device, frame_hop)
+        else:
+            batches = self._host_batches(device, frame_hop)
+        return self._with_source(batches) if self.restore_rate else batches
+
+    @staticmethod
+    def _with_source(batches) -> Iterator[Dict]:
+        """``restore_rate``: every file's own rate and frame count, from its header."""
+        for batch in batches:
+            info = [wav_info(p) for p in batch["audio_path"]]
+            batch["source_rate"] = [sr for _, _, sr in info]
+            batch["source_length"] = [frames for frames, _, _ in info]
+            yield batch
 
     def _device_batches(self, device, frame_hop) -> Iterator[Dict]:
         for paths in self.batch_files(frame_hop):

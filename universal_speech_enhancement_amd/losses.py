@@ -126,13 +126,16 @@ class WavSpecConvergence_Loss(torch.nn.Module):
         return batch_data
 
 
-def score_files(enhanced_path: str, clean_path: str, sampling_rate: int = 24000, normalize: bool = True, device="cuda") -> Dict[str, float]:
+def score_files(enhanced_path: str, clean_path: str, sampling_rate: int = 24000, normalize: bool = True, device="cuda",
+                est=None) -> Dict[str, float]:
     """One row of ``losses.csv``: the written enhanced file (its samples as they are in the file) against the clean file through the
     inference loader (``wavio.load_utterance``: first channel, resampled to ``sampling_rate``, peak-normalised when ``normalize``), over
-    the shortest common length.  -> the six unweighted terms and ``total``, their ``LSGAN_ALPHAS``-weighted sum."""
+    the shortest common length.  -> the six unweighted terms and ``total``, their ``LSGAN_ALPHAS``-weighted sum.  ``est`` (float32
+    ``[n]``): the enhanced file's samples where the file itself is not at ``sampling_rate`` (``data.restore_rate``)."""
     from .wavio import load_utterance, read_wav
-    est, _ = read_wav(enhanced_path)
-    est = (est if est.ndim == 1 else est[:, 0]).astype(np.float32)
+    if est is None:
+        est, _ = read_wav(enhanced_path)
+        est = (est if est.ndim == 1 else est[:, 0]).astype(np.float32)
     clean, _ = load_utterance(clean_path, sampling_rate, normalize)
     n = min(len(est), len(clean))
     if n < min_length(sampling_rate):

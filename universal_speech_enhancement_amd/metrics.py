@@ -88,14 +88,16 @@ def evaluate(est: torch.Tensor, clean: torch.Tensor, noisy: torch.Tensor, length
 
 
 def score_files(enhanced_path: str, clean_path: str, noisy_path: str, sampling_rate: int = 24000, normalize: bool = True,
-                device="cuda") -> Dict[str, float]:
+                device="cuda", est=None) -> Dict[str, float]:
     """One row of ``metrics.csv``: the written enhanced file (its samples as they are in the file) against the clean file, with the
     noisy input as the noise source; clean and noisy through the inference loader (``wavio.load_utterance``: first channel,
     resampled to ``sampling_rate``, peak-normalised when ``normalize``).  Files of different lengths are scored over the shortest,
-    as the reference's ``si_sdr_torch`` does (``other.py:111-113``)."""
+    as the reference's ``si_sdr_torch`` does (``other.py:111-113``).  ``est`` (float32 ``[n]``): the enhanced file's samples where the
+    file itself is not at ``sampling_rate`` (``data.restore_rate``); ``enhanced_path`` then only names the row."""
     from .wavio import load_utterance, read_wav
-    est, _ = read_wav(enhanced_path)
-    est = (est if est.ndim == 1 else est[:, 0]).astype(np.float32)
+    if est is None:
+        est, _ = read_wav(enhanced_path)
+        est = (est if est.ndim == 1 else est[:, 0]).astype(np.float32)
     clean, _ = load_utterance(clean_path, sampling_rate, normalize)
     noisy, _ = load_utterance(noisy_path, sampling_rate, normalize)
     n = min(len(est), len(clean), len(noisy))

@@ -26,6 +26,11 @@
         [data.device_load=true]                  (the loader's FFT resampling, peak normalisation, cast and collation on the device instead
                                                   of file by file on the host, which then only decodes; off by default.  A resampled input
                                                   equals the host loader's to within the last float32 bit, one at an unchanged rate bit for bit)
+        [data.restore_rate=true]                 (every output file at its source's own sample rate and frame count instead of 24 kHz: the
+                                                  model-rate output is resampled back on the device, a batch per call, so that a file
+                                                  can take the place of its noisy one; off by default.  A source at 24 kHz gives the
+                                                  same bytes either way; model.stage1_folder files, metrics.csv and losses.csv stay at
+                                                  the model's rate; the loader's peak normalisation is not undone)
         [data.clean_folder=clean/]               (score every enhanced file whose clean counterpart exists under clean/ at the same
                                                   relative path: SI-SDR / SI-SIR / SI-SAR / LSD on the device -> enhanced/metrics.csv)
         [data.clean_folder=clean/ data.convergence_losses=true]
@@ -111,32 +116,43 @@ def instantiate(node, **extra):
     return node
 
 
-def _score_batch(batch: dict, clean_folder: str, data_cfg: dict, device):
+def _model_rate_samples(batch: dict, model):
+    """``data.restore_rate``: for every item the samples its file holds without the flag, read back (the 16-bit codes over 32768, or
+    the float32 samples) - what ``metrics.csv`` and ``losses.csv`` are computed from, so that the flag does not change them.  The
+    quantisation is the hand-off's (``handoff.wav_handoff`` without normalisation: bit for bit the file round trip)."""
+    from .handoff import wav_handoff
+    wavs = batch["fake" if hasattr(model, "G") else "enhanced"]
+    rows = wav_handoff(wavs.detach().float().contiguous(), batch["sample_length"], model.wav_subtype, normalize=False)[0].cpu().numpy()
+    return [rows[i, : int(n)] for i, n in enumerate(batch["sample_length"])]
+
+
+def _score_batch(batch: dict, clean_folder: str, data_cfg: dict, device, est=None):
     """``data.clean_folder``: (relative path, metrics) of every file of the batch whose clean counterpart exists - the enhanced file as
-    ``predict_step`` wrote it against the clean file, the noisy input as the noise source (``metrics.score_files``)."""
+    ``predict_step`` wrote it (``est``: its samples at the model's rate, item by item, where the files are not at that rate) against
+    the clean file, the noisy input as the noise source (``metrics.score_files``)."""
     from .metrics import score_files
     rows = []
-    for noisy_path in batch["audio_path"]:
+    for i, noisy_path in enumerate(batch["audio_path"]):
         rel = os.path.relpath(noisy_path, batch["data_folder"])
         clean_path = os.path.join(clean_folder, rel)
         if os.path.isfile(clean_path):
             enhanced_path = noisy_path.replace(batch["data_folder"], batch["target_folder"])
             rows.append((rel, score_files(enhanced_path, clean_path, noisy_path, int(data_cfg.get("sampling_rate", 24000) or 0),
-                                          bool(data_cfg.get("normalize", True)), device)))
+                                          bool(data_cfg.get("normalize", True)), device, None if est is None else est[i])))
     return rows
 
 
-def _loss_batch(batch: dict, clean_folder: str, data_cfg: dict, device):
+def _loss_batch(batch: dict, clean_folder: str, data_cfg: dict, device, est=None):
     """``data.convergence_losses``: (relative path, convergence losses) of the files ``_score_batch`` scores (``losses.score_files``)."""
     from .losses import score_files
     rows = []
-    for noisy_path in batch["audio_path"]:
+    for i, noisy_path in enumerate(batch["audio_path"]):
         rel = os.path.relpath(noisy_path, batch["data_folder"])
         clean_path = os.path.join(clean_folder, rel)
         if os.path.isfile(clean_path):
             enhanced_path = noisy_path.replace(batch["data_folder"], batch["target_folder"])
             rows.append((rel, score_files(enhanced_path, clean_path, int(data_cfg.get("sampling_rate", 24000) or 0),
-                                          bool(data_cfg.get("normalize", True)), device)))
+                                          bool(data_cfg.get("normalize", True)), device, None if est is None else est[i])))
     return rows
 
 
@@ -195,10 +211,11 @@ def predict(cfg: dict):
         for i, batch in enumerate(data.predict_batches(device=device, frame_hop=owner.hop_length)):
             model.predict_step(batch, i)
             n += len(batch["name"])
+            est = _model_rate_samples(batch, model) if clean_folder and "source_rate" in batch else None
             if clean_folder:
-                rows += _score_batch(batch, clean_folder, cfg["data"], device)
+                rows += _score_batch(batch, clean_folder, cfg["data"], device, est)
             if with_losses:
-                loss_rows += _loss_batch(batch, clean_folder, cfg["data"], device)
+                loss_rows += _loss_batch(batch, clean_folder, cfg["data"], device, est)
     if clean_folder:
         from .metrics import write_csv
         write_csv(os.path.join(cfg["data"]["target_folder"], "metrics.csv" if world == 1 else f"metrics_rank{rank}.csv"), rows)

@@ -5,7 +5,11 @@
 
 ``resample_fft_device`` / ``load_batch_device`` (``use_resample_fft_dev`` / ``use_load_items_dev``, csrc/use_resample.hip): the same
 resampling, peak normalisation, cast and the loader's zero-padded collation on the device; the host only decodes the files.  There is
-no CPU implementation of the two."""
+no CPU implementation of the two.
+
+``store_batch_device`` (``use_store_items_dev``, csrc/use_resample.hip): the way out - a batch of model-rate float32 rows on the device,
+resampled back to each file's own frame count and quantised to the writer's 16-bit codes (or kept as float32), one call and one copy per
+batch; ``store_items_host`` is the same arithmetic on the host, ``write_wav_pcm16`` (``use_wav_write_pcm16``) writes ready-made codes."""
 from __future__ import annotations
 
 import ctypes as C
@@ -164,3 +168,93 @@ def load_batch_device(paths, sampling_rate: int = 24000, normalize: bool = True,
                                            wav[b].data_ptr(), stride, work.data_ptr(), work.numel(), stream), "use_load_items_dev")
             b = e
     return wav, lens, rates
+
+
+def write_wav_pcm16(path: str, codes: np.ndarray, sample_rate: int) -> None:
+    """The 16-bit file ``write_wav`` writes, from ready-made codes (int16 ``[frames]`` or ``[frames, channels]``, ``use_wav_write_pcm16``)."""
+    a = np.ascontiguousarray(codes)
+    if a.dtype != np.int16:
+        raise TypeError(f"codes must be int16, got {a.dtype}")
+    frames, ch = (a.shape[0], 1) if a.ndim == 1 else a.shape
+    check(lib().use_wav_write_pcm16(os.fsencode(path), a.ctypes.data_as(C.c_void_p), frames, ch, int(sample_rate)), "use_wav_write_pcm16")
+
+
+def _store_args(wav, lens, nums, subtype):
+    if subtype not in (PCM16, FLOAT32):
+        raise ValueError(f"unknown subtype {subtype!r} (wavio.PCM16 or wavio.FLOAT32)")
+    if wav.dim() != 2:
+        raise ValueError(f"wav must be [B, L], got shape {tuple(wav.shape)}")
+    B, L = wav.shape
+    lens = np.asarray(lens.cpu() if hasattr(lens, "cpu") else lens, dtype=np.int64).reshape(-1)
+    nums = np.asarray(nums.cpu() if hasattr(nums, "cpu") else nums, dtype=np.int64).reshape(-1)
+    if lens.shape[0] != B or nums.shape[0] != B:
+        raise ValueError(f"lens has {lens.shape[0]} and nums {nums.shape[0]} entries for a batch of {B}")
+    if (lens < 1).any() or (lens > L).any() or (nums < 1).any():
+        raise ValueError(f"lens={lens.tolist()} must lie in 1 ... {L} (the width of the batch) and nums={nums.tolist()} must be positive")
+    return lens, nums
+
+
+def _quantise(x32: np.ndarray) -> np.ndarray:
+    """The 16-bit codes ``use_wav_write`` stores for float32 samples: ``nearbyint(float64(x) * 32767)``, NaN -> 0, clamped."""
+    v = np.rint(x32.astype(np.float64) * 32767.0)
+    v[np.isnan(v)] = 0.0
+    return np.clip(v, -32768.0, 32767.0).astype(np.int16)
+
+
+def store_items_host(wav, lens, nums, subtype: int = PCM16) -> np.ndarray:
+    """``store_batch_device`` on the host, for CPU tensors and for items beyond the device's 2^24 samples: item b's first ``lens[b]``
+    float32 samples -> float64 -> ``resample_fft`` to ``nums[b]`` samples (``nums[b] == lens[b]``: as they are) -> float32 -> the
+    16-bit code ``write_wav`` stores (``PCM16``) or the float32 itself (``FLOAT32``).  -> host ``[B, max(nums)]``, zero past ``nums[b]``."""
+    import torch
+    wav = torch.as_tensor(wav)
+    lens, nums = _store_args(wav, lens, nums, subtype)
+    out = np.zeros((wav.shape[0], int(nums.max())), np.int16 if subtype == PCM16 else np.float32)
+    for b, (n, num) in enumerate(zip(lens.tolist(), nums.tolist())):
+        x32 = wav[b, :n].detach().cpu().numpy().astype(np.float32)
+        if num != n:
+            x32 = resample_fft(x32.astype(np.float64), num).astype(np.float32)
+        out[b, :num] = _quantise(x32) if subtype == PCM16 else x32
+    return out
+
+
+def store_batch_device(wav, lens, nums, subtype: int = PCM16, max_samples: int = 2 ** 24) -> np.ndarray:
+    """The way out of a batch on the device (``use_store_items_dev``): ``wav`` float32 CUDA ``[B, L]``, item b valid for ``lens[b]``
+    samples (the rest of a row is never read) and resampled to ``nums[b]`` samples in fp64, then rounded to float32 and stored as it is
+    (``FLOAT32``) or as the 16-bit code ``write_wav`` stores (``PCM16``).  -> host array ``[B, max(nums)]`` (float32 / int16), zero past
+    ``nums[b]``: one call, one device-to-host copy, one synchronisation.  An item with more than ``max_samples`` samples before or after
+    resampling goes through ``store_items_host`` instead."""
+    import torch
+    if not isinstance(wav, torch.Tensor) or not wav.is_cuda:
+        raise UseHipError("wav must be a CUDA (ROCm) tensor: use store_items_host for a CPU tensor")
+    if wav.dtype != torch.float32:
+        raise TypeError(f"wav must be float32, got {wav.dtype}")
+    lens, nums = _store_args(wav, lens, nums, subtype)
+    if wav.stride(1) != 1 or wav.stride(0) < wav.shape[1]:
+        wav = wav.contiguous()
+    B, stride, out_stride = wav.shape[0], wav.stride(0), int(nums.max())
+    limit = min(int(max_samples), 2 ** 24)
+    host = [b for b in range(B) if max(lens[b], nums[b]) > limit]
+    dev = wav.device
+    with torch.cuda.device(dev):
+        out = torch.empty(B, out_stride, dtype=torch.int16 if subtype == PCM16 else torch.float32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        b = 0
+        while b < B:                                        # one call per run of rows that the device forms: one call without host rows
+            if b in host:
+                b += 1
+                continue
+            e = b
+            while e < B and e not in host:
+                e += 1
+            k = e - b
+            nbytes = max(lib().use_store_workspace(int(lens[i]), int(nums[i])) for i in range(b, e))
+            work = _workspace(dev, nbytes)
+            check(lib().use_store_items_dev(wav[b].data_ptr(), stride, (C.c_int * k)(*lens[b:e].tolist()), (C.c_int64 * k)(*nums[b:e].tolist()),
+                                            k, subtype, out[b].data_ptr(), out_stride, work.data_ptr(), work.numel(), stream),
+                  "use_store_items_dev")
+            b = e
+        res = out.cpu().numpy()
+    for b in host:
+        res[b] = 0
+        res[b, : nums[b]] = store_items_host(wav[b: b + 1], lens[b: b + 1], nums[b: b + 1], subtype)[0]
+    return res
