@@ -313,6 +313,18 @@ size_t use_wav_handoff_workspace(int B, int64_t stride);
 int use_wav_handoff(const float* in, float* out, int64_t stride, const int* len_host, int B, int subtype /* USE_WAV_PCM16 | USE_WAV_FLOAT32 */,
                     int normalize, void* work, size_t work_bytes, double* peak_dev, use_stream_t s);
 
+/* The hand-off for files of several channels (data.channels=all): the rows of in / out are the channels of F files one after another, file f
+ * holding ch_host[f] rows (1 ... 64) of len_host[f] valid samples each (HOST ints, one entry per FILE).  Every sample goes through the
+ * arithmetic of use_wav_handoff; with normalize, mx is taken over all rows of a file - one gain per file, as the loader gives a file of
+ * several channels - and a silent channel of a file that is not silent stays exact zeros.  peak_dev: fp64 DEVICE [F], one peak per file.
+ * With F = 1 and ch = 1 the call is use_wav_handoff's, bit for bit.  work: use_wav_handoff_files_workspace(rows, stride) bytes for rows =
+ * the sum of ch_host, 8-byte aligned (0: bad arguments).  The same launches, guarantees and refusals as use_wav_handoff; also refused:
+ * a null ch_host, ch[f] < 1 or > 64, more than 65535 rows in all. */
+size_t use_wav_handoff_files_workspace(int rows, int64_t stride);
+int use_wav_handoff_files(const float* in, float* out, int64_t stride, const int* len_host, const int* ch_host, int F,
+                          int subtype /* USE_WAV_PCM16 | USE_WAV_FLOAT32 */, int normalize, void* work, size_t work_bytes, double* peak_dev,
+                          use_stream_t s);
+
 /* The convergence part of the refine stage's generator criterion, forward only and handle-free (reference
  * loss_function/monaural_loss.py:59-178, WavSpecConvergence_Loss; the same arithmetic inside WavSpecConvergence_HIFIGAN_Vocoder_G_Loss, which
  * LSGAN.yaml selects).  est, clean: float32 DEVICE [B][stride], item b valid for len_host[b] samples (HOST ints, as in use_metrics; the rest of a
@@ -583,6 +595,30 @@ int use_store_items_dev(const float* wav, int64_t stride, const int* len_host, c
                         int subtype /* USE_WAV_PCM16 | USE_WAV_FLOAT32 */, void* out, int64_t out_stride, void* work, size_t work_bytes,
                         use_stream_t s);
 int use_wav_write_pcm16(const char* path, const int16_t* codes, int64_t frames, int channels, int sample_rate);
+
+/* Files of several channels on the device (data.channels=all; csrc/use_resample.hip), handle-free.
+ * use_load_files_dev: F files, x_dev[f] (HOST array of fp64 DEVICE pointers) the whole decoded file as use_wav_read returns it, interleaved
+ *   [n_host[f]][ch_host[f]].  A file's channels are de-interleaved, each is resampled to num_host[f] samples with the arithmetic (and the
+ *   passes) of use_resample_fft_dev, and with normalize ONE peak is taken per file: mx = max |v| over all ch * num values by `fabs(v) > mx`,
+ *   every channel v / mx * 0.8 with two roundings - the channels keep their level relation, a silent channel stays exact zeros, a silent
+ *   file gives NaN.  Channel c of file f is row (ch[0] + ... + ch[f - 1]) + c of wav (float32 DEVICE [rows][stride]), zero from num to
+ *   stride.  A file of one channel has the bits use_load_items_dev gives it.  work: use_load_files_workspace(n, num, channels) bytes for the
+ *   largest file, 16-byte aligned (0: n or num < 1 or above 2^24, channels < 1 or > 64; a host function).
+ * use_store_files_dev: the way back.  wav float32 DEVICE [rows][stride], file f's ch_host[f] rows valid for len_host[f] samples each; every
+ *   row goes through use_store_items_dev's arithmetic to num_host[f] samples (num == len: no transform), and the file is written interleaved,
+ *   [num][ch], at out + out_off_host[f] (an ELEMENT offset; out is int16_t or float by subtype): the layout use_wav_write_pcm16 and
+ *   use_wav_write store as it is.  Nothing outside the F blocks of num * ch elements is written.  work: use_store_workspace(len, num) bytes
+ *   for the largest file.
+ * The guarantees of use_load_items_dev / use_store_items_dev hold: launches on `s` only, no allocation, no synchronisation, no atomics,
+ * 64-bit row offsets, and a file's output has the same bits in every run, in any batch and at any stride.
+ * USE_E_INVALID (argument named in use_last_error(), nothing launched): a null or misaligned pointer, F < 1, ch[f] < 1 or > 64, n / len or
+ * num < 1 or above 2^24, stride < num (load) or < len (store), a negative out_off, an unknown subtype, work_bytes too small. */
+size_t use_load_files_workspace(int64_t n, int64_t num, int channels);
+int use_load_files_dev(const double* const* x_dev /* [F] device pointers, held on the host */, const int64_t* n_host, const int64_t* num_host,
+                       const int* ch_host, int F, int normalize, float* wav, int64_t stride, void* work, size_t work_bytes, use_stream_t s);
+int use_store_files_dev(const float* wav, int64_t stride, const int* len_host /* [F] */, const int64_t* num_host /* [F] */, const int* ch_host,
+                        const int64_t* out_off_host /* [F] element offset of file f in out */, int F,
+                        int subtype /* USE_WAV_PCM16 | USE_WAV_FLOAT32 */, void* out, void* work, size_t work_bytes, use_stream_t s);
 
 /* timesteps of the sampler, torch.linspace(1, t_eps, N) float32 semantics (sampling/__init__.py:63); host only */
 int use_timesteps(int N, float t_eps, float* out);

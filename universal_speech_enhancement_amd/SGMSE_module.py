@@ -46,6 +46,8 @@ def _write_items(batch: dict, wavs, folder, subtype: str, restore: bool = True):
     ``wavio.store_items_host``).  A file whose rate is the model's has the bytes it has without the keys."""
     if "audio_path" not in batch:
         return
+    if "file_rows" in batch:
+        return _write_files(batch, wavs, folder, subtype, restore and "source_rate" in batch and "source_length" in batch)
     if restore and "source_rate" in batch and "source_length" in batch:
         return _write_items_restored(batch, wavs, folder, subtype)
     for i, wav in enumerate(wavs):
@@ -73,6 +75,41 @@ def _write_items_restored(batch: dict, wavs, folder, subtype: str):
             wavio.write_wav_pcm16(path, rows[i, :num], int(batch["source_rate"][i]))
         else:
             wavio.write_wav(path, rows[i, :num], int(batch["source_rate"][i]), wavio.FLOAT32)
+
+
+def _write_files(batch: dict, wavs, folder, subtype: str, restored: bool):
+    """A batch of ``LoadWavData(channels="all")``: the rows ``file_rows[f] = (first row, C)`` are the channels of one file and go back
+    into one C-channel file, ``[frames, C]`` interleaved.  ``restored``: at the source's rate and frame count, the whole batch in one
+    device call and one copy (``wavio.store_batch_device(channels=...)``; a CPU batch through ``wavio.store_files_host``); otherwise the
+    rows trimmed to ``sample_length`` and stacked, through the writer ``_write_items`` uses.  A mono file has the bytes it has without
+    the key."""
+    from . import wavio
+    if subtype not in ("PCM_16", "FLOAT"):
+        raise ValueError(f"unsupported WAV subtype {subtype!r} (PCM_16 or FLOAT)")
+    code = wavio.PCM16 if subtype == "PCM_16" else wavio.FLOAT32
+    wavs = torch.as_tensor(wavs).detach()
+    first = [r for r, _ in batch["file_rows"]]
+    chans = [c for _, c in batch["file_rows"]]
+    lens = [int(batch["sample_length"][r]) for r in first]
+    if restored:
+        nums = [int(batch["source_length"][r]) for r in first]
+        wavs = wavs.float()
+        files = (wavio.store_batch_device(wavs, lens, nums, code, channels=chans) if wavs.is_cuda
+                 else wavio.store_files_host(wavs, lens, nums, chans, code))
+    else:
+        host = wavs.cpu().numpy().astype(np.float32)
+    for f, (r, c) in enumerate(batch["file_rows"]):
+        path = batch["audio_path"][r].replace(batch["data_folder"], folder)
+        os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+        if restored:
+            a = files[f] if c > 1 else files[f][:, 0]
+            if code == wavio.PCM16:
+                wavio.write_wav_pcm16(path, a, int(batch["source_rate"][r]))
+            else:
+                wavio.write_wav(path, a, int(batch["source_rate"][r]), wavio.FLOAT32)
+        else:
+            a = host[r, : lens[f]] if c == 1 else np.ascontiguousarray(host[r: r + c, : lens[f]].T)
+            _write_wav(path, a, batch["sampling_rate"][r], subtype)
 
 
 try:                                                     # reference: class SGMSEModule(LightningModule), SGMSE_module.py:10

@@ -65,14 +65,20 @@ class USEModule(_Base):
         """Adds ``enhanced`` (the sampler's output, untouched), ``fake`` (the refined batch) and ``handoff_peak`` (float64 [B]: every
         item's peak as the second run's loader would find it) and writes item i of ``fake`` to
         ``audio_path[i].replace(data_folder, target_folder)``."""
-        from .handoff import wav_handoff
+        from .handoff import wav_handoff, wav_handoff_files
         batch = self.Score.sample(batch, **_with_path_seeds(self.sampler_kwargs, batch))
         enhanced = batch["enhanced"]
         lengths = batch.get("sample_length")
         if self.stage1_folder:
             # at the model's rate whatever data.restore_rate says: these are the files the second run's loader reads
             _write_items(batch, enhanced, self.stage1_folder, self.handoff_subtype, restore=False)
-        wav, peaks = wav_handoff(enhanced, lengths, self.handoff_subtype, self.normalize)
+        if "file_rows" in batch:
+            # data.channels=all: the stage-1 files hold several channels and the second run's loader gives each ONE gain
+            # (handoff_peak then has one entry per file)
+            file_lengths = None if lengths is None else [int(lengths[r]) for r, _ in batch["file_rows"]]
+            wav, peaks = wav_handoff_files(enhanced, file_lengths, [c for _, c in batch["file_rows"]], self.handoff_subtype, self.normalize)
+        else:
+            wav, peaks = wav_handoff(enhanced, lengths, self.handoff_subtype, self.normalize)
         stage2 = {"perturbed": wav}
         if lengths is not None:
             stage2["sample_length"] = lengths

@@ -197,6 +197,11 @@ SYMBOLS = {
     "use_store_workspace": (C.c_size_t, [_i64, _i64]),
     "use_store_items_dev": (_i, [_vp, _i64, C.POINTER(_i), C.POINTER(_i64), _i, _i, _vp, _i64, _vp, C.c_size_t, _vp]),
     "use_wav_write_pcm16": (_i, [C.c_char_p, _vp, _i64, _i, _i]),
+    "use_load_files_workspace": (C.c_size_t, [_i64, _i64, _i]),
+    "use_load_files_dev": (_i, [C.POINTER(_vp), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i), _i, _i, _vp, _i64, _vp, C.c_size_t, _vp]),
+    "use_store_files_dev": (_i, [_vp, _i64, C.POINTER(_i), C.POINTER(_i64), C.POINTER(_i), C.POINTER(_i64), _i, _i, _vp, _vp, C.c_size_t, _vp]),
+    "use_wav_handoff_files_workspace": (C.c_size_t, [_i, _i64]),
+    "use_wav_handoff_files": (_i, [_vp, _vp, _i64, C.POINTER(_i), C.POINTER(_i), _i, _i, _i, _vp, C.c_size_t, _vp, _vp]),
 }
 
 

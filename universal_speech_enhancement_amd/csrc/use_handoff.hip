@@ -14,10 +14,13 @@
 //   scale  (nblk, B)  every workgroup re-reduces the ceil(len[b] / HANDOFF_SLICE) partials of its row, transforms its slice and zeroes
 //                     its part of the padding; slice 0 stores the peak.  A workgroup reads and writes its own slice only, so out == in
 //                     is allowed.
+// use_wav_handoff_files (data.channels=all): the rows are the channels of files, and the second run's loader gives a file ONE gain.  The
+// peak kernel is the same; the scale kernel re-reduces the partials of all rows of its file, and the file's first row stores the peak.
 // No atomics and nothing to zero-initialise: a captured graph replays as it is.  Rows start wherever b * stride puts them (odd
 // strides), so a slice is a scalar head up to the next 16-byte boundary, float4 loads, and a scalar tail.
 #include <cstdarg>
 #include <cstdio>
+#include <vector>
 
 #include "../../include/use_hip.h"
 #include "use_kernels.h"
@@ -88,10 +91,12 @@ __global__ __launch_bounds__(256) void handoff_peak_kernel(const float* in, cons
     if (tid == 0) part[(size_t)b * nblk + blockIdx.x] = mx;
 }
 
-template <int SUBTYPE, int NORM>
+// FILES (use_wav_handoff_files): row b belongs to a file of file_rows[b].y rows that starts at row file_rows[b].x and is file number
+// file_rows[b].z; the rows of a file have one length, the peak is taken over the partials of all of them and stored once per file
+template <int SUBTYPE, int NORM, int FILES = 0>
 __global__ __launch_bounds__(256) void handoff_scale_kernel(const float* in, float* out, const int* __restrict__ lens,
                                                             const double* __restrict__ part, double* __restrict__ peak, int64_t stride,
-                                                            int nblk) {
+                                                            int nblk, const int3* __restrict__ file_rows = nullptr) {
     __shared__ double sh[4];
     const int b = blockIdx.y, tid = threadIdx.x;
     const int64_t L = lens[b], lo = (int64_t)blockIdx.x * HANDOFF_SLICE;
@@ -102,10 +107,20 @@ __global__ __launch_bounds__(256) void handoff_scale_kernel(const float* in, flo
     double mx = 0.0;
     if ((NORM && n > 0) || blockIdx.x == 0) {
         const int np = (int)((L + HANDOFF_SLICE - 1) / HANDOFF_SLICE);
-        const double* q = part + (size_t)b * nblk;
-        for (int j = tid; j < np; j += 256) mx = q[j] > mx ? q[j] : mx;
-        mx = block_max(mx, sh);
-        if (blockIdx.x == 0 && tid == 0) peak[b] = mx;
+        if (FILES) {
+            const int3 fr = file_rows[b];
+            for (int c = 0; c < fr.y; ++c) {
+                const double* q = part + (size_t)(fr.x + c) * nblk;
+                for (int j = tid; j < np; j += 256) mx = q[j] > mx ? q[j] : mx;
+            }
+            mx = block_max(mx, sh);
+            if (blockIdx.x == 0 && tid == 0 && b == fr.x) peak[fr.z] = mx;
+        } else {
+            const double* q = part + (size_t)b * nblk;
+            for (int j = tid; j < np; j += 256) mx = q[j] > mx ? q[j] : mx;
+            mx = block_max(mx, sh);
+            if (blockIdx.x == 0 && tid == 0) peak[b] = mx;
+        }
     }
     auto conv = [&](float x) -> float {
         double v = handoff_decode<SUBTYPE>(x);
@@ -151,6 +166,14 @@ HandoffWork handoff_layout(int B, int64_t stride) {
 }
 bool handoff_shape_ok(int B, int64_t stride) {                // gridDim = (nblk, B)
     return B >= 1 && B <= 65535 && stride >= 1 && (stride + HANDOFF_SLICE - 1) / HANDOFF_SLICE <= 0x7fffffff;
+}
+// use_wav_handoff_files: behind lens[B] lie (first row, rows, file) of every row, then the partials
+constexpr int HANDOFF_MAX_CHANNELS = 64;
+HandoffWork handoff_files_layout(int B, int64_t stride) {
+    HandoffWork w = handoff_layout(B, stride);
+    w.part = ((size_t)B * 4 * sizeof(int) + 7) & ~(size_t)7;
+    w.bytes = w.part + (size_t)B * (size_t)w.nblk * sizeof(double);
+    return w;
 }
 
 }  // namespace
@@ -202,5 +225,69 @@ int use_wav_handoff(const float* in, float* out, int64_t stride, const int* len_
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return failf(USE_E_HIP, "use_wav_handoff: launch failed: %s", hipGetErrorString(e));
+    return USE_OK;
+}
+
+size_t use_wav_handoff_files_workspace(int rows, int64_t stride) {
+    if (!handoff_shape_ok(rows, stride)) return 0;
+    return handoff_files_layout(rows, stride).bytes;
+}
+
+int use_wav_handoff_files(const float* in, float* out, int64_t stride, const int* len_host, const int* ch_host, int F, int subtype,
+                          int normalize, void* work, size_t work_bytes, double* peak_dev, use_stream_t s) {
+    if (F < 1 || F > 65535) return failf(USE_E_INVALID, "use_wav_handoff_files: F=%d must lie in 1 ... 65535", F);
+    if (stride < 1 || (stride + HANDOFF_SLICE - 1) / HANDOFF_SLICE > 0x7fffffff)
+        return failf(USE_E_INVALID, "use_wav_handoff_files: stride=%lld must be positive (and below 2^45)", (long long)stride);
+    if (!in) return failf(USE_E_INVALID, "use_wav_handoff_files: in is null");
+    if (!out) return failf(USE_E_INVALID, "use_wav_handoff_files: out is null");
+    if (!len_host) return failf(USE_E_INVALID, "use_wav_handoff_files: len_host is null");
+    if (!ch_host) return failf(USE_E_INVALID, "use_wav_handoff_files: ch_host is null");
+    if (!work) return failf(USE_E_INVALID, "use_wav_handoff_files: work is null");
+    if (!peak_dev) return failf(USE_E_INVALID, "use_wav_handoff_files: peak_dev is null");
+    if (subtype != USE_WAV_PCM16 && subtype != USE_WAV_FLOAT32)
+        return failf(USE_E_INVALID, "use_wav_handoff_files: subtype=%d is neither USE_WAV_PCM16 nor USE_WAV_FLOAT32", subtype);
+    int64_t rows = 0;
+    for (int f = 0; f < F; ++f) {
+        if (len_host[f] < 1 || len_host[f] > stride)
+            return failf(USE_E_INVALID, "use_wav_handoff_files: len[%d]=%d must lie in 1 ... stride = %lld", f, len_host[f], (long long)stride);
+        if (ch_host[f] < 1 || ch_host[f] > HANDOFF_MAX_CHANNELS)
+            return failf(USE_E_INVALID, "use_wav_handoff_files: ch[%d]=%d must lie in 1 ... %d", f, ch_host[f], HANDOFF_MAX_CHANNELS);
+        rows += ch_host[f];
+    }
+    if (rows > 65535) return failf(USE_E_INVALID, "use_wav_handoff_files: the files hold %lld rows, more than 65535", (long long)rows);
+    const int B = (int)rows;
+    const HandoffWork w = handoff_files_layout(B, stride);
+    if (work_bytes < w.bytes)
+        return failf(USE_E_INVALID, "use_wav_handoff_files: work_bytes=%zu is smaller than use_wav_handoff_files_workspace(%d, %lld) = %zu",
+                     work_bytes, B, (long long)stride, w.bytes);
+    if ((uintptr_t)work & 7) return failf(USE_E_INVALID, "use_wav_handoff_files: work must be 8-byte aligned");
+    if (((uintptr_t)in | (uintptr_t)out) & 3) return failf(USE_E_INVALID, "use_wav_handoff_files: in and out must be 4-byte aligned");
+    if ((uintptr_t)peak_dev & 7) return failf(USE_E_INVALID, "use_wav_handoff_files: peak_dev must be 8-byte aligned");
+
+    hipStream_t st = (hipStream_t)s;
+    int* lens = static_cast<int*>(work);
+    int* rows_dev = lens + B;
+    double* part = reinterpret_cast<double*>(static_cast<char*>(work) + w.part);
+    std::vector<int> host((size_t)B * 4);                     // lens[B], then (first row, rows, file) of every row
+    for (int f = 0, b = 0; f < F; ++f)
+        for (int c = 0, first = b; c < ch_host[f]; ++c, ++b) {
+            host[(size_t)b] = len_host[f];
+            host[(size_t)B + 3 * (size_t)b] = first; host[(size_t)B + 3 * (size_t)b + 1] = ch_host[f]; host[(size_t)B + 3 * (size_t)b + 2] = f;
+        }
+    launch_item_lengths(lens, host.data(), 4 * B, st);        // kernel arguments: no copy, no synchronisation
+    const int3* fr = reinterpret_cast<const int3*>(rows_dev);
+    const int nblk = (int)w.nblk;
+    const dim3 grid(nblk, B), block(256);
+    if (subtype == USE_WAV_PCM16) {
+        hipLaunchKernelGGL(handoff_peak_kernel<USE_WAV_PCM16>, grid, block, 0, st, in, lens, part, stride, nblk);
+        if (normalize) hipLaunchKernelGGL((handoff_scale_kernel<USE_WAV_PCM16, 1, 1>), grid, block, 0, st, in, out, lens, part, peak_dev, stride, nblk, fr);
+        else hipLaunchKernelGGL((handoff_scale_kernel<USE_WAV_PCM16, 0, 1>), grid, block, 0, st, in, out, lens, part, peak_dev, stride, nblk, fr);
+    } else {
+        hipLaunchKernelGGL(handoff_peak_kernel<USE_WAV_FLOAT32>, grid, block, 0, st, in, lens, part, stride, nblk);
+        if (normalize) hipLaunchKernelGGL((handoff_scale_kernel<USE_WAV_FLOAT32, 1, 1>), grid, block, 0, st, in, out, lens, part, peak_dev, stride, nblk, fr);
+        else hipLaunchKernelGGL((handoff_scale_kernel<USE_WAV_FLOAT32, 0, 1>), grid, block, 0, st, in, out, lens, part, peak_dev, stride, nblk, fr);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return failf(USE_E_HIP, "use_wav_handoff_files: launch failed: %s", hipGetErrorString(e));
     return USE_OK;
 }

@@ -25,6 +25,13 @@
 // to its length only, is widened to fp64, resampled to the file's frame count, rounded to float32 and stored as it is or as the 16-bit
 // code use_wav_write would store, with zeros up to the row's end.  At an unchanged length no transform runs and the row's bits pass.
 //
+// Files of several channels (use_load_files_dev / use_store_files_dev; data.channels=all): the host uploads a whole decoded file,
+// interleaved [n][ch].  On the way in it is de-interleaved into ch contiguous fp64 channels, each goes through resample_launch as an
+// item does, and the peak is ONE per file: the slice kernel runs over the ch * num contiguous values, one workgroup takes the maximum
+// of its partials (a maximum has no order: fixed shape, no atomics), and the scale kernel writes the file's rows under that one gain.
+// On the way out every row of a file takes store_launch's steps and is stored with stride ch, so that the file lies in `out` as
+// [num][ch], the order of the samples in a WAV file.  A file of one channel has the bits of the per-item calls.
+//
 // The bodies of the kernels are __host__ __device__ functions of the thread index (one per phase between two barriers), so that a
 // host program can run the same arithmetic without a device.
 #include <cstdarg>
@@ -297,6 +304,36 @@ __global__ __launch_bounds__(256) void store_kernel(const SRC* __restrict__ v, i
     }
 }
 
+// ---- files of several channels (use_load_files_dev / use_store_files_dev) ----
+// interleaved frames x[t * ch + c] -> ch contiguous channels out[c * n + t]; one thread per output element (count = n * ch)
+__global__ __launch_bounds__(256) void deinterleave_kernel(const double* __restrict__ x, int64_t n, int ch, int64_t count,
+                                                           double* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    const int64_t c = i / n, t = i - c * n;
+    out[i] = x[t * ch + c];
+}
+
+// one workgroup: fin[0] = the maximum of the np partial maxima of load_peak_kernel
+__global__ __launch_bounds__(256) void load_peak_final_kernel(const double* __restrict__ part, int np, double* __restrict__ fin) {
+    __shared__ double sh[4];
+    double mx = 0.0;
+    for (int j = threadIdx.x; j < np; j += 256) mx = part[j] > mx ? part[j] : mx;
+    mx = block_max(mx, sh);
+    if (threadIdx.x == 0) fin[0] = mx;
+}
+
+// store_kernel's sample for one channel of an interleaved file: dst[i * ch] = x32 = (float)v[i] or its 16-bit code, i < num (dst points
+// at the channel's first sample)
+template <typename SRC, typename DST>
+__global__ __launch_bounds__(256) void store_interleave_kernel(const SRC* __restrict__ v, int64_t num, DST* __restrict__ dst, int ch) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= num) return;
+    const float x32 = (float)v[i];
+    if constexpr (sizeof(DST) == 2) dst[i * ch] = pcm16_code(x32);
+    else dst[i * ch] = x32;
+}
+
 int failf(int code, const char* fmt, ...) {
     char buf[512];
     va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
@@ -385,6 +422,72 @@ void store_launch(const float* row, int64_t len, int64_t num, DST* dst, int64_t 
     hipLaunchKernelGGL(store_widen_kernel, dim3(blocks256(len)), block, 0, st, row, len, x);
     resample_launch(x, len, num, y, work, w, st);
     hipLaunchKernelGGL((store_kernel<double, DST>), grid, block, 0, st, (const double*)y, num, dst, out_stride);
+}
+
+// a file's workspace in use_load_files_dev: item_layout's (the transforms of one channel at a time), the partial maxima of all ch * num
+// values and their maximum, the ch de-interleaved channels (ch > 1), the ch resampled channels one after another (n != num)
+constexpr int FILE_MAX_CHANNELS = 64;
+struct FileWork { ItemWork item; size_t part, fin, chan, ys, bytes; int np; };
+bool channels_ok(int ch) { return ch >= 1 && ch <= FILE_MAX_CHANNELS; }
+FileWork file_layout(int64_t n, int64_t num, int ch) {
+    FileWork w;
+    w.item = item_layout(n, num);
+    w.np = (int)(((int64_t)ch * num + LOAD_SLICE - 1) / LOAD_SLICE);       // at most 64 * 2^24 / 4096 = 2^18
+    w.part = align16(w.item.bytes);
+    w.fin = w.part + align16((size_t)w.np * sizeof(double));
+    w.chan = w.fin + 16;
+    w.ys = w.chan + (ch > 1 ? align16((size_t)ch * (size_t)n * sizeof(double)) : 0);
+    w.bytes = w.ys + (n != num ? align16((size_t)ch * (size_t)num * sizeof(double)) : 0);
+    return w;
+}
+
+// one file of use_load_files_dev: x (interleaved [n][ch]) -> rows wav[0 ... ch) of width stride
+void load_file_launch(const double* x, int64_t n, int64_t num, int ch, int normalize, float* wav, int64_t stride, char* work, hipStream_t st) {
+    const FileWork w = file_layout(n, num, ch);
+    const dim3 block(256);
+    const double* v = x;                                          // ch contiguous channels of num samples
+    if (ch > 1) {
+        double* chan = reinterpret_cast<double*>(work + w.chan);
+        const int64_t count = (int64_t)ch * n;
+        hipLaunchKernelGGL(deinterleave_kernel, dim3(blocks256(count)), block, 0, st, x, n, ch, count, chan);
+        v = chan;
+    }
+    if (n != num) {
+        double* ys = reinterpret_cast<double*>(work + w.ys);
+        for (int c = 0; c < ch; ++c) resample_launch(v + (int64_t)c * n, n, num, ys + (int64_t)c * num, work, w.item, st);
+        v = ys;
+    }
+    double* part = reinterpret_cast<double*>(work + w.part);
+    double* fin = reinterpret_cast<double*>(work + w.fin);
+    if (normalize) {                                              // one peak over the file: the channels keep their level relation
+        hipLaunchKernelGGL(load_peak_kernel, dim3(w.np), block, 0, st, v, (int64_t)ch * num, part);
+        hipLaunchKernelGGL(load_peak_final_kernel, dim3(1), block, 0, st, (const double*)part, w.np, fin);
+    }
+    const dim3 grid((unsigned)((stride + LOAD_SLICE - 1) / LOAD_SLICE));
+    for (int c = 0; c < ch; ++c) {
+        float* row = wav + (int64_t)c * stride;
+        if (normalize) hipLaunchKernelGGL(load_scale_kernel<1>, grid, block, 0, st, v + (int64_t)c * num, num, (const double*)fin, 1, row, stride);
+        else hipLaunchKernelGGL(load_scale_kernel<0>, grid, block, 0, st, v + (int64_t)c * num, num, (const double*)fin, 1, row, stride);
+    }
+}
+
+// one file of use_store_files_dev: rows wav[0 ... ch) of width stride, valid for len -> dst[num][ch]; a row goes the way of store_launch
+template <typename DST>
+void store_file_launch(const float* wav, int64_t stride, int64_t len, int64_t num, int ch, DST* dst, char* work, hipStream_t st) {
+    const dim3 grid(blocks256(num)), block(256);
+    const ItemWork w = item_layout(len, num);
+    double* x = reinterpret_cast<double*>(work + w.bytes);
+    double* y = reinterpret_cast<double*>(work + w.y);
+    for (int c = 0; c < ch; ++c) {
+        const float* row = wav + (int64_t)c * stride;
+        if (len == num) {
+            hipLaunchKernelGGL((store_interleave_kernel<float, DST>), grid, block, 0, st, row, num, dst + c, ch);
+            continue;
+        }
+        hipLaunchKernelGGL(store_widen_kernel, dim3(blocks256(len)), block, 0, st, row, len, x);
+        resample_launch(x, len, num, y, work, w, st);
+        hipLaunchKernelGGL((store_interleave_kernel<double, DST>), grid, block, 0, st, (const double*)y, num, dst + c, ch);
+    }
 }
 
 }  // namespace
@@ -521,5 +624,95 @@ int use_store_items_dev(const float* wav, int64_t stride, const int* len_host, c
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return failf(USE_E_HIP, "use_store_items_dev: launch failed: %s", hipGetErrorString(e));
+    return USE_OK;
+}
+
+size_t use_load_files_workspace(int64_t n, int64_t num, int channels) {
+    if (!item_ok(n, num) || !channels_ok(channels)) return 0;
+    return file_layout(n, num, channels).bytes;
+}
+
+int use_load_files_dev(const double* const* x_dev, const int64_t* n_host, const int64_t* num_host, const int* ch_host, int F, int normalize,
+                       float* wav, int64_t stride, void* work, size_t work_bytes, use_stream_t s) {
+    if (F < 1) return failf(USE_E_INVALID, "use_load_files_dev: F=%d must be positive", F);
+    if (!x_dev) return failf(USE_E_INVALID, "use_load_files_dev: x_dev is null");
+    if (!n_host) return failf(USE_E_INVALID, "use_load_files_dev: n_host is null");
+    if (!num_host) return failf(USE_E_INVALID, "use_load_files_dev: num_host is null");
+    if (!ch_host) return failf(USE_E_INVALID, "use_load_files_dev: ch_host is null");
+    if (!wav) return failf(USE_E_INVALID, "use_load_files_dev: wav is null");
+    if (!work) return failf(USE_E_INVALID, "use_load_files_dev: work is null");
+    if ((uintptr_t)work & 15) return failf(USE_E_INVALID, "use_load_files_dev: work must be 16-byte aligned");
+    if ((uintptr_t)wav & 3) return failf(USE_E_INVALID, "use_load_files_dev: wav must be 4-byte aligned");
+    if (stride < 1 || (stride + LOAD_SLICE - 1) / LOAD_SLICE > 0x7fffffff)
+        return failf(USE_E_INVALID, "use_load_files_dev: stride=%lld must be positive (and below 2^43)", (long long)stride);
+    for (int f = 0; f < F; ++f) {
+        const int64_t n = n_host[f], num = num_host[f];
+        if (!channels_ok(ch_host[f])) return failf(USE_E_INVALID, "use_load_files_dev: ch[%d]=%d must lie in 1 ... %d", f, ch_host[f], FILE_MAX_CHANNELS);
+        if (n < 1 || num < 1)
+            return failf(USE_E_INVALID, "use_load_files_dev: n[%d]=%lld and num[%d]=%lld must be positive", f, (long long)n, f, (long long)num);
+        if (!item_ok(n, num))
+            return failf(USE_E_INVALID, "use_load_files_dev: max(n[%d], num[%d])=%lld exceeds 2^24", f, f, (long long)(n > num ? n : num));
+        if (!x_dev[f] || ((uintptr_t)x_dev[f] & 7)) return failf(USE_E_INVALID, "use_load_files_dev: x_dev[%d] is null or not 8-byte aligned", f);
+        if (stride < num)
+            return failf(USE_E_INVALID, "use_load_files_dev: stride=%lld is smaller than num[%d]=%lld", (long long)stride, f, (long long)num);
+        const size_t need = file_layout(n, num, ch_host[f]).bytes;
+        if (work_bytes < need)
+            return failf(USE_E_INVALID, "use_load_files_dev: work_bytes=%zu is smaller than use_load_files_workspace(%lld, %lld, %d) = %zu (file %d)",
+                         work_bytes, (long long)n, (long long)num, ch_host[f], need, f);
+    }
+    hipStream_t st = (hipStream_t)s;
+    int64_t row0 = 0;                                              // file f's rows: row0 ... row0 + ch[f] - 1
+    for (int f = 0; f < F; ++f) {
+        load_file_launch(x_dev[f], n_host[f], num_host[f], ch_host[f], normalize, wav + row0 * stride, stride, static_cast<char*>(work), st);
+        row0 += ch_host[f];
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return failf(USE_E_HIP, "use_load_files_dev: launch failed: %s", hipGetErrorString(e));
+    return USE_OK;
+}
+
+int use_store_files_dev(const float* wav, int64_t stride, const int* len_host, const int64_t* num_host, const int* ch_host,
+                        const int64_t* out_off_host, int F, int subtype, void* out, void* work, size_t work_bytes, use_stream_t s) {
+    if (F < 1) return failf(USE_E_INVALID, "use_store_files_dev: F=%d must be positive", F);
+    if (subtype != USE_WAV_PCM16 && subtype != USE_WAV_FLOAT32) return failf(USE_E_INVALID, "use_store_files_dev: unknown subtype %d", subtype);
+    if (!wav) return failf(USE_E_INVALID, "use_store_files_dev: wav is null");
+    if (!len_host) return failf(USE_E_INVALID, "use_store_files_dev: len_host is null");
+    if (!num_host) return failf(USE_E_INVALID, "use_store_files_dev: num_host is null");
+    if (!ch_host) return failf(USE_E_INVALID, "use_store_files_dev: ch_host is null");
+    if (!out_off_host) return failf(USE_E_INVALID, "use_store_files_dev: out_off_host is null");
+    if (!out) return failf(USE_E_INVALID, "use_store_files_dev: out is null");
+    if (!work) return failf(USE_E_INVALID, "use_store_files_dev: work is null");
+    if ((uintptr_t)wav & 3) return failf(USE_E_INVALID, "use_store_files_dev: wav must be 4-byte aligned");
+    const int bps = subtype == USE_WAV_PCM16 ? 2 : 4;
+    if ((uintptr_t)out & (uintptr_t)(bps - 1)) return failf(USE_E_INVALID, "use_store_files_dev: out must be %d-byte aligned", bps);
+    if ((uintptr_t)work & 15) return failf(USE_E_INVALID, "use_store_files_dev: work must be 16-byte aligned");
+    if (stride < 1) return failf(USE_E_INVALID, "use_store_files_dev: stride=%lld must be positive", (long long)stride);
+    for (int f = 0; f < F; ++f) {
+        const int64_t len = len_host[f], num = num_host[f];
+        if (!channels_ok(ch_host[f])) return failf(USE_E_INVALID, "use_store_files_dev: ch[%d]=%d must lie in 1 ... %d", f, ch_host[f], FILE_MAX_CHANNELS);
+        if (len < 1 || num < 1)
+            return failf(USE_E_INVALID, "use_store_files_dev: len[%d]=%lld and num[%d]=%lld must be positive", f, (long long)len, f, (long long)num);
+        if (len > stride)
+            return failf(USE_E_INVALID, "use_store_files_dev: len[%d]=%lld is larger than stride=%lld", f, (long long)len, (long long)stride);
+        if (!item_ok(len, num))
+            return failf(USE_E_INVALID, "use_store_files_dev: max(len[%d], num[%d])=%lld exceeds 2^24", f, f, (long long)(len > num ? len : num));
+        if (out_off_host[f] < 0) return failf(USE_E_INVALID, "use_store_files_dev: out_off[%d]=%lld must not be negative", f, (long long)out_off_host[f]);
+        const size_t need = store_bytes(len, num);
+        if (work_bytes < need)
+            return failf(USE_E_INVALID, "use_store_files_dev: work_bytes=%zu is smaller than use_store_workspace(%lld, %lld) = %zu (file %d)",
+                         work_bytes, (long long)len, (long long)num, need, f);
+    }
+    hipStream_t st = (hipStream_t)s;
+    char* base = static_cast<char*>(work);
+    int64_t row0 = 0;
+    for (int f = 0; f < F; ++f) {
+        const float* rows = wav + row0 * stride;
+        if (subtype == USE_WAV_PCM16)
+            store_file_launch(rows, stride, len_host[f], num_host[f], ch_host[f], static_cast<int16_t*>(out) + out_off_host[f], base, st);
+        else store_file_launch(rows, stride, len_host[f], num_host[f], ch_host[f], static_cast<float*>(out) + out_off_host[f], base, st);
+        row0 += ch_host[f];
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return failf(USE_E_HIP, "use_store_files_dev: launch failed: %s", hipGetErrorString(e));
     return USE_OK;
 }

@@ -15,7 +15,20 @@ samples (before or after resampling) takes the host path.
 
 ``restore_rate`` (no reference counterpart, off by default): every batch also carries ``source_rate`` and ``source_length``, the
 rate and frame count of each file as ``wav_info`` reports them, and the writers of the models (``SGMSE_module._write_items``) then
-write every output at its source's rate with exactly its frame count.  Off: the batch dict is what it always was."""
+write every output at its source's rate with exactly its frame count.  Off: the batch dict is what it always was.
+
+``channels`` (no reference counterpart; ``first`` by default: the reference's loader, which keeps the first channel of a file and drops the
+rest).  ``all``: a file of C channels gives C consecutive rows of the batch, in channel order, and the writers put them back together as
+one C-channel file.  The rules:
+  whole files   a batch holds whole files only: files are taken in the usual order while the row count stays <= ``batch_size``; a file of
+                more channels than that is a batch of its own.  ``bucket_by_length`` orders the files as before (T' comes from the header
+                and is the same for every channel of a file); sharding over ranks stays per file.
+  one gain      the peak normalisation is one gain per file, taken over all channels after resampling (``wavio.load_file_channels``), so
+                that the channels keep their level relation; a mono file gets the bits it gets with ``first``.
+  one seed      ``audio_path``, ``name``, ``sample_length`` and ``sampling_rate`` repeat for the rows of a file, so the ``per_item``
+                seeds, which are named by the path, are shared by its channels: equal channels come out equal.  Without ``per_item`` the
+                shared noise stream gives every row different noise.
+The batch gains ``channel`` and ``n_channels`` (per row) and ``file_rows`` (per file: ``(first row, C)``)."""
 from __future__ import annotations
 
 import os
@@ -25,18 +38,20 @@ import numpy as np
 import torch
 
 from .distributed import shard_list
-from .wavio import load_batch_device, load_utterance, resampled_length, wav_info
+from .wavio import check_channels, load_batch_device, load_file_channels, load_utterance, resampled_length, wav_info
 
 
 class LoadWavData:
     def __init__(self, data_folder: str, target_folder: str, normalize: bool = True, sampling_rate: int = 24000,
                  batch_size: int = 1, num_workers: int = 0, rank: int = 0, world_size: int = 1, bucket_by_length: bool = False,
-                 device_load: bool = False, device_load_max_samples: int = 2 ** 24, restore_rate: bool = False, **ignored):
+                 device_load: bool = False, device_load_max_samples: int = 2 ** 24, restore_rate: bool = False, channels: str = "first",
+                 **ignored):
         self.data_folder, self.target_folder = data_folder, target_folder
         self.normalize, self.sampling_rate, self.batch_size = normalize, sampling_rate, batch_size
         self.bucket_by_length = bool(bucket_by_length)
         self.device_load, self.device_load_max_samples = bool(device_load), int(device_load_max_samples)
         self.restore_rate = bool(restore_rate)
+        self.channels = check_channels(channels)
         files: List[str] = []
         for root, _, names in os.walk(data_folder):
             files += [os.path.join(root, n) for n in sorted(names) if n.endswith(".wav")]
@@ -58,30 +73,61 @@ class LoadWavData:
     def batch_files(self, frame_hop=None) -> List[List[str]]:
         """The file lists of the batches ``predict_batches`` yields, in its order.  Default: consecutive ``batch_size`` files of the
         shard.  ``bucket_by_length``: the shard ordered by (T', path relative to ``data_folder``), cut where T' changes or a batch is
-        full - a batch never mixes two values of T'; the same on every call."""
-        if not self.bucket_by_length:
+        full - a batch never mixes two values of T'; the same on every call.  ``channels="all"``: a file counts as many rows as it has
+        channels (from its header) and a batch is full at ``batch_size`` rows; a file of more channels than that is a batch of its own."""
+        if not self.bucket_by_length and self.channels == "first":
             return [self.filepaths[i:i + self.batch_size] for i in range(0, len(self.filepaths), self.batch_size)]
-        if frame_hop is None:
+        if self.bucket_by_length and frame_hop is None:
             raise ValueError("bucket_by_length needs frame_hop (the model's hop_length): predict_batches(device, frame_hop=...)")
-        keyed = sorted((self.padded_frames(p, frame_hop), os.path.relpath(p, self.data_folder).replace(os.sep, "/"), p)
-                       for p in self.filepaths)
+        if self.bucket_by_length:
+            keyed = sorted((self.padded_frames(p, frame_hop), os.path.relpath(p, self.data_folder).replace(os.sep, "/"), p)
+                           for p in self.filepaths)
+        else:
+            keyed = [(None, None, p) for p in self.filepaths]
         batches: List[List[str]] = []
-        last = None
+        last, rows = None, 0
         for Tp, _, p in keyed:
-            if Tp != last or len(batches[-1]) >= self.batch_size:
+            c = wav_info(p)[1] if self.channels == "all" else 1
+            if not batches or Tp != last or rows + c > self.batch_size:
                 batches.append([])
-                last = Tp
+                last, rows = Tp, 0
             batches[-1].append(p)
+            rows += c
         return batches
 
     def predict_batches(self, device="cuda", frame_hop=None) -> Iterator[Dict]:
         if self.device_load:
             if torch.device(device).type != "cuda":
                 raise ValueError(f"device_load=True needs a CUDA (ROCm) device, got {device!r}: the device loader has no CPU implementation")
-            batches = self._device_batches(device, frame_hop)
+            batches = self._device_batches(device, frame_hop) if self.channels == "first" else self._channel_batches(device, frame_hop)
         else:
-            batches = self._host_batches(device, frame_hop)
+            batches = self._host_batches(device, frame_hop) if self.channels == "first" else self._channel_batches(device, frame_hop)
         return self._with_source(batches) if self.restore_rate else batches
+
+    def _channel_batches(self, device, frame_hop) -> Iterator[Dict]:
+        """``channels="all"``: the rows of a batch are the channels of its files, file after file."""
+        for paths in self.batch_files(frame_hop):
+            if self.device_load:
+                wav, lens, rates, chans = load_batch_device(paths, self.sampling_rate, self.normalize, device, self.device_load_max_samples,
+                                                            channels="all")
+            else:
+                files = [load_file_channels(p, self.sampling_rate, self.normalize) for p in paths]
+                chans = [x.shape[0] for x, _ in files]
+                lens = np.repeat(np.array([x.shape[1] for x, _ in files], dtype=np.int32), chans)
+                rates = [sr for (_, sr), c in zip(files, chans) for _ in range(c)]
+                wav = torch.zeros(int(sum(chans)), int(lens.max()))
+                row = 0
+                for x, _ in files:
+                    wav[row: row + x.shape[0], : x.shape[1]] = torch.from_numpy(x)
+                    row += x.shape[0]
+                wav = wav.to(device)
+            rows = [p for p, c in zip(paths, chans) for _ in range(c)]
+            first = np.concatenate([[0], np.cumsum(chans)])[:-1]
+            yield {"perturbed": wav, "name": [os.path.basename(p).split(".wav")[0] for p in rows],
+                   "sample_length": torch.from_numpy(lens), "sampling_rate": rates, "audio_path": rows,
+                   "data_folder": self.data_folder, "target_folder": self.target_folder,
+                   "channel": [k for c in chans for k in range(c)], "n_channels": [c for c in chans for _ in range(c)],
+                   "file_rows": [(int(r), int(c)) for r, c in zip(first, chans)]}
 
     @staticmethod
     def _with_source(batches) -> Iterator[Dict]:

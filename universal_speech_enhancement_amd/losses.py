@@ -127,16 +127,20 @@ class WavSpecConvergence_Loss(torch.nn.Module):
 
 
 def score_files(enhanced_path: str, clean_path: str, sampling_rate: int = 24000, normalize: bool = True, device="cuda",
-                est=None) -> Dict[str, float]:
+                est=None, channel=None) -> Dict[str, float]:
     """One row of ``losses.csv``: the written enhanced file (its samples as they are in the file) against the clean file through the
     inference loader (``wavio.load_utterance``: first channel, resampled to ``sampling_rate``, peak-normalised when ``normalize``), over
     the shortest common length.  -> the six unweighted terms and ``total``, their ``LSGAN_ALPHAS``-weighted sum.  ``est`` (float32
-    ``[n]``): the enhanced file's samples where the file itself is not at ``sampling_rate`` (``data.restore_rate``)."""
-    from .wavio import load_utterance, read_wav
+    ``[n]``): the enhanced file's samples where the file itself is not at ``sampling_rate`` (``data.restore_rate``).  ``channel`` c
+    (``data.channels=all``): channel c of the enhanced file against channel c of the clean file (``wavio.load_file_channels``)."""
+    from .wavio import load_file_channels, load_utterance, read_wav
     if est is None:
         est, _ = read_wav(enhanced_path)
-        est = (est if est.ndim == 1 else est[:, 0]).astype(np.float32)
-    clean, _ = load_utterance(clean_path, sampling_rate, normalize)
+        est = (est if est.ndim == 1 else est[:, channel or 0]).astype(np.float32)
+    if channel is None:
+        clean, _ = load_utterance(clean_path, sampling_rate, normalize)
+    else:
+        clean = load_file_channels(clean_path, sampling_rate, normalize)[0][channel]
     n = min(len(est), len(clean))
     if n < min_length(sampling_rate):
         raise ValueError(f"{enhanced_path}: {n} common samples, the convergence losses need at least {min_length(sampling_rate)}")
@@ -146,15 +150,17 @@ def score_files(enhanced_path: str, clean_path: str, sampling_rate: int = 24000,
     return row
 
 
-def write_csv(path: str, rows: Sequence[Tuple[str, Dict[str, float]]]) -> None:
+def write_csv(path: str, rows: Sequence[Tuple], channel_column: bool = False) -> None:
     """``file, wav_l1, mag_l2, mag_log, mag_norm_l2, mel_log, mel_l2, total``: one row per file and a last row ``mean``; values as
-    ``repr(float)`` (they read back as the same float64)."""
+    ``repr(float)`` (they read back as the same float64).  ``channel_column`` (``data.channels=all``): rows are ``(file, channel,
+    losses)`` and a ``channel`` column follows ``file`` (empty in the ``mean`` row)."""
     cols = NAMES + ("total",)
+    lead = ("file", "channel") if channel_column else ("file",)
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
-        w.writerow(("file",) + cols)
-        for name, r in rows:
-            w.writerow([name] + [repr(float(r[k])) for k in cols])
+        w.writerow(lead + cols)
+        for *name, r in rows:
+            w.writerow(list(name) + [repr(float(r[k])) for k in cols])
         if rows:
-            w.writerow(["mean"] + [repr(float(np.mean([r[k] for _, r in rows]))) for k in cols])
+            w.writerow(["mean"] + [""] * (len(lead) - 1) + [repr(float(np.mean([row[-1][k] for row in rows]))) for k in cols])

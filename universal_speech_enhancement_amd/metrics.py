@@ -88,18 +88,24 @@ def evaluate(est: torch.Tensor, clean: torch.Tensor, noisy: torch.Tensor, length
 
 
 def score_files(enhanced_path: str, clean_path: str, noisy_path: str, sampling_rate: int = 24000, normalize: bool = True,
-                device="cuda", est=None) -> Dict[str, float]:
+                device="cuda", est=None, channel=None) -> Dict[str, float]:
     """One row of ``metrics.csv``: the written enhanced file (its samples as they are in the file) against the clean file, with the
     noisy input as the noise source; clean and noisy through the inference loader (``wavio.load_utterance``: first channel,
     resampled to ``sampling_rate``, peak-normalised when ``normalize``).  Files of different lengths are scored over the shortest,
     as the reference's ``si_sdr_torch`` does (``other.py:111-113``).  ``est`` (float32 ``[n]``): the enhanced file's samples where the
-    file itself is not at ``sampling_rate`` (``data.restore_rate``); ``enhanced_path`` then only names the row."""
-    from .wavio import load_utterance, read_wav
+    file itself is not at ``sampling_rate`` (``data.restore_rate``); ``enhanced_path`` then only names the row.  ``channel`` c
+    (``data.channels=all``): channel c of the enhanced file against channel c of the clean file, channel c of the noisy file as the
+    noise source, clean and noisy through ``wavio.load_file_channels`` (one gain per file)."""
+    from .wavio import load_file_channels, load_utterance, read_wav
     if est is None:
         est, _ = read_wav(enhanced_path)
-        est = (est if est.ndim == 1 else est[:, 0]).astype(np.float32)
-    clean, _ = load_utterance(clean_path, sampling_rate, normalize)
-    noisy, _ = load_utterance(noisy_path, sampling_rate, normalize)
+        est = (est if est.ndim == 1 else est[:, channel or 0]).astype(np.float32)
+    if channel is None:
+        clean, _ = load_utterance(clean_path, sampling_rate, normalize)
+        noisy, _ = load_utterance(noisy_path, sampling_rate, normalize)
+    else:
+        clean = load_file_channels(clean_path, sampling_rate, normalize)[0][channel]
+        noisy = load_file_channels(noisy_path, sampling_rate, normalize)[0][channel]
     n = min(len(est), len(clean), len(noisy))
     if n < MIN_LENGTH:
         raise ValueError(f"{enhanced_path}: {n} common samples, the metrics need at least {MIN_LENGTH}")
@@ -107,14 +113,16 @@ def score_files(enhanced_path: str, clean_path: str, noisy_path: str, sampling_r
     return {k: float(v[0]) for k, v in evaluate(*t).items()}
 
 
-def write_csv(path: str, rows: Sequence[Tuple[str, Dict[str, float]]]) -> None:
+def write_csv(path: str, rows: Sequence[Tuple], channel_column: bool = False) -> None:
     """``file, si_sdr, si_sir, si_sar, lsd``: one row per file and a last row ``mean``; values with 17 significant digits (they
-    read back as the same float64)."""
+    read back as the same float64).  ``channel_column`` (``data.channels=all``): rows are ``(file, channel, metrics)``, one per file and
+    channel, and a ``channel`` column follows ``file`` (empty in the ``mean`` row)."""
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    lead = ("file", "channel") if channel_column else ("file",)
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
-        w.writerow(("file",) + NAMES)
-        for name, r in rows:
-            w.writerow([name] + [repr(float(r[k])) for k in NAMES])
+        w.writerow(lead + NAMES)
+        for *name, r in rows:
+            w.writerow(list(name) + [repr(float(r[k])) for k in NAMES])
         if rows:
-            w.writerow(["mean"] + [repr(float(np.mean([r[k] for _, r in rows]))) for k in NAMES])
+            w.writerow(["mean"] + [""] * (len(lead) - 1) + [repr(float(np.mean([row[-1][k] for row in rows]))) for k in NAMES])

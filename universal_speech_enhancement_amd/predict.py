@@ -31,6 +31,13 @@
                                                   can take the place of its noisy one; off by default.  A source at 24 kHz gives the
                                                   same bytes either way; model.stage1_folder files, metrics.csv and losses.csv stay at
                                                   the model's rate; the loader's peak normalisation is not undone)
+        [data.channels=all]                      (every channel of a multi-channel file instead of the first alone: a file of C channels
+                                                  is C rows of the batch under ONE gain and comes back as a C-channel file, also with
+                                                  restore_rate and model=USE; a batch holds whole files, at most data.batch_size rows.
+                                                  Use it with model.sampler_kwargs.per_item=true: the channels of a file then share
+                                                  one noise seed and equal channels come out equal, while without it every row draws
+                                                  different noise from the shared stream.  metrics.csv / losses.csv get one row per
+                                                  file and channel and a channel column; first by default)
         [data.clean_folder=clean/]               (score every enhanced file whose clean counterpart exists under clean/ at the same
                                                   relative path: SI-SDR / SI-SIR / SI-SAR / LSD on the device -> enhanced/metrics.csv)
         [data.clean_folder=clean/ data.convergence_losses=true]
@@ -126,12 +133,35 @@ def _model_rate_samples(batch: dict, model):
     return [rows[i, : int(n)] for i, n in enumerate(batch["sample_length"])]
 
 
+def _scored_files(batch: dict, clean_folder: str):
+    """``data.channels=all``: (first row, C, relative path, clean path, enhanced path) of every file of the batch whose clean
+    counterpart exists and has the file's channel count; a clean file with another channel count is skipped and named on stderr."""
+    from .wavio import wav_info
+    for r, c in batch["file_rows"]:
+        noisy_path = batch["audio_path"][r]
+        rel = os.path.relpath(noisy_path, batch["data_folder"])
+        clean_path = os.path.join(clean_folder, rel)
+        if not os.path.isfile(clean_path):
+            continue
+        have = wav_info(clean_path)[1]
+        if have != c:
+            print(f"skipping {rel}: the clean file has {have} channel(s), the noisy file {c}", file=sys.stderr)
+            continue
+        yield r, c, rel, clean_path, noisy_path.replace(batch["data_folder"], batch["target_folder"])
+
+
 def _score_batch(batch: dict, clean_folder: str, data_cfg: dict, device, est=None):
     """``data.clean_folder``: (relative path, metrics) of every file of the batch whose clean counterpart exists - the enhanced file as
     ``predict_step`` wrote it (``est``: its samples at the model's rate, item by item, where the files are not at that rate) against
     the clean file, the noisy input as the noise source (``metrics.score_files``)."""
     from .metrics import score_files
     rows = []
+    if "file_rows" in batch:                                  # data.channels=all: one row per (file, channel)
+        for r, c, rel, clean_path, enhanced_path in _scored_files(batch, clean_folder):
+            for k in range(c):
+                rows.append((rel, k, score_files(enhanced_path, clean_path, batch["audio_path"][r], int(data_cfg.get("sampling_rate", 24000) or 0),
+                                                 bool(data_cfg.get("normalize", True)), device, None if est is None else est[r + k], channel=k)))
+        return rows
     for i, noisy_path in enumerate(batch["audio_path"]):
         rel = os.path.relpath(noisy_path, batch["data_folder"])
         clean_path = os.path.join(clean_folder, rel)
@@ -146,6 +176,12 @@ def _loss_batch(batch: dict, clean_folder: str, data_cfg: dict, device, est=None
     """``data.convergence_losses``: (relative path, convergence losses) of the files ``_score_batch`` scores (``losses.score_files``)."""
     from .losses import score_files
     rows = []
+    if "file_rows" in batch:
+        for r, c, rel, clean_path, enhanced_path in _scored_files(batch, clean_folder):
+            for k in range(c):
+                rows.append((rel, k, score_files(enhanced_path, clean_path, int(data_cfg.get("sampling_rate", 24000) or 0),
+                                                 bool(data_cfg.get("normalize", True)), device, None if est is None else est[r + k], channel=k)))
+        return rows
     for i, noisy_path in enumerate(batch["audio_path"]):
         rel = os.path.relpath(noisy_path, batch["data_folder"])
         clean_path = os.path.join(clean_folder, rel)
@@ -207,10 +243,11 @@ def predict(cfg: dict):
     n = 0
     clean_folder = cfg["data"].get("clean_folder")           # off by default: nothing below runs, no CSV is written
     rows, loss_rows = [], []
+    per_channel = cfg["data"].get("channels", "first") == "all"   # one CSV row per (file, channel), and a channel column
     with torch.no_grad():
         for i, batch in enumerate(data.predict_batches(device=device, frame_hop=owner.hop_length)):
             model.predict_step(batch, i)
-            n += len(batch["name"])
+            n += len(batch["file_rows"] if "file_rows" in batch else batch["name"])   # files, not rows
             est = _model_rate_samples(batch, model) if clean_folder and "source_rate" in batch else None
             if clean_folder:
                 rows += _score_batch(batch, clean_folder, cfg["data"], device, est)
@@ -218,10 +255,11 @@ def predict(cfg: dict):
                 loss_rows += _loss_batch(batch, clean_folder, cfg["data"], device, est)
     if clean_folder:
         from .metrics import write_csv
-        write_csv(os.path.join(cfg["data"]["target_folder"], "metrics.csv" if world == 1 else f"metrics_rank{rank}.csv"), rows)
+        write_csv(os.path.join(cfg["data"]["target_folder"], "metrics.csv" if world == 1 else f"metrics_rank{rank}.csv"), rows, per_channel)
     if with_losses:
         from .losses import write_csv as write_losses_csv
-        write_losses_csv(os.path.join(cfg["data"]["target_folder"], "losses.csv" if world == 1 else f"losses_rank{rank}.csv"), loss_rows)
+        write_losses_csv(os.path.join(cfg["data"]["target_folder"], "losses.csv" if world == 1 else f"losses_rank{rank}.csv"), loss_rows,
+                         per_channel)
     print(f"[rank {rank}] enhanced {n} file(s) -> {cfg['data']['target_folder']}")
     return n
 

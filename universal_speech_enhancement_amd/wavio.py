@@ -9,7 +9,11 @@ no CPU implementation of the two.
 
 ``store_batch_device`` (``use_store_items_dev``, csrc/use_resample.hip): the way out - a batch of model-rate float32 rows on the device,
 resampled back to each file's own frame count and quantised to the writer's 16-bit codes (or kept as float32), one call and one copy per
-batch; ``store_items_host`` is the same arithmetic on the host, ``write_wav_pcm16`` (``use_wav_write_pcm16``) writes ready-made codes."""
+batch; ``store_items_host`` is the same arithmetic on the host, ``write_wav_pcm16`` (``use_wav_write_pcm16``) writes ready-made codes.
+
+Files of several channels (``data.channels=all``): ``load_file_channels`` (host) and ``load_batch_device(channels="all")``
+(``use_load_files_dev``) make every channel of a file a row under one gain per file; ``store_batch_device(channels=...)``
+(``use_store_files_dev``) / ``store_files_host`` bring the rows of a file back as one interleaved ``[frames, channels]`` array."""
 from __future__ import annotations
 
 import ctypes as C
@@ -76,6 +80,43 @@ def load_utterance(path: str, sampling_rate: int = 24000, normalize: bool = True
     return a, sr.value
 
 
+CHANNEL_MODES = ("first", "all")                            # data.channels
+
+
+def check_channels(channels: str) -> str:
+    if channels not in CHANNEL_MODES:
+        raise ValueError(f"channels={channels!r}: 'first' (the first channel of every file, the reference's loader) or 'all'")
+    return channels
+
+
+def load_file_channels(path: str, sampling_rate: int = 24000, normalize: bool = True):
+    """Every channel of a file as an item of its own (``data.channels=all``): -> (float32 ``[C, L]``, sample rate).  Each channel is
+    resampled like ``load_utterance``'s; the gain is ONE per file, so that the channels keep their level relation: ``mx = max |v|`` over
+    all channels after resampling, in float64, by ``fabs(v) > mx`` (a NaN is never the peak), every channel ``v / mx * 0.8`` with two
+    roundings.  A silent channel of a file that is not silent stays exact zeros, a silent file gives NaN, a mono file is
+    ``load_utterance``'s row."""
+    frames, ch, _ = wav_info(path)
+    if ch == 1:
+        a, sr = load_utterance(path, sampling_rate, normalize)
+        return a[None], sr
+    a, sr = read_wav(path)
+    if frames < 1:
+        raise UseHipError(f"load_file_channels: '{path}' holds no samples")
+    target = int(sampling_rate or 0)
+    x = np.ascontiguousarray(a.T)                           # [C, frames], float64
+    if target > 0 and target != sr:
+        num = resampled_length(frames, sr, target)
+        x = np.stack([resample_fft(c, num) for c in x])
+        sr = target
+    if normalize:
+        mag = np.abs(x)
+        mag = mag[~np.isnan(mag)]
+        mx = np.float64(mag.max()) if mag.size else np.float64(0.0)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            x = x / mx * 0.8
+    return x.astype(np.float32), sr
+
+
 _WORK = {}                                                  # device -> the cached workspace of the device loader (uint8, grown on demand)
 
 
@@ -115,18 +156,76 @@ def resample_fft_device(x, num: int):
     return y
 
 
-def load_batch_device(paths, sampling_rate: int = 24000, normalize: bool = True, device="cuda", max_samples: int = 2 ** 24):
+def _load_files_device(paths, sampling_rate, normalize, dev, max_samples):
+    """``load_batch_device(channels="all")``: every file uploaded once, interleaved as ``read_wav`` returns it; the rows of the device
+    files are formed by one ``use_load_files_dev`` call per run of them."""
+    import torch
+    target = int(sampling_rate or 0)
+    limit = min(int(max_samples), 2 ** 24)
+    sigs, ns, nums, chans, rates, host_files = [], [], [], [], [], {}
+    for f, path in enumerate(paths):
+        a, sr = read_wav(path)
+        n, ch = a.shape[0], (1 if a.ndim == 1 else a.shape[1])
+        if n < 1:
+            raise UseHipError(f"load_batch_device: '{path}' holds no samples")
+        num = resampled_length(n, sr, target)
+        if max(n, num) * ch > limit or ch > 64:             # counted as frames x channels
+            host_files[f] = load_file_channels(path, target, normalize)[0]
+            sigs.append(None)
+        else:
+            sigs.append(np.ascontiguousarray(a).reshape(-1))
+        ns.append(n)
+        nums.append(num)
+        chans.append(ch)
+        rates += [target if target > 0 else sr] * ch
+    F, stride = len(ns), max(nums)
+    row0 = np.concatenate([[0], np.cumsum(chans)]).astype(np.int64)
+    lens = np.repeat(np.asarray(nums, dtype=np.int32), chans)
+    with torch.cuda.device(dev):
+        wav = torch.empty(int(row0[-1]), stride, dtype=torch.float32, device=dev)
+        xs = [None if s is None else torch.from_numpy(s).to(dev) for s in sigs]
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        f = 0
+        while f < F:
+            if f in host_files:
+                rows = torch.from_numpy(host_files[f])
+                wav[row0[f]: row0[f + 1], : rows.shape[1]] = rows.to(dev)
+                wav[row0[f]: row0[f + 1], rows.shape[1]:] = 0
+                f += 1
+                continue
+            e = f
+            while e < F and e not in host_files:
+                e += 1
+            k = e - f
+            work = _workspace(dev, max(lib().use_load_files_workspace(ns[i], nums[i], chans[i]) for i in range(f, e)))
+            ptrs = (C.c_void_p * k)(*[xs[i].data_ptr() for i in range(f, e)])
+            check(lib().use_load_files_dev(ptrs, (C.c_int64 * k)(*ns[f:e]), (C.c_int64 * k)(*nums[f:e]), (C.c_int * k)(*chans[f:e]), k,
+                                           int(bool(normalize)), wav[int(row0[f])].data_ptr(), stride, work.data_ptr(), work.numel(), stream),
+                  "use_load_files_dev")
+            f = e
+    return wav, lens, rates, chans
+
+
+def load_batch_device(paths, sampling_rate: int = 24000, normalize: bool = True, device="cuda", max_samples: int = 2 ** 24,
+                      channels: str = "first"):
     """The batch ``LoadWavData`` builds from ``paths``, formed on the device: -> (float32 ``[B, Lmax]`` on ``device``, int32 lengths
     ``[B]`` (host), sample rates).  The host decodes every file (``read_wav``) and uploads the first channel as float64; resampling to
     ``sampling_rate`` (0 / None: keep) at the length ``resampled_length`` gives, peak normalisation, the cast and the zero padding run
     in one ``use_load_items_dev`` call.  A file with more than ``max_samples`` samples before or after resampling goes through
-    ``load_utterance`` on the host instead: its row has the host loader's bits."""
+    ``load_utterance`` on the host instead: its row has the host loader's bits.
+
+    ``channels="all"``: a file of C channels gives C consecutive rows, in channel order, under ONE gain (``load_file_channels``); the
+    whole interleaved file is uploaded and ``use_load_files_dev`` forms its rows.  -> (wav ``[rows, Lmax]``, lengths and rates per ROW,
+    channel counts per FILE).  ``max_samples`` then counts frames x channels; a longer file takes ``load_file_channels`` on the host."""
     import torch
+    check_channels(channels)
     dev = torch.device(device)
     if dev.type != "cuda":
         raise ValueError(f"load_batch_device needs a CUDA (ROCm) device, got {dev}: the device loader has no CPU implementation")
     if dev.index is None:
         dev = torch.device("cuda", torch.cuda.current_device())
+    if channels == "all":
+        return _load_files_device(paths, sampling_rate, normalize, dev, max_samples)
     target = int(sampling_rate or 0)
     limit = min(int(max_samples), 2 ** 24)
     sigs, ns, nums, rates, host_rows = [], [], [], [], {}
@@ -217,17 +316,82 @@ def store_items_host(wav, lens, nums, subtype: int = PCM16) -> np.ndarray:
     return out
 
 
-def store_batch_device(wav, lens, nums, subtype: int = PCM16, max_samples: int = 2 ** 24) -> np.ndarray:
+def _file_args(wav, lens, nums, channels, subtype):
+    """Per-FILE ``lens`` / ``nums`` / ``channels`` of a batch whose rows are the channels of its files -> (lens, nums, channels, first
+    rows) as int64 arrays."""
+    chans = np.asarray(channels, dtype=np.int64).reshape(-1)
+    if chans.shape[0] < 1 or (chans < 1).any() or int(chans.sum()) != wav.shape[0]:
+        raise ValueError(f"channels={chans.tolist()} must be positive and add up to the {wav.shape[0]} rows of the batch")
+    row0 = np.concatenate([[0], np.cumsum(chans)]).astype(np.int64)
+    lens, nums = _store_args(wav[: chans.shape[0]], lens, nums, subtype)   # one entry per file; a view of F rows carries the width
+    return lens, nums, chans, row0
+
+
+def store_files_host(wav, lens, nums, channels, subtype: int = PCM16):
+    """``store_batch_device(channels=...)`` on the host: file f's rows through ``store_items_host``, interleaved.  -> a list of host
+    arrays ``[nums[f], channels[f]]``."""
+    import torch
+    wav = torch.as_tensor(wav)
+    lens, nums, chans, row0 = _file_args(wav, lens, nums, channels, subtype)
+    out = []
+    for f, c in enumerate(chans.tolist()):
+        rows = store_items_host(wav[row0[f]: row0[f] + c], [lens[f]] * c, [nums[f]] * c, subtype)
+        out.append(np.ascontiguousarray(rows[:, : nums[f]].T))
+    return out
+
+
+def _store_files_device(wav, lens, nums, channels, subtype, max_samples):
+    import torch
+    lens, nums, chans, row0 = _file_args(wav, lens, nums, channels, subtype)
+    if wav.stride(1) != 1 or wav.stride(0) < wav.shape[1]:
+        wav = wav.contiguous()
+    F, stride = len(chans), wav.stride(0)
+    limit = min(int(max_samples), 2 ** 24)
+    host = [f for f in range(F) if max(lens[f], nums[f]) > limit or chans[f] > 64]
+    offs = np.concatenate([[0], np.cumsum(nums * chans)]).astype(np.int64)     # the files lie one after another, no gap
+    dev = wav.device
+    with torch.cuda.device(dev):
+        out = torch.empty(max(int(offs[-1]), 1), dtype=torch.int16 if subtype == PCM16 else torch.float32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        f = 0
+        while f < F:                                        # one call per run of files that the device forms: one call without host files
+            if f in host:
+                f += 1
+                continue
+            e = f
+            while e < F and e not in host:
+                e += 1
+            k = e - f
+            work = _workspace(dev, max(lib().use_store_workspace(int(lens[i]), int(nums[i])) for i in range(f, e)))
+            check(lib().use_store_files_dev(wav[int(row0[f])].data_ptr(), stride, (C.c_int * k)(*lens[f:e].tolist()),
+                                            (C.c_int64 * k)(*nums[f:e].tolist()), (C.c_int * k)(*chans[f:e].tolist()),
+                                            (C.c_int64 * k)(*offs[f:e].tolist()), k, subtype, out.data_ptr(), work.data_ptr(), work.numel(),
+                                            stream), "use_store_files_dev")
+            f = e
+        flat = out.cpu().numpy()
+    res = [flat[offs[f]: offs[f + 1]].reshape(int(nums[f]), int(chans[f])) for f in range(F)]
+    for f in host:
+        res[f] = store_files_host(wav[row0[f]: row0[f + 1]], lens[f: f + 1], nums[f: f + 1], chans[f: f + 1], subtype)[0]
+    return res
+
+
+def store_batch_device(wav, lens, nums, subtype: int = PCM16, max_samples: int = 2 ** 24, channels=None):
     """The way out of a batch on the device (``use_store_items_dev``): ``wav`` float32 CUDA ``[B, L]``, item b valid for ``lens[b]``
     samples (the rest of a row is never read) and resampled to ``nums[b]`` samples in fp64, then rounded to float32 and stored as it is
     (``FLOAT32``) or as the 16-bit code ``write_wav`` stores (``PCM16``).  -> host array ``[B, max(nums)]`` (float32 / int16), zero past
     ``nums[b]``: one call, one device-to-host copy, one synchronisation.  An item with more than ``max_samples`` samples before or after
-    resampling goes through ``store_items_host`` instead."""
+    resampling goes through ``store_items_host`` instead.
+
+    ``channels`` (one count per FILE; ``lens`` and ``nums`` then per file too): the rows are the channels of files, file after file
+    (``data.channels=all``); every row goes the same way and the files come back interleaved (``use_store_files_dev``), as
+    ``write_wav`` / ``write_wav_pcm16`` store them.  -> a list of host arrays ``[nums[f], channels[f]]``, views of the one copy."""
     import torch
     if not isinstance(wav, torch.Tensor) or not wav.is_cuda:
         raise UseHipError("wav must be a CUDA (ROCm) tensor: use store_items_host for a CPU tensor")
     if wav.dtype != torch.float32:
         raise TypeError(f"wav must be float32, got {wav.dtype}")
+    if channels is not None:
+        return _store_files_device(wav, lens, nums, channels, subtype, max_samples)
     lens, nums = _store_args(wav, lens, nums, subtype)
     if wav.stride(1) != 1 or wav.stride(0) < wav.shape[1]:
         wav = wav.contiguous()
