@@ -554,6 +554,9 @@ int use_wav_read(const char* path, double** samples, int64_t* frames, int* chann
 int use_wav_write(const char* path, const float* samples, int64_t frames, int channels, int sample_rate, int subtype);
 int use_resample_fft(const double* x, int64_t n, int64_t num, double* y);
 int use_load_utterance(const char* path, int target_rate, int normalize, float** wav, int64_t* length, int* sample_rate);
+/* use_load_utterance with the peak it divided by: *peak = mx (fp64, by `fabs(v) > mx` over the resampled first channel; 0 for a silent
+ * file) when normalize != 0, otherwise *peak is not written.  peak may be null.  The row has use_load_utterance's bits. */
+int use_load_utterance_peak(const char* path, int target_rate, int normalize, float** wav, int64_t* length, int* sample_rate, double* peak);
 int use_wav_info(const char* path, int64_t* frames, int* channels, int* sample_rate);
 int64_t use_resampled_length(int64_t frames, int sample_rate, int target_rate);
 void use_free(void* p);
@@ -576,6 +579,11 @@ size_t use_resample_workspace(int64_t n, int64_t num);
 int use_resample_fft_dev(const double* x_dev, int64_t n, int64_t num, double* y_dev, void* work, size_t work_bytes, use_stream_t s);
 int use_load_items_dev(const double* const* x_dev /* [B] device pointers, held on the host */, const int64_t* n_host, const int64_t* num_host,
                        int B, int normalize, float* wav, int64_t stride, void* work, size_t work_bytes, use_stream_t s);
+/* use_load_items_dev that also hands out the peaks: peak_dev[b] = the very mx item b's scale kernel divides by, written by that kernel's first
+ * workgroup (no extra pass over the samples).  normalize == 0: nothing is written.  peak_dev null: use_load_items_dev.  The rows have the
+ * same bits either way.  USE_E_INVALID also for a peak_dev that is not 8-byte aligned. */
+int use_load_items_dev_peak(const double* const* x_dev, const int64_t* n_host, const int64_t* num_host, int B, int normalize, float* wav,
+                            int64_t stride, void* work, size_t work_bytes, double* peak_dev /* fp64 DEVICE [B] or null */, use_stream_t s);
 
 /* The way out on the device (csrc/use_resample.hip), handle-free: from the sampler's float32 rows to the samples of files at their own rate.
  * use_store_items_dev: wav float32 DEVICE [B][stride], item b valid for len_host[b] samples (HOST ints; a row is never read past them: after
@@ -594,6 +602,14 @@ size_t use_store_workspace(int64_t len, int64_t num);
 int use_store_items_dev(const float* wav, int64_t stride, const int* len_host, const int64_t* num_host, int B,
                         int subtype /* USE_WAV_PCM16 | USE_WAV_FLOAT32 */, void* out, int64_t out_stride, void* work, size_t work_bytes,
                         use_stream_t s);
+/* use_store_items_dev at the source's level (data.restore_level): gain_host[b] (HOST doubles, passed on as kernel arguments) multiplies every
+ * output sample of item b after the resampling and before the rounding to float32: x32 = (float)(v * g), v the fp64 value the store path
+ * holds (the resampled value, or the widened row sample at num == len), the product rounded once in fp64 and never contracted; then as above.
+ * gain_host null: use_store_items_dev itself, bit for bit (no multiplication by 1 takes place).  USE_E_INVALID (entry named, nothing
+ * launched) also for a gain that is NaN, infinite or negative. */
+int use_store_items_dev_gain(const float* wav, int64_t stride, const int* len_host, const int64_t* num_host,
+                             const double* gain_host /* HOST [B] or null */, int B, int subtype, void* out, int64_t out_stride, void* work,
+                             size_t work_bytes, use_stream_t s);
 int use_wav_write_pcm16(const char* path, const int16_t* codes, int64_t frames, int channels, int sample_rate);
 
 /* Files of several channels on the device (data.channels=all; csrc/use_resample.hip), handle-free.
@@ -619,6 +635,16 @@ int use_load_files_dev(const double* const* x_dev /* [F] device pointers, held o
 int use_store_files_dev(const float* wav, int64_t stride, const int* len_host /* [F] */, const int64_t* num_host /* [F] */, const int* ch_host,
                         const int64_t* out_off_host /* [F] element offset of file f in out */, int F,
                         int subtype /* USE_WAV_PCM16 | USE_WAV_FLOAT32 */, void* out, void* work, size_t work_bytes, use_stream_t s);
+/* The two with the file's peak and gain (data.restore_level), ONE per file as the normalisation is: peak_dev[f] = the mx file f's rows were
+ * divided by (written by the workgroup that reduces the file's partial maxima; normalize == 0: nothing is written), and gain_host[f] applied
+ * to every channel of file f as use_store_items_dev_gain applies it.  A null pointer: the call above, bit for bit.  USE_E_INVALID also for
+ * a misaligned peak_dev and a gain that is NaN, infinite or negative. */
+int use_load_files_dev_peak(const double* const* x_dev, const int64_t* n_host, const int64_t* num_host, const int* ch_host, int F, int normalize,
+                            float* wav, int64_t stride, void* work, size_t work_bytes, double* peak_dev /* fp64 DEVICE [F] or null */,
+                            use_stream_t s);
+int use_store_files_dev_gain(const float* wav, int64_t stride, const int* len_host, const int64_t* num_host, const int* ch_host,
+                             const int64_t* out_off_host, const double* gain_host /* HOST [F], one per file, or null */, int F, int subtype,
+                             void* out, void* work, size_t work_bytes, use_stream_t s);
 
 /* timesteps of the sampler, torch.linspace(1, t_eps, N) float32 semantics (sampling/__init__.py:63); host only */
 int use_timesteps(int N, float t_eps, float* out);

@@ -36,20 +36,26 @@ def _with_path_seeds(sampler_kwargs: dict, batch: dict) -> dict:
     return kw
 
 
-def _write_items(batch: dict, wavs, folder, subtype: str, restore: bool = True):
+def _write_items(batch: dict, wavs, folder, subtype: str, restore: bool = True, gains=None):
     """Item i of ``wavs``, trimmed to ``sample_length[i]``, to ``audio_path[i].replace(data_folder, folder)`` (reference
     SGMSE_module.py:72-80); a batch without ``audio_path`` writes nothing.
 
     A batch that carries ``source_rate`` and ``source_length`` (``LoadWavData(restore_rate=True)``) is written at its sources' own
     rates instead, unless ``restore`` is off: item i, resampled from its ``sample_length[i]`` samples to exactly ``source_length[i]``
     frames, at ``source_rate[i]`` - the whole batch in one device call and one copy (``wavio.store_batch_device``; a CPU batch through
-    ``wavio.store_items_host``).  A file whose rate is the model's has the bytes it has without the keys."""
+    ``wavio.store_items_host``).  A file whose rate is the model's has the bytes it has without the keys.
+
+    A batch that carries ``source_gain`` (``LoadWavData(restore_level=True)``) is written at its sources' level, unless ``restore`` is
+    off: through the same store functions with ``gains`` = ``source_gain``, or the caller's ``gains`` (one per row) in its place - at
+    the source's rate and frame count where the batch has them, else at ``sampling_rate`` / ``sample_length``."""
     if "audio_path" not in batch:
         return
+    gains = (batch["source_gain"] if gains is None else gains) if restore and "source_gain" in batch else None
+    restored = bool(restore and "source_rate" in batch and "source_length" in batch)
     if "file_rows" in batch:
-        return _write_files(batch, wavs, folder, subtype, restore and "source_rate" in batch and "source_length" in batch)
-    if restore and "source_rate" in batch and "source_length" in batch:
-        return _write_items_restored(batch, wavs, folder, subtype)
+        return _write_files(batch, wavs, folder, subtype, restored, gains)
+    if restored or gains is not None:
+        return _write_items_restored(batch, wavs, folder, subtype, restored, gains)
     for i, wav in enumerate(wavs):
         noisy_path = batch["audio_path"][i]
         sample_length = int(batch["sample_length"][i])
@@ -59,30 +65,35 @@ def _write_items(batch: dict, wavs, folder, subtype: str, restore: bool = True):
         _write_wav(path, wav.detach().cpu().numpy().astype(np.float32)[:sample_length], sample_rate, subtype)
 
 
-def _write_items_restored(batch: dict, wavs, folder, subtype: str):
+def _write_items_restored(batch: dict, wavs, folder, subtype: str, restored: bool = True, gains=None):
+    """The batch through the store functions: at ``source_rate`` / ``source_length`` (``restored``) or at the model's rate and
+    ``sample_length`` (only ``gains`` to apply), with ``gains`` (float64, one per row) or without."""
     from . import wavio
     if subtype not in ("PCM_16", "FLOAT"):
         raise ValueError(f"unsupported WAV subtype {subtype!r} (PCM_16 or FLOAT)")
     code = wavio.PCM16 if subtype == "PCM_16" else wavio.FLOAT32
     wavs = torch.as_tensor(wavs).detach().float()
     lens = [int(n) for n in batch["sample_length"]]
-    nums = [int(n) for n in batch["source_length"]]
-    rows = (wavio.store_batch_device if wavs.is_cuda else wavio.store_items_host)(wavs, lens, nums, code)
+    nums = [int(n) for n in batch["source_length"]] if restored else lens
+    rates = batch["source_rate"] if restored else batch["sampling_rate"]
+    kw = {} if gains is None else {"gains": gains}
+    rows = (wavio.store_batch_device if wavs.is_cuda else wavio.store_items_host)(wavs, lens, nums, code, **kw)
     for i, num in enumerate(nums):
         path = batch["audio_path"][i].replace(batch["data_folder"], folder)
         os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
         if code == wavio.PCM16:
-            wavio.write_wav_pcm16(path, rows[i, :num], int(batch["source_rate"][i]))
+            wavio.write_wav_pcm16(path, rows[i, :num], int(rates[i]))
         else:
-            wavio.write_wav(path, rows[i, :num], int(batch["source_rate"][i]), wavio.FLOAT32)
+            wavio.write_wav(path, rows[i, :num], int(rates[i]), wavio.FLOAT32)
 
 
-def _write_files(batch: dict, wavs, folder, subtype: str, restored: bool):
+def _write_files(batch: dict, wavs, folder, subtype: str, restored: bool, gains=None):
     """A batch of ``LoadWavData(channels="all")``: the rows ``file_rows[f] = (first row, C)`` are the channels of one file and go back
     into one C-channel file, ``[frames, C]`` interleaved.  ``restored``: at the source's rate and frame count, the whole batch in one
     device call and one copy (``wavio.store_batch_device(channels=...)``; a CPU batch through ``wavio.store_files_host``); otherwise the
     rows trimmed to ``sample_length`` and stacked, through the writer ``_write_items`` uses.  A mono file has the bytes it has without
-    the key."""
+    the key.  ``gains`` (one per ROW, equal over the rows of a file): the store functions' way too, with the file's gain, at the
+    source's rate (``restored``) or at ``sampling_rate`` / ``sample_length``."""
     from . import wavio
     if subtype not in ("PCM_16", "FLOAT"):
         raise ValueError(f"unsupported WAV subtype {subtype!r} (PCM_16 or FLOAT)")
@@ -91,22 +102,25 @@ def _write_files(batch: dict, wavs, folder, subtype: str, restored: bool):
     first = [r for r, _ in batch["file_rows"]]
     chans = [c for _, c in batch["file_rows"]]
     lens = [int(batch["sample_length"][r]) for r in first]
-    if restored:
-        nums = [int(batch["source_length"][r]) for r in first]
+    stored = restored or gains is not None
+    if stored:
+        nums = [int(batch["source_length"][r]) for r in first] if restored else lens
+        rates = batch["source_rate"] if restored else batch["sampling_rate"]
+        kw = {} if gains is None else {"gains": [float(gains[r]) for r in first]}
         wavs = wavs.float()
-        files = (wavio.store_batch_device(wavs, lens, nums, code, channels=chans) if wavs.is_cuda
-                 else wavio.store_files_host(wavs, lens, nums, chans, code))
+        files = (wavio.store_batch_device(wavs, lens, nums, code, channels=chans, **kw) if wavs.is_cuda
+                 else wavio.store_files_host(wavs, lens, nums, chans, code, **kw))
     else:
         host = wavs.cpu().numpy().astype(np.float32)
     for f, (r, c) in enumerate(batch["file_rows"]):
         path = batch["audio_path"][r].replace(batch["data_folder"], folder)
         os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
-        if restored:
+        if stored:
             a = files[f] if c > 1 else files[f][:, 0]
             if code == wavio.PCM16:
-                wavio.write_wav_pcm16(path, a, int(batch["source_rate"][r]))
+                wavio.write_wav_pcm16(path, a, int(rates[r]))
             else:
-                wavio.write_wav(path, a, int(batch["source_rate"][r]), wavio.FLOAT32)
+                wavio.write_wav(path, a, int(rates[r]), wavio.FLOAT32)
         else:
             a = host[r, : lens[f]] if c == 1 else np.ascontiguousarray(host[r: r + c, : lens[f]].T)
             _write_wav(path, a, batch["sampling_rate"][r], subtype)

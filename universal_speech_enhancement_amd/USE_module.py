@@ -64,7 +64,9 @@ class USEModule(_Base):
     def predict_step(self, batch: dict, batch_idx: int = 0) -> dict:
         """Adds ``enhanced`` (the sampler's output, untouched), ``fake`` (the refined batch) and ``handoff_peak`` (float64 [B]: every
         item's peak as the second run's loader would find it) and writes item i of ``fake`` to
-        ``audio_path[i].replace(data_folder, target_folder)``."""
+        ``audio_path[i].replace(data_folder, target_folder)``.  A batch with ``source_gain`` (``data.restore_level``): the refined files
+        get ``source_gain * (handoff_peak / 0.8)`` - both normalisations undone, in float64 on the host - or ``source_gain`` alone when
+        the hand-off does not normalise; the stage-1 files stay at the model's level."""
         from .handoff import wav_handoff, wav_handoff_files
         batch = self.Score.sample(batch, **_with_path_seeds(self.sampler_kwargs, batch))
         enhanced = batch["enhanced"]
@@ -84,7 +86,14 @@ class USEModule(_Base):
             stage2["sample_length"] = lengths
         batch["fake"] = self.G(stage2, **self.refine_kwargs)["fake"]
         batch["handoff_peak"] = peaks
-        _write_items(batch, batch["fake"], batch.get("target_folder"), self.wav_subtype)
+        gains = None
+        if "source_gain" in batch and self.normalize:
+            import numpy as np
+            g2 = peaks.detach().cpu().numpy().astype(np.float64) / np.float64(0.8)
+            if "file_rows" in batch:
+                g2 = np.repeat(g2, [c for _, c in batch["file_rows"]])
+            gains = np.asarray(batch["source_gain"], dtype=np.float64) * g2
+        _write_items(batch, batch["fake"], batch.get("target_folder"), self.wav_subtype, gains=gains)
         return batch
 
     def training_step(self, *a, **k):

@@ -188,18 +188,24 @@ SYMBOLS = {
     "use_wav_write": (_i, [C.c_char_p, _vp, _i64, _i, _i, _i]),
     "use_resample_fft": (_i, [_vp, _i64, _i64, _vp]),
     "use_load_utterance": (_i, [C.c_char_p, _i, _i, C.POINTER(C.POINTER(C.c_float)), C.POINTER(_i64), C.POINTER(_i)]),
+    "use_load_utterance_peak": (_i, [C.c_char_p, _i, _i, C.POINTER(C.POINTER(C.c_float)), C.POINTER(_i64), C.POINTER(_i), C.POINTER(C.c_double)]),
     "use_wav_info": (_i, [C.c_char_p, C.POINTER(_i64), C.POINTER(_i), C.POINTER(_i)]),
     "use_resampled_length": (_i64, [_i64, _i, _i]),
     "use_free": (None, [_vp]),
     "use_resample_workspace": (C.c_size_t, [_i64, _i64]),
     "use_resample_fft_dev": (_i, [_vp, _i64, _i64, _vp, _vp, C.c_size_t, _vp]),
     "use_load_items_dev": (_i, [C.POINTER(_vp), C.POINTER(_i64), C.POINTER(_i64), _i, _i, _vp, _i64, _vp, C.c_size_t, _vp]),
+    "use_load_items_dev_peak": (_i, [C.POINTER(_vp), C.POINTER(_i64), C.POINTER(_i64), _i, _i, _vp, _i64, _vp, C.c_size_t, _vp, _vp]),
     "use_store_workspace": (C.c_size_t, [_i64, _i64]),
     "use_store_items_dev": (_i, [_vp, _i64, C.POINTER(_i), C.POINTER(_i64), _i, _i, _vp, _i64, _vp, C.c_size_t, _vp]),
+    "use_store_items_dev_gain": (_i, [_vp, _i64, C.POINTER(_i), C.POINTER(_i64), C.POINTER(C.c_double), _i, _i, _vp, _i64, _vp, C.c_size_t, _vp]),
     "use_wav_write_pcm16": (_i, [C.c_char_p, _vp, _i64, _i, _i]),
     "use_load_files_workspace": (C.c_size_t, [_i64, _i64, _i]),
     "use_load_files_dev": (_i, [C.POINTER(_vp), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i), _i, _i, _vp, _i64, _vp, C.c_size_t, _vp]),
     "use_store_files_dev": (_i, [_vp, _i64, C.POINTER(_i), C.POINTER(_i64), C.POINTER(_i), C.POINTER(_i64), _i, _i, _vp, _vp, C.c_size_t, _vp]),
+    "use_load_files_dev_peak": (_i, [C.POINTER(_vp), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i), _i, _i, _vp, _i64, _vp, C.c_size_t, _vp, _vp]),
+    "use_store_files_dev_gain": (_i, [_vp, _i64, C.POINTER(_i), C.POINTER(_i64), C.POINTER(_i), C.POINTER(_i64), C.POINTER(C.c_double), _i, _i, _vp, _vp,
+                                      C.c_size_t, _vp]),
     "use_wav_handoff_files_workspace": (C.c_size_t, [_i, _i64]),
     "use_wav_handoff_files": (_i, [_vp, _vp, _i64, C.POINTER(_i), C.POINTER(_i), _i, _i, _i, _vp, C.c_size_t, _vp, _vp]),
 }

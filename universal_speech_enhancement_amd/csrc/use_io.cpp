@@ -271,6 +271,10 @@ int use_wav_info(const char* path, int64_t* frames, int* channels, int* sample_r
 }
 
 int use_load_utterance(const char* path, int target_rate, int normalize, float** wav, int64_t* length, int* sample_rate) {
+    return use_load_utterance_peak(path, target_rate, normalize, wav, length, sample_rate, nullptr);
+}
+
+int use_load_utterance_peak(const char* path, int target_rate, int normalize, float** wav, int64_t* length, int* sample_rate, double* peak) {
     if (!wav || !length || !sample_rate) return use_set_error(USE_E_INVALID, "use_load_utterance: null argument");
     double* raw = nullptr; int64_t frames = 0; int ch = 0, sr = 0;
     const int rc = use_wav_read(path, &raw, &frames, &ch, &sr);
@@ -286,14 +290,15 @@ int use_load_utterance(const char* path, int target_rate, int normalize, float**
         x.swap(y);
         sr = target_rate;
     }
+    double mx = 0.0;
     if (normalize) {                                                                        // loadwav_dataset.py:99-100
-        double mx = 0.0;
         for (double v : x) mx = fabs(v) > mx ? fabs(v) : mx;
         for (double& v : x) v = v / mx * 0.8;                                                // (a silent file gives NaN, as in the reference)
     }
     float* out = (float*)malloc(sizeof(float) * x.size());
     if (!out) return use_set_error(USE_E_NOMEM, "use_load_utterance: out of memory");
     for (size_t i = 0; i < x.size(); ++i) out[i] = (float)x[i];
+    if (normalize && peak) *peak = mx;                                                      // the divisor itself (data.restore_level)
     *wav = out; *length = (int64_t)x.size(); *sample_rate = sr;
     return USE_OK;
 }

@@ -251,16 +251,18 @@ __global__ __launch_bounds__(256) void load_peak_kernel(const double* __restrict
     if (threadIdx.x == 0) part[blockIdx.x] = mx;
 }
 
-// grid ceil(stride / LOAD_SLICE): row[i] = (float)(v[i] / mx * 0.8) (NORM) or (float)v[i] for i < L, 0 for L <= i < stride
+// grid ceil(stride / LOAD_SLICE): row[i] = (float)(v[i] / mx * 0.8) (NORM) or (float)v[i] for i < L, 0 for L <= i < stride.
+// peak (NORM, or null): the first workgroup, which always holds mx (L >= 1), stores the divisor there
 template <int NORM>
 __global__ __launch_bounds__(256) void load_scale_kernel(const double* __restrict__ v, int64_t L, const double* __restrict__ part, int np,
-                                                         float* __restrict__ row, int64_t stride) {
+                                                         float* __restrict__ row, int64_t stride, double* __restrict__ peak) {
     __shared__ double sh[4];
     const int64_t lo = (int64_t)blockIdx.x * LOAD_SLICE, hi = min(stride, lo + LOAD_SLICE);
     double mx = 0.0;
     if (NORM && lo < L) {
         for (int j = threadIdx.x; j < np; j += 256) mx = part[j] > mx ? part[j] : mx;
         mx = block_max(mx, sh);
+        if (peak && blockIdx.x == 0 && threadIdx.x == 0) peak[0] = mx;
     }
     for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
         float o = 0.f;
@@ -288,15 +290,23 @@ __device__ __forceinline__ int16_t pcm16_code(float x32) {
     return (int16_t)(v > 32767.0 ? 32767.0 : v < -32768.0 ? -32768.0 : v);
 }
 
-// grid ceil(out_stride / LOAD_SLICE): row[i] = x32 = (float)v[i] (DST float) or its 16-bit code (DST int16_t) for i < num, 0 for
+// the float32 sample of the way out: (float)v, or with GAIN (float)(v * g), the product rounded once in fp64 and never contracted (the
+// source's level, data.restore_level); without GAIN g is not read and a float's bits pass
+template <typename SRC, int GAIN>
+__device__ __forceinline__ float store_sample(SRC v, double g) {
+    if constexpr (GAIN) return (float)__dmul_rn((double)v, g);
+    else return (float)v;
+}
+
+// grid ceil(out_stride / LOAD_SLICE): row[i] = x32 = store_sample(v[i]) (DST float) or its 16-bit code (DST int16_t) for i < num, 0 for
 // num <= i < out_stride.  SRC double: the resampled signal; SRC float: the item's own row (num == len), whose bits pass unchanged
-template <typename SRC, typename DST>
-__global__ __launch_bounds__(256) void store_kernel(const SRC* __restrict__ v, int64_t num, DST* __restrict__ row, int64_t out_stride) {
+template <typename SRC, typename DST, int GAIN>
+__global__ __launch_bounds__(256) void store_kernel(const SRC* __restrict__ v, int64_t num, DST* __restrict__ row, int64_t out_stride, double g) {
     const int64_t lo = (int64_t)blockIdx.x * LOAD_SLICE, hi = min(out_stride, lo + LOAD_SLICE);
     for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
         DST o = 0;
         if (i < num) {
-            const float x32 = (float)v[i];
+            const float x32 = store_sample<SRC, GAIN>(v[i], g);
             if constexpr (sizeof(DST) == 2) o = pcm16_code(x32);
             else o = x32;
         }
@@ -314,22 +324,26 @@ __global__ __launch_bounds__(256) void deinterleave_kernel(const double* __restr
     out[i] = x[t * ch + c];
 }
 
-// one workgroup: fin[0] = the maximum of the np partial maxima of load_peak_kernel
-__global__ __launch_bounds__(256) void load_peak_final_kernel(const double* __restrict__ part, int np, double* __restrict__ fin) {
+// one workgroup: fin[0] = the maximum of the np partial maxima of load_peak_kernel, and peak[0] too where the caller asks for it
+__global__ __launch_bounds__(256) void load_peak_final_kernel(const double* __restrict__ part, int np, double* __restrict__ fin,
+                                                              double* __restrict__ peak) {
     __shared__ double sh[4];
     double mx = 0.0;
     for (int j = threadIdx.x; j < np; j += 256) mx = part[j] > mx ? part[j] : mx;
     mx = block_max(mx, sh);
-    if (threadIdx.x == 0) fin[0] = mx;
+    if (threadIdx.x == 0) {
+        fin[0] = mx;
+        if (peak) peak[0] = mx;
+    }
 }
 
-// store_kernel's sample for one channel of an interleaved file: dst[i * ch] = x32 = (float)v[i] or its 16-bit code, i < num (dst points
-// at the channel's first sample)
-template <typename SRC, typename DST>
-__global__ __launch_bounds__(256) void store_interleave_kernel(const SRC* __restrict__ v, int64_t num, DST* __restrict__ dst, int ch) {
+// store_kernel's sample for one channel of an interleaved file: dst[i * ch] = x32 = store_sample(v[i]) or its 16-bit code, i < num (dst
+// points at the channel's first sample)
+template <typename SRC, typename DST, int GAIN>
+__global__ __launch_bounds__(256) void store_interleave_kernel(const SRC* __restrict__ v, int64_t num, DST* __restrict__ dst, int ch, double g) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= num) return;
-    const float x32 = (float)v[i];
+    const float x32 = store_sample<SRC, GAIN>(v[i], g);
     if constexpr (sizeof(DST) == 2) dst[i * ch] = pcm16_code(x32);
     else dst[i * ch] = x32;
 }
@@ -338,6 +352,14 @@ int failf(int code, const char* fmt, ...) {
     char buf[512];
     va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
     return use_set_error(code, buf);
+}
+
+// a gain of the way out: finite and not negative; -> USE_OK, or USE_E_INVALID with the entry named
+int gains_ok(const char* fn, const double* gain, int count) {
+    for (int i = 0; gain && i < count; ++i)
+        if (!(gain[i] >= 0.0) || gain[i] > 1.7976931348623157e308)
+            return failf(USE_E_INVALID, "%s: gain_host[%d]=%g must be finite and not negative", fn, i, gain[i]);
+    return USE_OK;
 }
 
 // ---- host: workspace layout and launches ----
@@ -408,12 +430,13 @@ void resample_launch(const double* x, int64_t n, int64_t num, double* y, char* w
 // an item's workspace on the way out: item_layout's, then the row widened to fp64
 size_t store_bytes(int64_t len, int64_t num) { return item_layout(len, num).bytes + align16((size_t)len * sizeof(double)); }
 
-// one item of use_store_items_dev: row[0 ... len) -> dst[0 ... out_stride)
+// one item of use_store_items_dev: row[0 ... len) -> dst[0 ... out_stride); gain null: the instantiations without a gain
 template <typename DST>
-void store_launch(const float* row, int64_t len, int64_t num, DST* dst, int64_t out_stride, char* work, hipStream_t st) {
+void store_launch(const float* row, int64_t len, int64_t num, DST* dst, int64_t out_stride, const double* gain, char* work, hipStream_t st) {
     const dim3 grid((unsigned)((out_stride + LOAD_SLICE - 1) / LOAD_SLICE)), block(256);
     if (len == num) {
-        hipLaunchKernelGGL((store_kernel<float, DST>), grid, block, 0, st, row, num, dst, out_stride);
+        if (gain) hipLaunchKernelGGL((store_kernel<float, DST, 1>), grid, block, 0, st, row, num, dst, out_stride, *gain);
+        else hipLaunchKernelGGL((store_kernel<float, DST, 0>), grid, block, 0, st, row, num, dst, out_stride, 1.0);
         return;
     }
     const ItemWork w = item_layout(len, num);
@@ -421,7 +444,8 @@ void store_launch(const float* row, int64_t len, int64_t num, DST* dst, int64_t 
     double* y = reinterpret_cast<double*>(work + w.y);
     hipLaunchKernelGGL(store_widen_kernel, dim3(blocks256(len)), block, 0, st, row, len, x);
     resample_launch(x, len, num, y, work, w, st);
-    hipLaunchKernelGGL((store_kernel<double, DST>), grid, block, 0, st, (const double*)y, num, dst, out_stride);
+    if (gain) hipLaunchKernelGGL((store_kernel<double, DST, 1>), grid, block, 0, st, (const double*)y, num, dst, out_stride, *gain);
+    else hipLaunchKernelGGL((store_kernel<double, DST, 0>), grid, block, 0, st, (const double*)y, num, dst, out_stride, 1.0);
 }
 
 // a file's workspace in use_load_files_dev: item_layout's (the transforms of one channel at a time), the partial maxima of all ch * num
@@ -442,7 +466,8 @@ FileWork file_layout(int64_t n, int64_t num, int ch) {
 }
 
 // one file of use_load_files_dev: x (interleaved [n][ch]) -> rows wav[0 ... ch) of width stride
-void load_file_launch(const double* x, int64_t n, int64_t num, int ch, int normalize, float* wav, int64_t stride, char* work, hipStream_t st) {
+void load_file_launch(const double* x, int64_t n, int64_t num, int ch, int normalize, float* wav, int64_t stride, double* peak, char* work,
+                      hipStream_t st) {
     const FileWork w = file_layout(n, num, ch);
     const dim3 block(256);
     const double* v = x;                                          // ch contiguous channels of num samples
@@ -461,19 +486,20 @@ void load_file_launch(const double* x, int64_t n, int64_t num, int ch, int norma
     double* fin = reinterpret_cast<double*>(work + w.fin);
     if (normalize) {                                              // one peak over the file: the channels keep their level relation
         hipLaunchKernelGGL(load_peak_kernel, dim3(w.np), block, 0, st, v, (int64_t)ch * num, part);
-        hipLaunchKernelGGL(load_peak_final_kernel, dim3(1), block, 0, st, (const double*)part, w.np, fin);
+        hipLaunchKernelGGL(load_peak_final_kernel, dim3(1), block, 0, st, (const double*)part, w.np, fin, peak);
     }
     const dim3 grid((unsigned)((stride + LOAD_SLICE - 1) / LOAD_SLICE));
     for (int c = 0; c < ch; ++c) {
         float* row = wav + (int64_t)c * stride;
-        if (normalize) hipLaunchKernelGGL(load_scale_kernel<1>, grid, block, 0, st, v + (int64_t)c * num, num, (const double*)fin, 1, row, stride);
-        else hipLaunchKernelGGL(load_scale_kernel<0>, grid, block, 0, st, v + (int64_t)c * num, num, (const double*)fin, 1, row, stride);
+        if (normalize) hipLaunchKernelGGL(load_scale_kernel<1>, grid, block, 0, st, v + (int64_t)c * num, num, (const double*)fin, 1, row, stride, (double*)nullptr);
+        else hipLaunchKernelGGL(load_scale_kernel<0>, grid, block, 0, st, v + (int64_t)c * num, num, (const double*)fin, 1, row, stride, (double*)nullptr);
     }
 }
 
 // one file of use_store_files_dev: rows wav[0 ... ch) of width stride, valid for len -> dst[num][ch]; a row goes the way of store_launch
 template <typename DST>
-void store_file_launch(const float* wav, int64_t stride, int64_t len, int64_t num, int ch, DST* dst, char* work, hipStream_t st) {
+void store_file_launch(const float* wav, int64_t stride, int64_t len, int64_t num, int ch, DST* dst, const double* gain, char* work,
+                       hipStream_t st) {
     const dim3 grid(blocks256(num)), block(256);
     const ItemWork w = item_layout(len, num);
     double* x = reinterpret_cast<double*>(work + w.bytes);
@@ -481,12 +507,14 @@ void store_file_launch(const float* wav, int64_t stride, int64_t len, int64_t nu
     for (int c = 0; c < ch; ++c) {
         const float* row = wav + (int64_t)c * stride;
         if (len == num) {
-            hipLaunchKernelGGL((store_interleave_kernel<float, DST>), grid, block, 0, st, row, num, dst + c, ch);
+            if (gain) hipLaunchKernelGGL((store_interleave_kernel<float, DST, 1>), grid, block, 0, st, row, num, dst + c, ch, *gain);
+            else hipLaunchKernelGGL((store_interleave_kernel<float, DST, 0>), grid, block, 0, st, row, num, dst + c, ch, 1.0);
             continue;
         }
         hipLaunchKernelGGL(store_widen_kernel, dim3(blocks256(len)), block, 0, st, row, len, x);
         resample_launch(x, len, num, y, work, w, st);
-        hipLaunchKernelGGL((store_interleave_kernel<double, DST>), grid, block, 0, st, (const double*)y, num, dst + c, ch);
+        if (gain) hipLaunchKernelGGL((store_interleave_kernel<double, DST, 1>), grid, block, 0, st, (const double*)y, num, dst + c, ch, *gain);
+        else hipLaunchKernelGGL((store_interleave_kernel<double, DST, 0>), grid, block, 0, st, (const double*)y, num, dst + c, ch, 1.0);
     }
 }
 
@@ -528,6 +556,12 @@ int use_resample_fft_dev(const double* x_dev, int64_t n, int64_t num, double* y_
 
 int use_load_items_dev(const double* const* x_dev, const int64_t* n_host, const int64_t* num_host, int B, int normalize, float* wav,
                        int64_t stride, void* work, size_t work_bytes, use_stream_t s) {
+    return use_load_items_dev_peak(x_dev, n_host, num_host, B, normalize, wav, stride, work, work_bytes, nullptr, s);
+}
+
+int use_load_items_dev_peak(const double* const* x_dev, const int64_t* n_host, const int64_t* num_host, int B, int normalize, float* wav,
+                            int64_t stride, void* work, size_t work_bytes, double* peak_dev, use_stream_t s) {
+    if ((uintptr_t)peak_dev & 7) return failf(USE_E_INVALID, "use_load_items_dev: peak_dev must be 8-byte aligned");
     if (B < 1) return failf(USE_E_INVALID, "use_load_items_dev: B=%d must be positive", B);
     if (!x_dev) return failf(USE_E_INVALID, "use_load_items_dev: x_dev is null");
     if (!n_host) return failf(USE_E_INVALID, "use_load_items_dev: n_host is null");
@@ -569,9 +603,9 @@ int use_load_items_dev(const double* const* x_dev, const int64_t* n_host, const 
         const dim3 grid((unsigned)((stride + LOAD_SLICE - 1) / LOAD_SLICE)), block(256);
         if (normalize) {
             hipLaunchKernelGGL(load_peak_kernel, dim3(np), block, 0, st, v, num, part);
-            hipLaunchKernelGGL(load_scale_kernel<1>, grid, block, 0, st, v, num, part, np, row, stride);
+            hipLaunchKernelGGL(load_scale_kernel<1>, grid, block, 0, st, v, num, part, np, row, stride, peak_dev ? peak_dev + b : (double*)nullptr);
         } else {
-            hipLaunchKernelGGL(load_scale_kernel<0>, grid, block, 0, st, v, num, part, np, row, stride);
+            hipLaunchKernelGGL(load_scale_kernel<0>, grid, block, 0, st, v, num, part, np, row, stride, (double*)nullptr);
         }
     }
     const hipError_t e = hipGetLastError();
@@ -586,6 +620,11 @@ size_t use_store_workspace(int64_t len, int64_t num) {
 
 int use_store_items_dev(const float* wav, int64_t stride, const int* len_host, const int64_t* num_host, int B, int subtype, void* out,
                         int64_t out_stride, void* work, size_t work_bytes, use_stream_t s) {
+    return use_store_items_dev_gain(wav, stride, len_host, num_host, nullptr, B, subtype, out, out_stride, work, work_bytes, s);
+}
+
+int use_store_items_dev_gain(const float* wav, int64_t stride, const int* len_host, const int64_t* num_host, const double* gain_host, int B,
+                             int subtype, void* out, int64_t out_stride, void* work, size_t work_bytes, use_stream_t s) {
     if (B < 1) return failf(USE_E_INVALID, "use_store_items_dev: B=%d must be positive", B);
     if (subtype != USE_WAV_PCM16 && subtype != USE_WAV_FLOAT32) return failf(USE_E_INVALID, "use_store_items_dev: unknown subtype %d", subtype);
     if (!wav) return failf(USE_E_INVALID, "use_store_items_dev: wav is null");
@@ -615,12 +654,15 @@ int use_store_items_dev(const float* wav, int64_t stride, const int* len_host, c
             return failf(USE_E_INVALID, "use_store_items_dev: work_bytes=%zu is smaller than use_store_workspace(%lld, %lld) = %zu (item %d)",
                          work_bytes, (long long)len, (long long)num, need, b);
     }
+    if (gains_ok("use_store_items_dev", gain_host, B)) return USE_E_INVALID;
     hipStream_t st = (hipStream_t)s;
     char* base = static_cast<char*>(work);
     for (int b = 0; b < B; ++b) {
         const float* row = wav + (int64_t)b * stride;
-        if (subtype == USE_WAV_PCM16) store_launch(row, len_host[b], num_host[b], static_cast<int16_t*>(out) + (int64_t)b * out_stride, out_stride, base, st);
-        else store_launch(row, len_host[b], num_host[b], static_cast<float*>(out) + (int64_t)b * out_stride, out_stride, base, st);
+        const double* g = gain_host ? gain_host + b : nullptr;
+        if (subtype == USE_WAV_PCM16)
+            store_launch(row, len_host[b], num_host[b], static_cast<int16_t*>(out) + (int64_t)b * out_stride, out_stride, g, base, st);
+        else store_launch(row, len_host[b], num_host[b], static_cast<float*>(out) + (int64_t)b * out_stride, out_stride, g, base, st);
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return failf(USE_E_HIP, "use_store_items_dev: launch failed: %s", hipGetErrorString(e));
@@ -634,6 +676,12 @@ size_t use_load_files_workspace(int64_t n, int64_t num, int channels) {
 
 int use_load_files_dev(const double* const* x_dev, const int64_t* n_host, const int64_t* num_host, const int* ch_host, int F, int normalize,
                        float* wav, int64_t stride, void* work, size_t work_bytes, use_stream_t s) {
+    return use_load_files_dev_peak(x_dev, n_host, num_host, ch_host, F, normalize, wav, stride, work, work_bytes, nullptr, s);
+}
+
+int use_load_files_dev_peak(const double* const* x_dev, const int64_t* n_host, const int64_t* num_host, const int* ch_host, int F, int normalize,
+                            float* wav, int64_t stride, void* work, size_t work_bytes, double* peak_dev, use_stream_t s) {
+    if ((uintptr_t)peak_dev & 7) return failf(USE_E_INVALID, "use_load_files_dev: peak_dev must be 8-byte aligned");
     if (F < 1) return failf(USE_E_INVALID, "use_load_files_dev: F=%d must be positive", F);
     if (!x_dev) return failf(USE_E_INVALID, "use_load_files_dev: x_dev is null");
     if (!n_host) return failf(USE_E_INVALID, "use_load_files_dev: n_host is null");
@@ -663,7 +711,8 @@ int use_load_files_dev(const double* const* x_dev, const int64_t* n_host, const 
     hipStream_t st = (hipStream_t)s;
     int64_t row0 = 0;                                              // file f's rows: row0 ... row0 + ch[f] - 1
     for (int f = 0; f < F; ++f) {
-        load_file_launch(x_dev[f], n_host[f], num_host[f], ch_host[f], normalize, wav + row0 * stride, stride, static_cast<char*>(work), st);
+        load_file_launch(x_dev[f], n_host[f], num_host[f], ch_host[f], normalize, wav + row0 * stride, stride,
+                         peak_dev ? peak_dev + f : (double*)nullptr, static_cast<char*>(work), st);
         row0 += ch_host[f];
     }
     const hipError_t e = hipGetLastError();
@@ -673,6 +722,12 @@ int use_load_files_dev(const double* const* x_dev, const int64_t* n_host, const 
 
 int use_store_files_dev(const float* wav, int64_t stride, const int* len_host, const int64_t* num_host, const int* ch_host,
                         const int64_t* out_off_host, int F, int subtype, void* out, void* work, size_t work_bytes, use_stream_t s) {
+    return use_store_files_dev_gain(wav, stride, len_host, num_host, ch_host, out_off_host, nullptr, F, subtype, out, work, work_bytes, s);
+}
+
+int use_store_files_dev_gain(const float* wav, int64_t stride, const int* len_host, const int64_t* num_host, const int* ch_host,
+                             const int64_t* out_off_host, const double* gain_host, int F, int subtype, void* out, void* work, size_t work_bytes,
+                             use_stream_t s) {
     if (F < 1) return failf(USE_E_INVALID, "use_store_files_dev: F=%d must be positive", F);
     if (subtype != USE_WAV_PCM16 && subtype != USE_WAV_FLOAT32) return failf(USE_E_INVALID, "use_store_files_dev: unknown subtype %d", subtype);
     if (!wav) return failf(USE_E_INVALID, "use_store_files_dev: wav is null");
@@ -702,14 +757,16 @@ int use_store_files_dev(const float* wav, int64_t stride, const int* len_host, c
             return failf(USE_E_INVALID, "use_store_files_dev: work_bytes=%zu is smaller than use_store_workspace(%lld, %lld) = %zu (file %d)",
                          work_bytes, (long long)len, (long long)num, need, f);
     }
+    if (gains_ok("use_store_files_dev", gain_host, F)) return USE_E_INVALID;
     hipStream_t st = (hipStream_t)s;
     char* base = static_cast<char*>(work);
     int64_t row0 = 0;
     for (int f = 0; f < F; ++f) {
         const float* rows = wav + row0 * stride;
+        const double* g = gain_host ? gain_host + f : nullptr;
         if (subtype == USE_WAV_PCM16)
-            store_file_launch(rows, stride, len_host[f], num_host[f], ch_host[f], static_cast<int16_t*>(out) + out_off_host[f], base, st);
-        else store_file_launch(rows, stride, len_host[f], num_host[f], ch_host[f], static_cast<float*>(out) + out_off_host[f], base, st);
+            store_file_launch(rows, stride, len_host[f], num_host[f], ch_host[f], static_cast<int16_t*>(out) + out_off_host[f], g, base, st);
+        else store_file_launch(rows, stride, len_host[f], num_host[f], ch_host[f], static_cast<float*>(out) + out_off_host[f], g, base, st);
         row0 += ch_host[f];
     }
     const hipError_t e = hipGetLastError();

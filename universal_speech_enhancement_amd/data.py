@@ -17,6 +17,12 @@ samples (before or after resampling) takes the host path.
 rate and frame count of each file as ``wav_info`` reports them, and the writers of the models (``SGMSE_module._write_items``) then
 write every output at its source's rate with exactly its frame count.  Off: the batch dict is what it always was.
 
+``restore_level`` (no reference counterpart, off by default): every batch also carries ``source_gain``, a float64 host tensor with one
+entry per row: ``mx / 0.8``, ``mx`` the peak the loader divided the file by (exactly 1 with ``normalize=false``, 0 for a silent file;
+the same for all channels of a file under ``channels=all``).  The writers multiply every output sample by it, in fp64 before their
+rounding to float32, so that a file comes out at its source's level; the tensors of the batch are not touched.  Off: the batch dict
+and the loader calls are what they always were.
+
 ``channels`` (no reference counterpart; ``first`` by default: the reference's loader, which keeps the first channel of a file and drops the
 rest).  ``all``: a file of C channels gives C consecutive rows of the batch, in channel order, and the writers put them back together as
 one C-channel file.  The rules:
@@ -38,19 +44,26 @@ import numpy as np
 import torch
 
 from .distributed import shard_list
-from .wavio import check_channels, load_batch_device, load_file_channels, load_utterance, resampled_length, wav_info
+from .wavio import check_channels, load_batch_device, load_file_channels, load_utterance, resampled_length, source_gain, wav_info
+
+
+def _gains(peaks, counts) -> torch.Tensor:
+    """``source_gain`` of a batch: from the peak of every file (``peaks`` ``None``: not normalised, gain 1), repeated over the
+    ``counts[f]`` rows of file f."""
+    g = np.array([source_gain(None if peaks is None else peaks[f]) for f in range(len(counts))], dtype=np.float64)
+    return torch.from_numpy(np.repeat(g, counts))
 
 
 class LoadWavData:
     def __init__(self, data_folder: str, target_folder: str, normalize: bool = True, sampling_rate: int = 24000,
                  batch_size: int = 1, num_workers: int = 0, rank: int = 0, world_size: int = 1, bucket_by_length: bool = False,
                  device_load: bool = False, device_load_max_samples: int = 2 ** 24, restore_rate: bool = False, channels: str = "first",
-                 **ignored):
+                 restore_level: bool = False, **ignored):
         self.data_folder, self.target_folder = data_folder, target_folder
         self.normalize, self.sampling_rate, self.batch_size = normalize, sampling_rate, batch_size
         self.bucket_by_length = bool(bucket_by_length)
         self.device_load, self.device_load_max_samples = bool(device_load), int(device_load_max_samples)
-        self.restore_rate = bool(restore_rate)
+        self.restore_rate, self.restore_level = bool(restore_rate), bool(restore_level)
         self.channels = check_channels(channels)
         files: List[str] = []
         for root, _, names in os.walk(data_folder):
@@ -61,6 +74,9 @@ class LoadWavData:
         return len(self.filepaths)
 
     def _item(self, path: str) -> Dict:
+        if self.restore_level:
+            x, sr, mx = load_utterance(path, self.sampling_rate, self.normalize, return_peak=True)
+            return {"perturbed": x, "name": os.path.basename(path).split(".wav")[0], "audio_path": path, "sampling_rate": sr, "peak": mx}
         x, sr = load_utterance(path, self.sampling_rate, self.normalize)       # native loader (csrc/use_io.cpp)
         return {"perturbed": x, "name": os.path.basename(path).split(".wav")[0], "audio_path": path, "sampling_rate": sr}
 
@@ -107,11 +123,20 @@ class LoadWavData:
     def _channel_batches(self, device, frame_hop) -> Iterator[Dict]:
         """``channels="all"``: the rows of a batch are the channels of its files, file after file."""
         for paths in self.batch_files(frame_hop):
-            if self.device_load:
+            peaks = None
+            if self.device_load and self.restore_level:
+                wav, lens, rates, chans, peaks = load_batch_device(paths, self.sampling_rate, self.normalize, device,
+                                                                   self.device_load_max_samples, channels="all", return_peaks=True)
+            elif self.device_load:
                 wav, lens, rates, chans = load_batch_device(paths, self.sampling_rate, self.normalize, device, self.device_load_max_samples,
                                                             channels="all")
             else:
-                files = [load_file_channels(p, self.sampling_rate, self.normalize) for p in paths]
+                if self.restore_level:
+                    files = [load_file_channels(p, self.sampling_rate, self.normalize, return_peak=True) for p in paths]
+                    peaks = [mx for _, _, mx in files] if self.normalize else None
+                    files = [(x, sr) for x, sr, _ in files]
+                else:
+                    files = [load_file_channels(p, self.sampling_rate, self.normalize) for p in paths]
                 chans = [x.shape[0] for x, _ in files]
                 lens = np.repeat(np.array([x.shape[1] for x, _ in files], dtype=np.int32), chans)
                 rates = [sr for (_, sr), c in zip(files, chans) for _ in range(c)]
@@ -123,11 +148,14 @@ class LoadWavData:
                 wav = wav.to(device)
             rows = [p for p, c in zip(paths, chans) for _ in range(c)]
             first = np.concatenate([[0], np.cumsum(chans)])[:-1]
-            yield {"perturbed": wav, "name": [os.path.basename(p).split(".wav")[0] for p in rows],
-                   "sample_length": torch.from_numpy(lens), "sampling_rate": rates, "audio_path": rows,
-                   "data_folder": self.data_folder, "target_folder": self.target_folder,
-                   "channel": [k for c in chans for k in range(c)], "n_channels": [c for c in chans for _ in range(c)],
-                   "file_rows": [(int(r), int(c)) for r, c in zip(first, chans)]}
+            batch = {"perturbed": wav, "name": [os.path.basename(p).split(".wav")[0] for p in rows],
+                     "sample_length": torch.from_numpy(lens), "sampling_rate": rates, "audio_path": rows,
+                     "data_folder": self.data_folder, "target_folder": self.target_folder,
+                     "channel": [k for c in chans for k in range(c)], "n_channels": [c for c in chans for _ in range(c)],
+                     "file_rows": [(int(r), int(c)) for r, c in zip(first, chans)]}
+            if self.restore_level:
+                batch["source_gain"] = _gains(peaks, list(chans))
+            yield batch
 
     @staticmethod
     def _with_source(batches) -> Iterator[Dict]:
@@ -140,10 +168,17 @@ class LoadWavData:
 
     def _device_batches(self, device, frame_hop) -> Iterator[Dict]:
         for paths in self.batch_files(frame_hop):
-            wav, lens, rates = load_batch_device(paths, self.sampling_rate, self.normalize, device, self.device_load_max_samples)
-            yield {"perturbed": wav, "name": [os.path.basename(p).split(".wav")[0] for p in paths],
-                   "sample_length": torch.from_numpy(lens), "sampling_rate": rates, "audio_path": list(paths),
-                   "data_folder": self.data_folder, "target_folder": self.target_folder}
+            if self.restore_level:
+                wav, lens, rates, peaks = load_batch_device(paths, self.sampling_rate, self.normalize, device, self.device_load_max_samples,
+                                                            return_peaks=True)
+            else:
+                wav, lens, rates = load_batch_device(paths, self.sampling_rate, self.normalize, device, self.device_load_max_samples)
+            batch = {"perturbed": wav, "name": [os.path.basename(p).split(".wav")[0] for p in paths],
+                     "sample_length": torch.from_numpy(lens), "sampling_rate": rates, "audio_path": list(paths),
+                     "data_folder": self.data_folder, "target_folder": self.target_folder}
+            if self.restore_level:
+                batch["source_gain"] = _gains(peaks, [1] * len(paths))
+            yield batch
 
     def _host_batches(self, device, frame_hop) -> Iterator[Dict]:
         for paths in self.batch_files(frame_hop):
@@ -152,7 +187,10 @@ class LoadWavData:
             wav = torch.zeros(len(items), int(lens.max()))
             for k, it in enumerate(items):
                 wav[k, : lens[k]] = torch.from_numpy(it["perturbed"])
-            yield {"perturbed": wav.to(device), "name": [it["name"] for it in items],
-                   "sample_length": torch.from_numpy(lens), "sampling_rate": [it["sampling_rate"] for it in items],
-                   "audio_path": [it["audio_path"] for it in items], "data_folder": self.data_folder,
-                   "target_folder": self.target_folder}
+            batch = {"perturbed": wav.to(device), "name": [it["name"] for it in items],
+                     "sample_length": torch.from_numpy(lens), "sampling_rate": [it["sampling_rate"] for it in items],
+                     "audio_path": [it["audio_path"] for it in items], "data_folder": self.data_folder,
+                     "target_folder": self.target_folder}
+            if self.restore_level:
+                batch["source_gain"] = _gains([it["peak"] for it in items] if self.normalize else None, [1] * len(items))
+            yield batch

@@ -30,7 +30,15 @@
                                                   model-rate output is resampled back on the device, a batch per call, so that a file
                                                   can take the place of its noisy one; off by default.  A source at 24 kHz gives the
                                                   same bytes either way; model.stage1_folder files, metrics.csv and losses.csv stay at
-                                                  the model's rate; the loader's peak normalisation is not undone)
+                                                  the model's rate; the loader's peak normalisation is not undone unless
+                                                  data.restore_level=true asks for it)
+        [data.restore_level=true]                (every output file at its source's level instead of peaking near 0.8: the peak the
+                                                  loader divided by is carried to the writer, which multiplies every sample by
+                                                  peak / 0.8 in fp64 before its rounding to float32 - with model=USE by the hand-off's
+                                                  peak / 0.8 as well - so that quiet and loud recordings keep their level relation; off
+                                                  by default, alone or with restore_rate, device_load and channels=all.  16-bit output
+                                                  clamps as always, wav_subtype=FLOAT keeps values above 1; model.stage1_folder files,
+                                                  metrics.csv and losses.csv stay at the model's level; data.normalize=false: gain 1)
         [data.channels=all]                      (every channel of a multi-channel file instead of the first alone: a file of C channels
                                                   is C rows of the batch under ONE gain and comes back as a C-channel file, also with
                                                   restore_rate and model=USE; a batch holds whole files, at most data.batch_size rows.
@@ -124,8 +132,8 @@ def instantiate(node, **extra):
 
 
 def _model_rate_samples(batch: dict, model):
-    """``data.restore_rate``: for every item the samples its file holds without the flag, read back (the 16-bit codes over 32768, or
-    the float32 samples) - what ``metrics.csv`` and ``losses.csv`` are computed from, so that the flag does not change them.  The
+    """``data.restore_rate`` / ``data.restore_level``: for every item the samples its file holds without the flags, read back (the 16-bit codes over 32768, or
+    the float32 samples) - what ``metrics.csv`` and ``losses.csv`` are computed from, so that the flags do not change them.  The
     quantisation is the hand-off's (``handoff.wav_handoff`` without normalisation: bit for bit the file round trip)."""
     from .handoff import wav_handoff
     wavs = batch["fake" if hasattr(model, "G") else "enhanced"]
@@ -248,7 +256,7 @@ def predict(cfg: dict):
         for i, batch in enumerate(data.predict_batches(device=device, frame_hop=owner.hop_length)):
             model.predict_step(batch, i)
             n += len(batch["file_rows"] if "file_rows" in batch else batch["name"])   # files, not rows
-            est = _model_rate_samples(batch, model) if clean_folder and "source_rate" in batch else None
+            est = _model_rate_samples(batch, model) if clean_folder and ("source_rate" in batch or "source_gain" in batch) else None
             if clean_folder:
                 rows += _score_batch(batch, clean_folder, cfg["data"], device, est)
             if with_losses:
