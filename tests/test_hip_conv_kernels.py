@@ -18,6 +18,12 @@ sqrt(K) u S (the probabilistic rounding-error bound), not u S.  Measured on fp32
 flat form (0.14 of this bound), while one dropped product of K is ~S / K, hundreds of times the bound.  Each case prints its worst
 |err| / bound; every ratio must stay below 1.
 
+conv_sk is not one kernel: launch_conv_sk picks the tile, 32 or 64 output channels per workgroup (NJ) and the channels per K pass (CP) from
+the operands.  tests/conv_sk_forms.py mirrors that choice on the host; every conv_sk case asserts from it the form it was written to
+reach before it launches (FORMS), so a case cannot drift onto another form unnoticed, and tests/test_conv_sk_forms_host.py checks on the
+CPU that the cases cover every form and that defects of the decomposition exceed this bound.  The bound does not depend on the form:
+eight-way split-K only shortens the chains (measured: at most 0.32 of it in 16 bits, 0.06 in fp32, at K up to 9216).
+
 `-m "not gpu"` checks the reference itself: against the oracle's res-block goldens (tests/golden/resblock_*.npz) composed from it
 as the engine composes the res-block, and against a direct loop implementation on a tiny shape."""
 import ctypes as C
@@ -499,6 +505,87 @@ for dt in (0, 1, 2):
 for dt in (1, 2):
     _add(1, dt, 1, 40, 16, 128, 4, odt=0, gn="coef", act=1, res=1)
 
+# ---- the forms launch_conv_sk picks (tests/conv_sk_forms.py mirrors the launcher; tests/test_conv_sk_forms_host.py holds the coverage) ----
+# The conv_sk cases above all run NJ = 1 with one K pass per source and cpu_ <= 4.  The cases below are appended (a case's seed depends on
+# its index) and each states the form it was written to reach, asserted from the mirror before anything is launched:
+#   FORMS[index] = (NJ, CP, workgroups the tile-width rule compares, cpu_ per pass per source, weight branches)
+N_CASES_ONE_FORM = len(CASES)
+FORMS = {}
+
+
+def _add_sk(form, dt, B, H, W, C0, Cout, **kw):
+    FORMS[len(CASES)] = form
+    _add(7, dt, B, H, W, C0, Cout, **kw)
+
+
+CONV0_ST2 = dict(gn="st", act=1, scale=RS, stats=1, temb="item")                     # Conv_1 with the shortcut, GroupNorm from totals
+NIN3 = dict(ntaps=1, gn="st", act=0, res=1, scale=RS, stats=1)
+for dt in (1, 2):
+    # NJ 1, CP 256: cpu_ 7, 5, 6, 8; a partial last pass with c_loc = 256; four passes on a 2-column map; a 1-column map
+    _add_sk((1, 256, 5 * 2 * 4, [[7], [5], [6]], ("slab", "slab")), dt, 2, 16, 20, 224, 128, C1=160, XC0=192, **CONV1_SC)
+    _add_sk((1, 256, 5 * 2 * 8, [[8], [8]], ("slab", None)), dt, 2, 16, 20, 256, 256, C1=256, **CONV0)
+    _add_sk((1, 256, 2 * 2 * 2, [[8, 4]], ("slab", None)), dt, 2, 8, 10, 384, 64, creal=40, **CONV1_RES)
+    _add_sk((1, 256, 1 * 2 * 8, [[8, 8, 8, 8]], ("slab", None)), dt, 2, 16, 2, 1024, 256, **CONV1_RES_PYR)
+    _add_sk((1, 256, 1 * 2 * 8, [[8], [8], [8]], ("slab", "slab")), dt, 2, 8, 1, 256, 256, XC0=256, XC1=256, **CONV1_SC)
+    # NJ 2, CP 128: two passes per source; a second source behind a partial pass, cpu_ 4, 1, 3, 2; the row-major weight branch (1x1);
+    # Cout % 64 != 0 above the threshold stays NJ 1
+    _add_sk((2, 128, 5 * 13 * 8, [[4, 4], [4, 4], [4, 4]], ("slab", "slab")), dt, 13, 16, 20, 256, 256, XC0=256, XC1=256, **CONV1_SC)
+    _add_sk((2, 128, 2 * 33 * 8, [[4, 1], [3], [2]], ("slab", "slab")), dt, 33, 8, 10, 160, 256, C1=96, XC0=64, creal=200, **CONV0_ST2)
+    _add_sk((2, 128, 2 * 33 * 8, [[4, 4]], ("row", None)), dt, 33, 8, 10, 256, 256, **NIN3)
+    _add_sk((1, 256, 2 * 33 * 11, [[2]], ("slab", None)), dt, 33, 8, 10, 64, 352, **CONV0_FIR)
+    # the fp32-out head with a partial second pass
+    _add_sk((1, 256, 5 * 2 * 0, [[8, 4]], ("row", None)), dt, 2, 16, 20, 384, 4, odt=0, gn="coef", act=1, res=1)
+# fp32 storage.  NJ 1, CP 128: two passes, a second source behind a partial pass
+_add_sk((1, 128, 5 * 2 * 4, [[4, 4]], ("slab", None)), 0, 2, 16, 20, 256, 128, creal=100, **CONV1_RES)
+_add_sk((1, 128, 1 * 2 * 2, [[4, 1], [3], [4, 1]], ("slab", "slab")), 0, 2, 7, 9, 160, 64, C1=96, XC0=160, **CONV1_SC)
+# NJ 2, CP 64 (what fp32 training runs below 4096 pixels); exactly 512 workgroups (narrow) and 768 (wide): the two sides of the seam
+_add_sk((2, 64, 64 * 3 * 4, [[2, 2]], ("slab", None)), 0, 3, 64, 64, 128, 128, **CONV1_RES_PYR)
+_add_sk((2, 64, 16 * 3 * 12, [[2, 1], [2], [2, 1]], ("slab", "slab")), 0, 3, 64, 16, 96, 384, C1=64, XC0=96, **CONV1_SC)
+_add_sk((1, 128, 64 * 2 * 4, [[2]], ("slab", None)), 0, 2, 64, 64, 64, 128, **CONV0)
+_add_sk((2, 64, 64 * 2 * 6, [[2]], ("slab", None)), 0, 2, 64, 64, 64, 192, creal=150, **CONV0)
+_add_sk((2, 64, 2 * 33 * 8, [[2, 2, 2, 2]], ("row", None)), 0, 33, 8, 10, 256, 256, **NIN3)
+# tall maps of one or two columns, where the tallest tile of every width exceeds the halo: sk_tile's second round (22 x 2 and 21 x 1 tiles;
+# before it these maps ran as 128 and 41 one-pixel tiles)
+for dt in (0, 1, 2):
+    _add_sk((1, 128 if dt == 0 else 256, 3 * 2 * 2, [[2], [1]], ("slab", None)), dt, 2, 64, 2, 64, 64, C1=32, **CONV0)
+_add_sk((1, 256, 2 * 2 * 3, [[4], [1]], ("slab", "slab")), 1, 2, 41, 1, 128, 96, XC0=32, **CONV1_SC)
+
+# conv_v4 / conv_v5 / conv_v2 re-order their workgroups per XCD only when gridDim.x % 8 == 0; no case above has such a grid.  2 x 4 = 8
+# tiles (ragged in H for conv_v2), and 16 tiles, where the re-ordering is no longer the identity.  XCD_TILES[index] = gridDim.x
+XCD_TILES = {}
+
+
+def _add_xcd(tiles, kern, dt, B, H, W, C0, Cout, **kw):
+    XCD_TILES[len(CASES)] = tiles
+    _add(kern, dt, B, H, W, C0, Cout, **kw)
+
+
+for kern, dts in ((4, (0, 1, 2)), (5, (1, 2))):
+    for dt in dts:
+        _add_xcd(8, kern, dt, 2, 32, 128, 64, 128, **CONV1_RES)
+for dt in (0, 1, 2):
+    _add_xcd(8, 2, dt, 2, 31, 64, 64, 128, **CONV0_CAT)
+_add_xcd(16, 5, 1, 1, 32, 256, 64, 128, **CONV0_FIR)
+_add_xcd(16, 2, 1, 1, 32, 128, 64, 128, **CONV0_FIR)
+
+
+def _assert_form(c):
+    """The case reaches the form it was written for (conv_sk: instantiation, workgroup count, passes, weight branches; XCD cases: the grid)."""
+    import conv_sk_forms as skf
+    i = CASES.index(c)
+    if c["kern"] == 7:
+        assert skf.sk_eligible(c), "conv_sk does not run this case"
+        NJ, CP, tiles, wgs, passes = skf.sk_form(c)
+        if i < N_CASES_ONE_FORM:
+            assert NJ == 1 and all(len(p) == 1 and p[0] <= 4 for p in passes), (NJ, CP, passes)
+        else:
+            eNJ, eCP, ewgs, epasses, ebranch = FORMS[i]
+            assert (NJ, CP, passes, skf.weight_branch(c)) == (eNJ, eCP, epasses, ebranch), (NJ, CP, wgs, passes, skf.weight_branch(c))
+            assert wgs == ewgs, (tiles, wgs, ewgs)
+    if i in XCD_TILES:
+        n = skf.v2_tiles(c["H"], c["W"]) if c["kern"] == 2 else skf.wide_tiles(c["H"], c["W"])
+        assert n == XCD_TILES[i] and n % 8 == 0, (n, XCD_TILES[i])
+
 
 # what use_conv_choice may name when the dispatcher runs a case on the kernel its forced variant runs (variant 1: the pyramid head is one of its kernels)
 CHOICE = {7: ("conv_sk",), 2: ("conv_v2",), 4: ("conv_v4",), 5: ("conv_v5",), 1: ("conv_generic", "pyr_conv", "pyr_conv_ws")}
@@ -522,6 +609,7 @@ def _dispatch_options(c):
 @pytest.mark.parametrize("c", CASES, ids=[_case_id(c) for c in CASES])
 def test_conv_kernel_matches_float64_reference(c):
     kern, dt = c["kern"], c["dt"]
+    _assert_form(c)
     f, ref, S, creal = _make_case(c, seed=len(_case_id(c)) * 7919 + CASES.index(c))
     rc, out, stats = _run_conv(f, kern)
     assert rc == 0, _lib().lib().use_last_error()

@@ -351,16 +351,20 @@ long g_sk_max_px = 16L * 20L;     // largest map (pixels) served by conv_sk (32x
 // tile shape: TH x TW <= 64 pixels, halo <= 128 pixels, fewest tiles, then the smallest halo; rows balanced over the tiles
 void sk_tile(int H, int W, int pad, int* th, int* tw) {
     long best = -1; int bh = 1, bw = 1;
-    for (int w = 1; w <= W && w <= SK_MT; ++w) {
-        int hmax = SK_MT / w; if (hmax > H) hmax = H;
-        const int ny = (H + hmax - 1) / hmax;
-        const int h = (H + ny - 1) / ny;
-        const int halo = (h + 2 * pad) * (w + 2 * pad);
-        if (halo > SK_HPMAX) continue;
-        const long tiles = (long)ny * ((W + w - 1) / w);
-        const long key = tiles * 1024 + halo;
-        if (best < 0 || key < best) { best = key; bh = h; bw = w; }
-    }
+    // second round, only when the first finds nothing: tall maps of one or two columns (64x2, 41x1, ...), where the tallest tile of
+    // every width exceeds the halo - the tile height capped by the halo instead of one-pixel tiles
+    for (int capped = 0; capped < 2 && best < 0; ++capped)
+        for (int w = 1; w <= W && w <= SK_MT; ++w) {
+            int hmax = SK_MT / w; if (hmax > H) hmax = H;
+            if (capped) { const int hcap = SK_HPMAX / (w + 2 * pad) - 2 * pad; if (hmax > hcap) hmax = hcap; if (hmax < 1) continue; }
+            const int ny = (H + hmax - 1) / hmax;
+            const int h = (H + ny - 1) / ny;
+            const int halo = (h + 2 * pad) * (w + 2 * pad);
+            if (halo > SK_HPMAX) continue;
+            const long tiles = (long)ny * ((W + w - 1) / w);
+            const long key = tiles * 1024 + halo;
+            if (best < 0 || key < best) { best = key; bh = h; bw = w; }
+        }
     *th = bh; *tw = bw;
 }
 
