@@ -356,6 +356,36 @@ size_t use_spec_losses_workspace(int B, int64_t stride, int sampling_rate);
 int use_spec_losses(const float* est, const float* clean, const int* len_host, int B, int64_t stride, int sampling_rate,
                     void* work, size_t work_bytes, double* out_dev, use_stream_t s);
 
+/* Short-time objective intelligibility of an enhanced batch against its clean signals, handle-free: STOI (Taal et al. 2011) and ESTOI (Jensen &
+ * Taal 2016) as pystoi.stoi(clean, est, sampling_rate, extended) defines them - with SI-SDR (use_metrics) what the reference's validation loop
+ * reports (sgmse/util/inference.py: evaluate_model).  est, clean: float32 DEVICE [B][stride], item b valid for len_host[b] samples (HOST ints, as
+ * in use_metrics; the rest of a row is never read).  out_dev: fp64 DEVICE [B][USE_STOI_COUNT]: the two scores and T, the number of STFT frames
+ * they were taken over.  Per item:
+ *   1. both signals to 10 kHz: y[n] = sum_j x[j] h'[L + n q - j p], n < ceil(len p / q), p / q = 10000 / sampling_rate, x zero past both ends;
+ *      h' = p h / sum h, h = kaiser(2 L + 1, 0.1102 (60 - 8.7)) 2 p fc sinc(2 fc t), fc = 1 / (2 max(p, q)), L = ceil(52 / (2.8714 fc)), t = -L..L
+ *      (scipy.signal.resample_poly(x, p, q, window = h / sum h); 871 taps at 24 kHz).  10 kHz in: no filter.
+ *   2. frames of 256 at hop 128 under w = np.hanning(258)[1:-1]; frame k is kept iff max(E) - 40 - E_k < 0, E_k = 20 log10(|w clean_k| + 2^-52);
+ *      both signals are rebuilt by overlap-add of their own windowed kept frames (K kept frames: (K - 1) 128 + 256 samples).
+ *   3. T = K - 1 frames (start 128 i, i < K - 1) times w again, zero-padded to 512, |rfft|^2; 15 third-octave bands from 150 Hz:
+ *      tob[b][t] = sqrt(sum of bins [lo_b, hi_b)), edges 7 9 11 14 17 22 27 34 43 55 69 87 109 138 174 219.
+ *   4. segments m = 0 .. T - 30 of 30 frames.  STOI: per band row c = |x| / (|y| + eps), y' = min(c y, x (1 + 10^(15/20))), row means removed,
+ *      rows divided by (|.| + eps), d = sum x y' / (15 (T - 29)).  ESTOI: rows, then columns, freed of their mean and scaled to unit norm,
+ *      d = sum x_n y_n / (30 (T - 29)).  eps = 2^-52.  T < 30: both scores are 1e-5 (pystoi's value).
+ * Two departures from pystoi: ESTOI's eps * randn dither is left out, and a row or column whose sum of squares is exactly 0 is scaled by 0 (the
+ * dither's expectation) instead of 1 / 0 - exact zeros in est cannot turn a score into NaN.
+ * Precision: float32 samples in, everything after the load in fp64 (taps by Kaiser's I0 power series to convergence).  Every sum has a fixed
+ * order that depends on len[b] and the item's own data alone: an item's three values are the same bits in any batch, at any stride, in every
+ * run (no atomics; the kept frames are compacted by an integer scan and gathered, never scattered).  Row offsets b * stride are 64-bit.
+ * work: use_stoi_workspace(B, stride, sampling_rate) bytes of device scratch, 8-byte aligned (0: bad arguments).  Seven launches on `s` (+ one
+ * per 64 items for the lengths), no synchronisation, no allocation, nothing to zero between calls: K stays on the device, the grids are sized
+ * for no frame removed.  USE_E_INVALID (argument named in use_last_error(), nothing launched): a sampling_rate other than 10000 / 16000 /
+ * 24000 / 48000, B < 1 or > 65535, stride < 1, a null est / clean / len_host / work / out_dev, len[b] > stride, a len[b] whose resampled
+ * length ceil(len p / q) is under 256 (the minimum is 613 at 24 kHz), work_bytes too small. */
+enum { USE_STOI_STOI = 0, USE_STOI_ESTOI = 1, USE_STOI_FRAMES = 2, USE_STOI_COUNT = 3 };
+size_t use_stoi_workspace(int B, int64_t stride, int sampling_rate);
+int use_stoi(const float* est, const float* clean, const int* len_host, int B, int64_t stride, int sampling_rate,
+             void* work, size_t work_bytes, double* out_dev, use_stream_t s);
+
 /* Counters of a handle: "graph_captures" (segments of the sampling loop captured so far), "plans_built", "plan_cache_hits", "ode_steps",
  * "ode_rejected", "ode_nfev_max" (of the last use_sample_ode),
  * "plans_parked", "plan_stale" (1: use_set_option was called since use_plan - the evaluation entry points will refuse the plan).  A handle keeps the plans - workspace, state, time-embedding tables, captured graphs - of the most recently used

@@ -141,6 +141,8 @@ SYMBOLS = {
     "use_wav_handoff": (_i, [_vp, _vp, _i64, C.POINTER(_i), _i, _i, _i, _vp, C.c_size_t, _vp, _vp]),
     "use_spec_losses_workspace": (C.c_size_t, [_i, _i64, _i]),
     "use_spec_losses": (_i, [_vp, _vp, C.POINTER(_i), _i, _i64, _i, _vp, C.c_size_t, _vp, _vp]),
+    "use_stoi_workspace": (C.c_size_t, [_i, _i64, _i]),
+    "use_stoi": (_i, [_vp, _vp, C.POINTER(_i), _i, _i64, _i, _vp, C.c_size_t, _vp, _vp]),
     "use_sde_prior": (_i, [_vp, _vp, _vp, _u64, _vp, _i64, _vp]),
     "use_fill_noise": (_i, [_vp, _u64, _i, _vp, _i64, _vp]),
     "use_fill_noise_items": (_i, [_vp, C.POINTER(_u64), _i, _i, _vp, _i64, _vp]),

@@ -48,6 +48,9 @@
                                                   file and channel and a channel column; first by default)
         [data.clean_folder=clean/]               (score every enhanced file whose clean counterpart exists under clean/ at the same
                                                   relative path: SI-SDR / SI-SIR / SI-SAR / LSD on the device -> enhanced/metrics.csv)
+        [data.clean_folder=clean/ data.intelligibility=true]
+                                                 (two more columns of metrics.csv: STOI and ESTOI of the same files on the device, as
+                                                  pystoi defines them; a file with fewer than 30 frames gets 1e-5 and a warning)
         [data.clean_folder=clean/ data.convergence_losses=true]
                                                  (the same files against the refine stage's training objective, forward only: waveform
                                                   L1, multi-resolution STFT and log-mel distances on the device -> enhanced/losses.csv)
@@ -158,17 +161,28 @@ def _scored_files(batch: dict, clean_folder: str):
         yield r, c, rel, clean_path, noisy_path.replace(batch["data_folder"], batch["target_folder"])
 
 
+def _warn_short(rel: str, row: dict, what: str = ""):
+    """``data.intelligibility``: one line for a file too short for a STOI segment (its two scores are pystoi's 1e-5)."""
+    from .metrics import STOI_MIN_FRAMES
+    if row.get("stoi_frames", STOI_MIN_FRAMES) < STOI_MIN_FRAMES:
+        print(f"warning: {rel}{what}: {int(row['stoi_frames'])} frame(s) after the silent ones are removed, STOI needs {STOI_MIN_FRAMES}: "
+              f"stoi and estoi are {row['stoi']:g}", file=sys.stderr)
+
+
 def _score_batch(batch: dict, clean_folder: str, data_cfg: dict, device, est=None):
     """``data.clean_folder``: (relative path, metrics) of every file of the batch whose clean counterpart exists - the enhanced file as
     ``predict_step`` wrote it (``est``: its samples at the model's rate, item by item, where the files are not at that rate) against
     the clean file, the noisy input as the noise source (``metrics.score_files``)."""
     from .metrics import score_files
     rows = []
+    stoi = bool(data_cfg.get("intelligibility"))              # data.intelligibility: stoi and estoi join the row
     if "file_rows" in batch:                                  # data.channels=all: one row per (file, channel)
         for r, c, rel, clean_path, enhanced_path in _scored_files(batch, clean_folder):
             for k in range(c):
                 rows.append((rel, k, score_files(enhanced_path, clean_path, batch["audio_path"][r], int(data_cfg.get("sampling_rate", 24000) or 0),
-                                                 bool(data_cfg.get("normalize", True)), device, None if est is None else est[r + k], channel=k)))
+                                                 bool(data_cfg.get("normalize", True)), device, None if est is None else est[r + k], channel=k,
+                                                 intelligibility=stoi)))
+                _warn_short(rel, rows[-1][-1], f" channel {k}")
         return rows
     for i, noisy_path in enumerate(batch["audio_path"]):
         rel = os.path.relpath(noisy_path, batch["data_folder"])
@@ -176,7 +190,8 @@ def _score_batch(batch: dict, clean_folder: str, data_cfg: dict, device, est=Non
         if os.path.isfile(clean_path):
             enhanced_path = noisy_path.replace(batch["data_folder"], batch["target_folder"])
             rows.append((rel, score_files(enhanced_path, clean_path, noisy_path, int(data_cfg.get("sampling_rate", 24000) or 0),
-                                          bool(data_cfg.get("normalize", True)), device, None if est is None else est[i])))
+                                          bool(data_cfg.get("normalize", True)), device, None if est is None else est[i], intelligibility=stoi)))
+            _warn_short(rel, rows[-1][-1])
     return rows
 
 
@@ -227,6 +242,9 @@ def predict(cfg: dict):
     with_losses = bool(cfg["data"].get("convergence_losses"))   # off by default: nothing of it runs, no losses.csv is written
     if with_losses and not cfg["data"].get("clean_folder"):
         raise SystemExit("data.convergence_losses=true needs data.clean_folder=<the folder of the clean files>")
+    with_stoi = bool(cfg["data"].get("intelligibility"))       # off by default: nothing of it runs, metrics.csv keeps its four columns
+    if with_stoi and not cfg["data"].get("clean_folder"):
+        raise SystemExit("data.intelligibility=true needs data.clean_folder=<the folder of the clean files>")
     rank, world, local = D.init_from_env()
     torch.cuda.set_device(local)
     data = instantiate(cfg["data"], rank=rank, world_size=world)
@@ -262,8 +280,9 @@ def predict(cfg: dict):
             if with_losses:
                 loss_rows += _loss_batch(batch, clean_folder, cfg["data"], device, est)
     if clean_folder:
-        from .metrics import write_csv
-        write_csv(os.path.join(cfg["data"]["target_folder"], "metrics.csv" if world == 1 else f"metrics_rank{rank}.csv"), rows, per_channel)
+        from .metrics import NAMES, STOI_NAMES, write_csv
+        write_csv(os.path.join(cfg["data"]["target_folder"], "metrics.csv" if world == 1 else f"metrics_rank{rank}.csv"), rows, per_channel,
+                  NAMES + STOI_NAMES if with_stoi else NAMES)
     if with_losses:
         from .losses import write_csv as write_losses_csv
         write_losses_csv(os.path.join(cfg["data"]["target_folder"], "losses.csv" if world == 1 else f"losses_rank{rank}.csv"), loss_rows,

@@ -1,5 +1,6 @@
 """The part of the reference's ``sgmse/util/other.py`` this package has: ``pad_spec`` (``:128-135``) and the evaluation metrics
-``lsd``, ``si_sdr_components`` and ``energy_ratios`` (``:15-62``), names and argument order as there.
+``lsd``, ``si_sdr_components`` and ``energy_ratios`` (``:15-62``), names and argument order as there; and ``stoi`` with the signature of
+``pystoi.stoi``, which the reference's validation loop imports (``sgmse/util/inference.py``).
 
 ``pad_spec`` zero-pads the frame axis on the right to the next multiple of 64 so the 6 FIR down/up-samplings of NCSN++ round-trip.
 The two reductions run on the device (``universal_speech_enhancement_amd.metrics``, kernel file csrc/use_metrics.hip): they take
@@ -63,3 +64,11 @@ def energy_ratios(s_hat, s, n, eps=EPS, lengths=None):
     _check_eps(eps)
     (s_hat, s, n), was_numpy, was_1d = _to_device(s_hat, s, n)
     return tuple(_like_reference(v, was_numpy, was_1d) for v in metrics.energy_ratios(s_hat, s, n, lengths))
+
+
+def stoi(x, y, fs_sig, extended=False, lengths=None):
+    """``pystoi.stoi(x, y, fs_sig, extended)``: the clean signal FIRST, then the processed one; STOI, or ESTOI with ``extended``
+    (``use_stoi``, csrc/use_stoi.hip: without pystoi's dither, so the same inputs give the same bits)."""
+    from ... import metrics
+    (x, y), was_numpy, was_1d = _to_device(x, y)
+    return _like_reference(metrics.stoi(y, x, lengths, int(fs_sig), extended), was_numpy, was_1d)
