@@ -386,6 +386,65 @@ size_t use_stoi_workspace(int B, int64_t stride, int sampling_rate);
 int use_stoi(const float* est, const float* clean, const int* len_host, int B, int64_t stride, int sampling_rate,
              void* work, size_t work_bytes, double* out_dev, use_stream_t s);
 
+/* The degradation simulator of the training data, handle-free: what the reference's comm_distort_simu_dataset.__getitem__ does to a clean
+ * excerpt, per item of a batch on the device, for the stages named below (the others - EQ, STFT masks, codecs, ... - are not built).
+ * clean: float32 DEVICE [B][stride], item b valid for len_host[b] samples.  noise: float32 DEVICE [B][noise_stride] or null; the row of an
+ * item with add_noise holds noise_len_host[b] >= len[b] samples, of which the first len[b] are read.  rir: float32 DEVICE [B][rir_stride] or
+ * null; an item with reverb reads rir_len taps, already trimmed to start at the peak and divided by it (get_rir; the host's work).  packet:
+ * fp64 DEVICE [packet_count] factors or null; an item with packet_frame > 0 reads ceil(len / packet_frame) of them from packet_off.  params: HOST [B] records;
+ * the host draws every parameter, the device draws nothing.  Per item, in fp64 after the load, each stage optional:
+ *   1. reverb    full = (x * rir)[:len] (the noisy branch), early = (x * rir[:6])[:len] (the clean target).  early is a direct sum; full
+ *                is an FFT convolution at M = pow2 >= len + rir_len - 1: the transforms of x and of rir, their product, one inverse FFT.
+ *   2. add_noise P(w) = mean of w^2 over the samples librosa.effects.split(w, top_db = 50) keeps: frame RMS over 2048 samples at hop 512,
+ *                centred and zero-padded, 1 + len / 512 frames; frame k is kept iff 10 log10(max(1e-10, p_k)) - 10 log10(max(1e-10, max p))
+ *                > -50; sample s is kept iff frame s / 512 is.  scale = sqrt(P(clean) / (P(noise) + 1e-8) / snr_lin + 1e-8),
+ *                noisy = clean + scale * noise (clean: the full-reverb signal).  snr_lin = 10^(snr / 10).
+ *   3. loudness  n_loud intervals of len / n_loud samples, interval i times loud[i]; the tail is left as it is.
+ *   4. clip      USE_CLIP_HARD: clip(x, -clip_a, clip_a).  USE_CLIP_HARD_ON_RATE: numpy's 1000-bin histogram of |x| over [min, max]; the
+ *                threshold is the first left edge whose cumulative count exceeds (1 - clip_a) len.  USE_CLIP_SOFT: m x / (|m|^p + |x|^p +
+ *                1e-5)^(1 / p), m the signed maximum, p = clip_a.  USE_CLIP_SIGMOID1: (2 / (1 + exp(-clip_a x)) - 1) clip_b.
+ *                USE_CLIP_SIGMOID2: c = clip(x, -clip_a, clip_a), b = 1.5 c - 0.3 c^2, clip_b (2 / (1 + exp(-(b > 0 ? 4 : 0.5) b)) - 1).  Both
+ *                sigmoids times sqrt(mean x^2) / (sqrt(mean y^2) + 1e-8).  USE_CLIP_SOX and USE_CLIP_PEDAL are refused: not built.
+ *   5. dc        x + dc_offset.
+ *   6. packets   frame j of packet_frame samples (the last may be short) times packet[packet_off + j].
+ *   7. volume    USE_VOLUME_PEAK: both signals times volume_target / (max(peak_noisy, peak_clean) + 1e-6); USE_VOLUME_RMS: the level is
+ *                sqrt(P(.) + 1e-8) with stage 2's P.  Then both times 0.99 / peak iff the peak exceeds 0.99 (volume_clip_dual).  normalize:
+ *                both / max(peak_noisy, peak_clean) * 0.8, two roundings.
+ * perturbed, clean_out: DEVICE [B][stride] of float32 (out_fp64 = 0) or fp64 (1); the float32 value is the cast of the fp64 one, and both
+ * rows are zero from len[b] to stride.  scalars_dev: fp64 DEVICE [B][USE_DISTORT_SCALARS].  keep_dev: null, or uint8 DEVICE [B][2][keep_stride],
+ * keep_stride >= 1 + len / 512: the kept frames of stage 2 (clean, then noise), written for the items with add_noise.
+ * Every product and sum above is rounded once (no contraction), every reduction has a place fixed by len and rir_len alone: partials by
+ * plain store, re-reduced in a fixed order by one workgroup; the histogram counts are integers.  An item's rows and scalars are the same
+ * bits alone, at any row of any batch, at any stride, in every run.  The items run one after another on `s` and share only the workspace:
+ * use_distort_workspace(len, rir_len) bytes for the largest item (rir_len = 0: no reverb; 0: bad arguments), 16-byte aligned.  No
+ * synchronisation, no allocation.  USE_E_INVALID (argument named, nothing launched): a null clean / len_host / params / perturbed / clean_out
+ * / scalars_dev / work, B outside 1 ... 65535, len[b] < 1 or > stride, reverb with a null rir, rir_len < 1 or > rir_stride or len + rir_len
+ * - 1 > 2^24, add_noise with a null noise or noise_len[b] < len[b] or > noise_stride, an unknown or unbuilt clip_kind, a rate outside
+ * (0, 1], n_loud outside 0 ... 5, packet_frame < 0 (the stage is off at 0), a null packet or frames outside packet_count, an unknown volume mode, a non-finite
+ * parameter, a short workspace or keep_stride. */
+enum { USE_CLIP_NONE = 0, USE_CLIP_HARD = 1, USE_CLIP_HARD_ON_RATE = 2, USE_CLIP_SOFT = 3, USE_CLIP_SIGMOID1 = 4, USE_CLIP_SIGMOID2 = 5,
+       USE_CLIP_SOX = 6, USE_CLIP_PEDAL = 7 };
+enum { USE_VOLUME_NONE = 0, USE_VOLUME_PEAK = 1, USE_VOLUME_RMS = 2 };
+enum { USE_DISTORT_NOISE_SCALE = 0, USE_DISTORT_CLIP_THRESHOLD = 1, USE_DISTORT_VOLUME_SCALE = 2, USE_DISTORT_NORM_FACTOR = 3,
+       USE_DISTORT_CLIP_SCALE = 4, USE_DISTORT_P_CLEAN = 5, USE_DISTORT_P_NOISE = 6, USE_DISTORT_ENERGY_SCALE = 7, USE_DISTORT_SCALARS = 8 };
+typedef struct use_distort_params {
+    int reverb, rir_len;          /* stage 1 */
+    int add_noise;                /* stage 2 */
+    int n_loud;                   /* stage 3: 0 (off) ... 5 */
+    int clip_kind;                /* stage 4: USE_CLIP_* */
+    int dc;                       /* stage 5 */
+    int packet_frame;             /* stage 6: 0 (off), or the frame size in samples */
+    int volume, normalize;        /* stage 7: USE_VOLUME_*; output_normalize */
+    int reserved;
+    long long packet_off;
+    double snr_lin, loud[5], clip_a, clip_b, dc_offset, volume_target;
+} use_distort_params;
+size_t use_distort_workspace(int64_t len, int64_t rir_len);
+int use_distort(const float* clean, const float* noise, const float* rir, const double* packet, int64_t packet_count, const int* len_host,
+                const int* noise_len_host, const use_distort_params* params, int B, int64_t stride, int64_t noise_stride,
+                int64_t rir_stride, int out_fp64, void* perturbed, void* clean_out, double* scalars_dev, unsigned char* keep_dev,
+                int64_t keep_stride, void* work, size_t work_bytes, use_stream_t s);
+
 /* Counters of a handle: "graph_captures" (segments of the sampling loop captured so far), "plans_built", "plan_cache_hits", "ode_steps",
  * "ode_rejected", "ode_nfev_max" (of the last use_sample_ode),
  * "plans_parked", "plan_stale" (1: use_set_option was called since use_plan - the evaluation entry points will refuse the plan).  A handle keeps the plans - workspace, state, time-embedding tables, captured graphs - of the most recently used

@@ -81,6 +81,18 @@ class UseSamplerTraceEntry(C.Structure):
                 ("noise", C.c_void_p)]
 
 
+CLIP_KINDS = {"none": 0, "hard": 1, "hard_on_rate": 2, "soft": 3, "sigmoid1": 4, "sigmoid2": 5, "sox": 6, "pedal": 7}      # USE_CLIP_*
+VOLUME_MODES = {"none": 0, "peak": 1, "rms": 2}                                                                        # USE_VOLUME_*
+DISTORT_SCALARS = ("noise_scale", "clip_threshold", "volume_scale", "norm_factor", "clip_scale", "p_clean", "p_noise", "energy_scale")
+
+
+class UseDistortParams(C.Structure):
+    _fields_ = ([(k, C.c_int) for k in ("reverb", "rir_len", "add_noise", "n_loud", "clip_kind", "dc", "packet_frame", "volume", "normalize",
+                                        "reserved")] +
+                [("packet_off", C.c_longlong), ("snr_lin", C.c_double), ("loud", C.c_double * 5), ("clip_a", C.c_double),
+                 ("clip_b", C.c_double), ("dc_offset", C.c_double), ("volume_target", C.c_double)])
+
+
 class UseHipError(RuntimeError):
     pass
 
@@ -143,6 +155,9 @@ SYMBOLS = {
     "use_spec_losses": (_i, [_vp, _vp, C.POINTER(_i), _i, _i64, _i, _vp, C.c_size_t, _vp, _vp]),
     "use_stoi_workspace": (C.c_size_t, [_i, _i64, _i]),
     "use_stoi": (_i, [_vp, _vp, C.POINTER(_i), _i, _i64, _i, _vp, C.c_size_t, _vp, _vp]),
+    "use_distort_workspace": (C.c_size_t, [_i64, _i64]),
+    "use_distort": (_i, [_vp, _vp, _vp, _vp, _i64, C.POINTER(_i), C.POINTER(_i), C.POINTER(UseDistortParams), _i, _i64, _i64, _i64, _i, _vp, _vp,
+                         _vp, _vp, _i64, _vp, C.c_size_t, _vp]),
     "use_sde_prior": (_i, [_vp, _vp, _vp, _u64, _vp, _i64, _vp]),
     "use_fill_noise": (_i, [_vp, _u64, _i, _vp, _i64, _vp]),
     "use_fill_noise_items": (_i, [_vp, C.POINTER(_u64), _i, _i, _vp, _i64, _vp]),
